@@ -17,16 +17,23 @@ stream, served from L2 / Infinity Cache) is reported beside it, not as `value`.
 Multi-GPU (driver: python -m torch.distributed.run --nproc-per-node N bench.py
 --gpus N ...): channels shard over ranks (32 per GPU, BASELINE configs[4]), no
 data-path collective; RCCL is used only for the barrier and the max-over-ranks
-of the elapsed time.  scaling = "weak".  Behind the headline region every rank
-also times ITS share of BASELINE configs[4] (16 GPS L1 C/A + 8 Galileo E1 5-tap
-+ 8 BeiDou B1I channels, open loop) and its PRNs of the configs[3] search
+of the elapsed time.  scaling = "weak".  With --full, behind the headline region
+every rank also times ITS share of BASELINE configs[4] (16 GPS L1 C/A + 8 Galileo
+E1 5-tap + 8 BeiDou B1I channels, open loop) and its PRNs of the configs[3] search
 (PRN i on GPU (i - 1) mod G); both travel in `per_gpu[]`, their sums in
 `hybrid_all_gpus` / `acquisition_all_gpus`.
 
 The headline is the contract's region: W warm-up steps, then K timed steps
-(no pre-roll by default).  On this chip that region lies inside a start-of-load
-power transient; the figure after ~10 ms of load is reported beside it as
-`roofline.steady_state_frac` (and `--preroll-ms 15` moves the timed region there).
+(no pre-roll by default).  A plain run does that alone: set-up, warm-up, the K
+timed steps, the outputs of the last step when --dump-outputs DIR is given
+(DIR/correlators.npy: float32 (channels, epochs, taps, re/im), the E/P/L values
+a caller of the batched launch receives; seeded inputs, the same every run), and
+the JSON line.  --full adds everything else behind the timed region: the
+diagnostic pass (on this chip the contract's region lies inside a start-of-load
+power transient; the figure after ~10 ms of load is reported as
+`roofline.steady_state_frac`, and `--preroll-ms 15` moves the timed region
+there), the sanity check of the prompt correlators, the other entries of the
+line with their rooflines, acquisition and the CPU baselines.
 """
 import argparse
 import json
@@ -223,7 +230,14 @@ def main():
     ap.add_argument("--preroll-ms", type=float, default=0.0, help="untimed launches of the same step IN FRONT of the W warm-up steps, "
         "about this many ms of GPU time (named in the JSON line as `preroll`).  Default 0: the headline is the contract's region, W "
         "warm-up steps then K timed ones; the steady-state figure is reported beside it as roofline.steady_state_frac")
+    ap.add_argument("--full", action="store_true", help="behind the timed region, also run the diagnostic pass, the sanity check, the other "
+        "entries of the line, acquisition and the CPU baselines (--segments, --no-shared, --no-acq, --acq-*, --no-cpu, --cpu-seconds "
+        "shape them); a plain run measures the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed to DIR/correlators.npy "
+        "(float32, channels x epochs x taps x re/im; correlators_rank<r>.npy per rank with several GPUs)")
     args = ap.parse_args()
+    if not args.full:
+        args.segments, args.no_shared, args.no_acq, args.no_cpu = 0, True, True, True
 
     import torch
     import gnsscorr
@@ -324,6 +338,12 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     kernel_ms = float(ev0.elapsed_time(ev1)) / args.steps
+    # what the last timed step handed its caller, read before any --full entry reuses d_out.  768 B per epoch: 64 MB would take
+    # E > 87000, whose IQ buffers (200 kB per channel-epoch) no GPU holds
+    out = d_out.cpu().numpy().reshape(N_CHANNELS, E, N_TAPS, 2) if (args.full or args.dump_outputs) else None
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "correlators.npy" if world == 1 else "correlators_rank%d.npy" % rank), out)
 
     # ---- diagnostic pass, OUTSIDE the timed region and after it (it changes neither `value` nor `ms_per_step` nor `kernel_ms`):
     # the same lead-in as the timed region (W warm-up launches from an idle GPU, synchronise), then SEG_LEN x n_seg back-to-back
@@ -367,7 +387,7 @@ def main():
         "steady_state_hbm_frac": (alg_bytes / (steady_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS) if steady_ms else None,
         "cold_start_kernel_ms": cold_ms}
 
-    vceil = load_valu_ceilings()
+    vceil = load_valu_ceilings() if args.full else {}
 
     # ---- BASELINE configs[4], one GPU's share: 32 channels = 16 GPS L1 C/A + 8 Galileo E1 (5 taps, 4 ms) + 8 BeiDou B1I, open loop.
     # EVERY rank times its own share (gnss_flowgraph.cc:496-499: every channel hangs on the one conditioner output; here channel g of
@@ -522,7 +542,7 @@ def main():
     # every rank's share of BASELINE configs[4] (the hybrid mix) and of configs[3] (its PRNs of the 32), timed behind the headline
     # region with no barrier in between: nothing waits on another rank's extras; the figures travel in per_gpu[]
     share = None
-    if world > 1 or not (args.no_shared and args.no_acq):
+    if args.full and (world > 1 or not (args.no_shared and args.no_acq)):
         share = {"hybrid": None, "acquisition": None}
         if world > 1 or not args.no_shared:
             share["hybrid"] = run_hybrid()
@@ -540,10 +560,10 @@ def main():
     per_gpu = sharding.gather_per_rank(mine, dist, world)
 
     # sanity: the prompt correlators see their signals (guards against timing a broken path)
-    out = d_out.cpu().numpy().reshape(N_CHANNELS, E, N_TAPS, 2)
-    pmag = np.hypot(out[:, :, 1, 0], out[:, :, 1, 1]).mean(axis=1)
-    expect = np.array([t["amp"] * N_EPOCH for t in truths])
-    assert np.all(pmag > 0.5 * expect), "prompt correlators lost the signal"
+    if args.full:
+        pmag = np.hypot(out[:, :, 1, 0], out[:, :, 1, 1]).mean(axis=1)
+        expect = np.array([t["amp"] * N_EPOCH for t in truths])
+        assert np.all(pmag > 0.5 * expect), "prompt correlators lost the signal"
 
     result = None
     if rank == 0:

@@ -6,7 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 import bench
 n, e = int(sys.argv[1]), int(sys.argv[2])
 bench.N_EPOCH = n
-sys.argv = ['bench.py', '--no-cpu', '--no-acq', '--no-shared', '--epochs', str(e), '--steps', '20']
+sys.argv = ['bench.py', '--full', '--no-cpu', '--no-acq', '--no-shared', '--epochs', str(e), '--steps', '20']
 try:
     bench.main()
 except AssertionError as ex:
