@@ -213,6 +213,7 @@ API = {
     "gc_trk_loop_stop": (C.c_int, [_vp, C.c_int]),
     "gc_trk_loop_run_dev": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "gc_trk_loop_set_geometry": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "gc_trk_loop_set_mixed": (C.c_int, [_vp, C.c_int]),
     "gc_trk_loop_run": (C.c_int, [_vp, C.c_int, _vp]),
     "gc_gps_l1_ca_code_gen_float": (C.c_int, [_fp, C.c_int32, C.c_uint32]),
     "gc_gps_l1_ca_code_gen_complex_sampled": (C.c_int, [_fp, C.c_uint32, C.c_int32, C.c_uint32, C.POINTER(C.c_int32)]),
@@ -740,11 +741,22 @@ class TrackingBatch:
 class TrackingLoop:
     """gc_trk_loop: closed-loop DLL/PLL tracking on the device (correlations + loop maths per epoch in one launch)."""
 
-    def __init__(self, ctx, n_channels, max_code_length):
+    def __init__(self, ctx, n_channels, max_code_length, mixed=False):
         self._ctx = ctx
         self.n_channels = n_channels
         self._h = _vp()
         _check(load_library().gc_trk_loop_create(ctx._h, n_channels, max_code_length, C.byref(self._h)))
+        if mixed:
+            try:
+                self.set_mixed(True)
+            except BaseException:
+                self.close()
+                raise
+
+    def set_mixed(self, on=True):
+        """Mixed mode (gc_trk_loop_set_mixed): each channel its own tap count, pilot mode, code length and period, all in
+        one launch.  Only while no channel is started."""
+        _check(load_library().gc_trk_loop_set_mixed(self._h, 1 if on else 0))
 
     def set_input_dev(self, ch, dev_ptr, n_samples):
         _check(load_library().gc_trk_loop_set_input_dev(self._h, ch, _vp(dev_ptr), int(n_samples)))

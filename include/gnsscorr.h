@@ -327,7 +327,8 @@ typedef struct
  * (dll_pll_veml_tracking.cc:1730-1770, 1898-1906) and to its binary dump (:1196-1243). */
 typedef struct
 {
-    float corr[10];              /* n_taps complex correlator outputs (re, im) */
+    float corr[10];              /* n_taps complex correlator outputs (re, im); in a mixed engine (gc_trk_loop_set_mixed)
+                                  * each channel's own tap count */
     float carrier_doppler_hz, code_freq_chips;
     float carr_phase_error_hz, carr_error_filt_hz, code_error_chips, code_error_filt_chips;
     float cn0_db_hz, carrier_lock_test;
@@ -388,10 +389,13 @@ gc_status gc_trk_loop_set_input_dev(gc_trk_loop* l, int ch, const void* dev_iq, 
 gc_status gc_trk_loop_set_input_stream(gc_trk_loop* l, int ch, gc_stream* s);
 /* Installs (sync != NULL) or removes the synchronisation / extension description of channel `ch`; it takes effect at the
  * next gc_trk_loop_start.  data_code (data_code_length floats, same length as the tracking replica) is required with
- * track_pilot and ignored otherwise.  All channels of one engine share the pilot mode. */
+ * track_pilot and ignored otherwise.  All channels of a default engine share the pilot mode; a mixed engine
+ * (gc_trk_loop_set_mixed) takes it per channel. */
 gc_status gc_trk_loop_set_sync(gc_trk_loop* l, int ch, const gc_loop_sync_conf* sync, const float* data_code, int data_code_length);
 /* dll_pll_veml_tracking::start_tracking (:549-747): uploads the replica (code_length_chips *
- * code_samples_per_chip floats), sets the taps from the spacings and initialises the loop. */
+ * code_samples_per_chip floats), sets the taps from the spacings and initialises the loop.  In a default engine every
+ * running channel has the same tap count (veml) and pilot mode; a mixed engine (gc_trk_loop_set_mixed) lifts both checks.
+ * The high_dyn mode is always shared by the running channels of one engine. */
 gc_status gc_trk_loop_start(gc_trk_loop* l, int ch, const gc_loop_conf* conf, const float* code, int code_length);
 /* Puts channel `ch` back in standby (all-zero records, state 0) until the next gc_trk_loop_start; channels that were never
  * started are in the same state, so an engine can be sized for the receiver's channel count and filled as acquisitions succeed. */
@@ -403,6 +407,15 @@ gc_status gc_trk_loop_stop(gc_trk_loop* l, int ch);
  * per code period, the last slice to finish runs the loop maths) measured slower than one workgroup per channel (13.4 vs 11.4 us per
  * period at 32 channels) and is accepted by experiments builds only; the product library takes 0 or 1. */
 gc_status gc_trk_loop_set_geometry(gc_trk_loop* l, int threads_per_workgroup, int slices_per_channel);
+/* Mixed mode (on != 0): every channel slot carries its own tap count (3 or 5), pilot mode, code length and code period, and
+ * all channels still run in one launch on one stream (a hybrid receiver: GPS L1 C/A, Galileo E1 and BeiDou B1I slots on one
+ * RF stream).  The launch sizes its LDS code image for the largest need among the started channels.  Run semantics do not
+ * change: n_epochs is the capacity per channel, and a channel whose input ends (the n_samples of gc_trk_loop_set_input_dev,
+ * or the ring's head) writes invalid records after that, so a caller that wants T seconds of every channel sizes n_epochs
+ * for the SHORTEST code period (64 ms of GPS: 64 records, of which a 4 ms Galileo E1 channel fills 16).  high_dyn stays
+ * engine-wide.  Allowed only while no channel is started (GC_ERR_STATE otherwise); a mixed engine runs one workgroup per
+ * channel (no slices_per_channel > 1). */
+gc_status gc_trk_loop_set_mixed(gc_trk_loop* l, int on);
 gc_status gc_trk_loop_run_dev(gc_trk_loop* l, int n_epochs, gc_loop_record* dev_records, void* stream);
 gc_status gc_trk_loop_run(gc_trk_loop* l, int n_epochs, gc_loop_record* host_records);
 
