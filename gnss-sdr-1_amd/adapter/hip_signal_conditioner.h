@@ -1,0 +1,126 @@
+/*!
+ * \file hip_signal_conditioner.h
+ * \brief The signal conditioner of one RF source on the GPU: data-type adapter + frequency-translating FIR input filter + decimation,
+ * writing the RF stream ring that hip_acquisition_bank and hip_tracking_group read.
+ *
+ * In the reference a signal conditioner (data_type_adapter, input_filter, resampler) sits between every source and its channels
+ * (gnss_flowgraph.cc:496-499); for a capture at an intermediate frequency or from a wide-band front end the input filter is
+ * Freq_Xlating_Fir_Filter (src/algorithms/input_filter/adapters/freq_xlating_fir_filter.cc).  This class takes that adapter's
+ * configuration keys under its role --
+ *   IF                   [Hz]  frequency moved to 0                           (default 0)
+ *   sampling_frequency   [Hz]  rate of the raw samples                        (default 4000000)
+ *   decimation_factor          D, 1..64                                       (default 1)
+ *   input_item_type            "gr_complex" | "cshort" | "cbyte"              (default "gr_complex")
+ *   filter_type                "lowpass": a windowed-sinc design from bw / tw (gc_fir_low_pass, the counterpart of
+ *                              gr::filter::firdes::low_pass(1.0, sampling_frequency, bw, tw)); anything else: the caller passes
+ *                              the taps (e.g. a Remez design from the band keys) to the constructor
+ *   bw, tw               [Hz]  cut-off and transition width                   (defaults (sampling_frequency / D) / 2 and bw / 10)
+ * -- owns a GC_IQ_F32 ring at sampling_frequency / D plus the device conditioner (gc_conditioner) that writes it, and hands the ring to
+ * the acquisition bank and the tracking group.  The output item type is always gr_complex.  general_work of the source-side block
+ * calls push(items, n); everything downstream addresses the ring by sample number at the OUTPUT rate.  The filter delays the signal
+ * by group_delay_samples() output samples; as in the reference, that is left in the observables.
+ */
+#ifndef GNSSCORR_HIP_SIGNAL_CONDITIONER_H_
+#define GNSSCORR_HIP_SIGNAL_CONDITIONER_H_
+
+#include "gnss_sdr_types.h"
+#include <string>
+#include <vector>
+
+class hip_signal_conditioner
+{
+public:
+    /*! ring_capacity / max_window: size of the output ring and its longest window, in OUTPUT samples (gc_stream_create);
+     *  taps: used unless filter_type is "lowpass" */
+    hip_signal_conditioner(gc_ctx* ctx, ConfigurationInterface* configuration, const std::string& role, uint64_t ring_capacity, uint32_t max_window,
+        const std::vector<float>& taps = std::vector<float>())
+        : d_role(role), d_taps(taps)
+    {
+        d_if = configuration->property(role + ".IF", 0.0);
+        d_fs_in = configuration->property(role + ".sampling_frequency", 4000000.0);
+        d_decimation = configuration->property(role + ".decimation_factor", static_cast<int32_t>(1));
+        d_item_type = configuration->property(role + ".input_item_type", std::string("gr_complex"));
+        const std::string filter_type = configuration->property(role + ".filter_type", std::string("bandpass"));
+        int format = GC_IQ_F32;
+        if (d_item_type == "gr_complex") format = GC_IQ_F32;
+        else if (d_item_type == "cshort") format = GC_IQ_I16;
+        else if (d_item_type == "cbyte") format = GC_IQ_I8;
+        else
+            {
+                d_status = GC_ERR_INVALID;
+                return;
+            }
+        if (d_decimation < 1 || d_fs_in <= 0.0)
+            {
+                d_status = GC_ERR_INVALID;
+                return;
+            }
+        if (filter_type == "lowpass")
+            {
+                const double bw = configuration->property(role + ".bw", (d_fs_in / d_decimation) / 2.0);
+                const double tw = configuration->property(role + ".tw", bw / 10.0);
+                int n = 0;
+                d_status = gc_fir_low_pass(1.0, d_fs_in, bw, tw, nullptr, 0, &n);
+                if (d_status != GC_OK) return;
+                d_taps.assign(static_cast<size_t>(n), 0.0f);
+                d_status = gc_fir_low_pass(1.0, d_fs_in, bw, tw, d_taps.data(), n, &n);
+                if (d_status != GC_OK) return;
+            }
+        gc_conditioner_conf c;
+        c.fs_in = d_fs_in;
+        c.translate_hz = d_if;
+        c.decimation = static_cast<uint32_t>(d_decimation);
+        c.n_taps = static_cast<uint32_t>(d_taps.size());
+        c.in_format = format;
+        c.reserved = 0;
+        d_status = gc_stream_create(ctx, GC_IQ_F32, ring_capacity, max_window, &d_ring);
+        if (d_status == GC_OK) d_status = gc_conditioner_create(ctx, &c, d_taps.data(), d_ring, &d_cond);
+    }
+    ~hip_signal_conditioner()
+    {
+        if (d_cond) gc_conditioner_destroy(d_cond);
+        if (d_ring) gc_stream_destroy(d_ring);
+    }
+    hip_signal_conditioner(const hip_signal_conditioner&) = delete;
+    hip_signal_conditioner& operator=(const hip_signal_conditioner&) = delete;
+
+    //! the conditioned ring: pass it to hip_acquisition_bank / hip_tracking_group together with fs_out()
+    gc_stream* ring() const { return d_ring; }
+    //! GNSS-SDR.internal_fs_sps of everything downstream
+    double fs_out() const { return d_fs_in / d_decimation; }
+    double fs_in() const { return d_fs_in; }
+    int decimation() const { return d_decimation; }
+    const std::vector<float>& taps() const { return d_taps; }
+    //! delay of a symmetric filter, in output samples
+    double group_delay_samples() const { return d_taps.empty() ? 0.0 : (static_cast<double>(d_taps.size()) - 1.0) / 2.0 / d_decimation; }
+    size_t item_size() const { return d_item_type == "gr_complex" ? 8 : d_item_type == "cshort" ? 4 : 2; }
+    std::string role() const { return d_role; }
+    std::string implementation() const { return "Freq_Xlating_Fir_Filter"; }
+
+    /*! n_items raw items of input_item_type; first_out / n_out (optional): the outputs they completed.  Asynchronous. */
+    gc_status push(const void* items, uint64_t n_items, uint64_t* first_out = nullptr, uint64_t* n_out = nullptr)
+    {
+        if (d_cond == nullptr) return d_status;  // construction failed
+        d_status = gc_conditioner_push(d_cond, items, n_items, first_out, n_out);
+        return d_status;
+    }
+    //! output samples produced so far (the ring's head)
+    uint64_t head() const
+    {
+        uint64_t h = 0;
+        if (d_cond) gc_conditioner_info(d_cond, nullptr, &h);
+        return h;
+    }
+    gc_status last_status() const { return d_status; }
+
+private:
+    std::string d_role, d_item_type;
+    std::vector<float> d_taps;
+    double d_if = 0.0, d_fs_in = 0.0;
+    int32_t d_decimation = 1;
+    gc_stream* d_ring = nullptr;
+    gc_conditioner* d_cond = nullptr;
+    gc_status d_status = GC_OK;
+};
+
+#endif  // GNSSCORR_HIP_SIGNAL_CONDITIONER_H_

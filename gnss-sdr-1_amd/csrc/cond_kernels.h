@@ -1,0 +1,36 @@
+// cond_kernels.h -- launcher of the signal conditioner kernel: frequency-translating FIR decimator (mix down, low-pass, decimate)
+// from a ring of raw samples into a piece of an RF stream ring (gc_stream) and its mirror.
+#ifndef COND_KERNELS_H
+#define COND_KERNELS_H
+#include "gnsscorr.h"
+#include <hip/hip_runtime.h>
+
+#define GC_COND_MAX_DECIMATION 64
+#define GC_COND_MAX_TAPS 1024
+#define GC_COND_THREADS 256
+#define GC_COND_LDS_SAMPLES 8192  // float2 entries of one workgroup's input tile (64 KiB)
+
+// One piece of outputs that is contiguous in the output ring.
+struct CondJob
+{
+    const void* raw;               // raw ring (HBM): raw sample n lives at n % raw_cap; raw_cap is a multiple of 8 samples and the
+                                   // allocation is 16-byte aligned, so an aligned 16-byte vector never straddles the wrap
+    unsigned raw_cap;
+    const float* taps;             // n_taps floats (HBM), read with uniform (scalar) loads
+    int n_taps;
+    int decimation;
+    unsigned long long phase_inc;  // turns per input sample in units of 2^-64; 0 = no mixer
+    unsigned long long first_out;  // absolute number m of the first output of the piece
+    unsigned n_out;                // outputs in the piece
+    float2* dst;                   // where output first_out goes (ring position first_out % capacity)
+    float2* mirror_dst;            // the same position behind the ring
+    unsigned n_mirror;             // the first n_mirror outputs of the piece are stored to mirror_dst as well
+};
+
+// Outputs per workgroup for a launch (a multiple of 64, at most 1024): as many as fit in GC_COND_LDS_SAMPLES, fewer when the
+// launch would not reach `want_groups` workgroups.  Results never depend on it.
+int cond_tile_outputs(int decimation, int n_taps, unsigned n_out, int want_groups);
+// Enqueues the conditioner for one piece on `st`.  iq_format: format of the raw ring.
+hipError_t cond_launch(int iq_format, hipStream_t st, const CondJob& job, int tile_outputs);
+
+#endif

@@ -1,0 +1,208 @@
+// cond_kernels.hip -- the signal conditioner's kernel (gfx950): frequency-translating FIR decimator, the device image of the
+// reference's Freq_Xlating_Fir_Filter input filter (src/algorithms/input_filter/adapters/freq_xlating_fir_filter.cc):
+//
+//   y[m] = sum_{k=0}^{T-1} h[k] * x[mD - k] * exp(-j 2 pi phi(mD - k)),   phi(n) = ((n * inc) mod 2^64) >> 32  [2^-32 turns]
+//
+// One workgroup produces a tile of outputs.  It loads the (tile - 1) D + T raw samples the tile needs with 16-byte loads, converts
+// (plain cast) and mixes each of them ONCE, and stores them to LDS in polyphase order: input i of the tile at row i % D, column
+// i / D.  Output j, tap k reads input j D + (T - 1 - k), i.e. row (T - 1 - k) % D -- the same for every lane -- and column
+// j + (T - 1 - k) / D: the 64 lanes of a wave read 64 consecutive float2 for any D (ds_read_b64, no bank conflict; a flat layout
+// would be read with a stride of 2 D dwords, a D-way conflict for D = 2, 4, 8 ...).  Rows are an odd number of float2 long, which
+// spreads the D rows a wave's mixed samples are written to over the banks.  The taps are read with uniform (scalar) loads; every
+// output accumulates in float32 in tap order k = 0 .. T-1, so an output's bits do not depend on the tile it falls in.
+#include "cond_kernels.h"
+
+typedef float cond_f32x4 __attribute__((ext_vector_type(4)));
+typedef short cond_i16x8 __attribute__((ext_vector_type(8)));
+typedef signed char cond_i8x16 __attribute__((ext_vector_type(16)));
+
+// 16 bytes of raw samples
+template <int FMT>
+struct CondRaw;
+template <>
+struct CondRaw<GC_IQ_F32>
+{
+    typedef cond_f32x4 vec;
+    static constexpr int N = 2, ELEM = 8;
+};
+template <>
+struct CondRaw<GC_IQ_I16>
+{
+    typedef cond_i16x8 vec;
+    static constexpr int N = 4, ELEM = 4;
+};
+template <>
+struct CondRaw<GC_IQ_I8>
+{
+    typedef cond_i8x16 vec;
+    static constexpr int N = 8, ELEM = 2;
+};
+
+// (cos, sin) of 2 pi phase / 2^32.  The argument reduction is exact: the nearest quarter turn comes from the top bits, the signed
+// remainder (|r| <= 2^29) is an angle in [-pi/4, pi/4] that float32 holds to 2^-24 of its size (<= 4.7e-8 rad).  Taylor
+// polynomials to x^9 / x^8: truncation below 2.5e-8 on that interval.
+static __device__ __forceinline__ float2 cond_cos_sin(unsigned phase)
+{
+    const unsigned q = (phase + 0x20000000u) >> 30;
+    const int r = (int)(phase - (q << 30));
+    const float x = (float)r * 1.4629180792671596e-9f;  // (pi / 2) / 2^30
+    const float x2 = x * x;
+    float s = fmaf(x2, 2.7557319224e-6f, -1.9841269841e-4f);
+    s = fmaf(s, x2, 8.3333333333e-3f);
+    s = fmaf(s, x2, -1.6666666667e-1f);
+    s = fmaf(x * x2, s, x);
+    float c = fmaf(x2, 2.4801587302e-5f, -1.3888888889e-3f);
+    c = fmaf(c, x2, 4.1666666667e-2f);
+    c = fmaf(c, x2, -0.5f);
+    c = fmaf(c, x2, 1.0f);
+    switch (q & 3u)
+        {
+        case 0: return float2{c, s};
+        case 1: return float2{-s, c};
+        case 2: return float2{-c, -s};
+        default: return float2{s, -c};
+        }
+}
+
+template <int FMT, int R, bool MIX>
+__global__ __launch_bounds__(GC_COND_THREADS) void cond_fir_decim_kernel(const CondJob job, const int tile, const int rowlen)
+{
+    extern __shared__ float2 cond_lds[];
+    typedef typename CondRaw<FMT>::vec vec;
+    constexpr int S = CondRaw<FMT>::N;
+    const int tid = threadIdx.x;
+    const int D = job.decimation, T = job.n_taps;
+    const unsigned o0 = blockIdx.x * (unsigned)tile;  // first output of the tile, counted in the piece
+    const int tn = (int)min((unsigned)tile, job.n_out - o0);
+    const long long a0 = (long long)(job.first_out + o0) * D - (T - 1);  // absolute number of the tile's first input (< 0: zeros)
+    const int count = (tn - 1) * D + T;
+    // whole 16-byte vectors from the boundary below a0; those below sample 0 read as zeros
+    const long long av = a0 & ~(long long)(S - 1);
+    const int n_vec = (int)((a0 + count - av + S - 1) / S);
+    const unsigned long long avp = av < 0 ? 0ull : (unsigned long long)av;
+    const unsigned base = (unsigned)(avp % job.raw_cap);
+    for (int v = tid; v < n_vec; v += GC_COND_THREADS)
+        {
+            const long long nv = av + (long long)v * S;
+            vec raw = vec(0);
+            if (nv >= 0)
+                {
+                    unsigned pos = base + (unsigned)(nv - (long long)avp);  // count + S < raw_cap: at most one wrap
+                    if (pos >= job.raw_cap) pos -= job.raw_cap;
+                    raw = *reinterpret_cast<const vec*>(static_cast<const char*>(job.raw) + (size_t)pos * CondRaw<FMT>::ELEM);
+                }
+#pragma unroll
+            for (int e = 0; e < S; e++)
+                {
+                    const int i = (int)(nv + e - a0);
+                    if (i < 0 || i >= count) continue;
+                    float2 x = float2{(float)raw[2 * e], (float)raw[2 * e + 1]};
+                    if (MIX && nv >= 0)
+                        {
+                            const unsigned phase = (unsigned)((((unsigned long long)(nv + e)) * job.phase_inc) >> 32);
+                            const float2 cs = cond_cos_sin(phase);
+                            // x * (cos - j sin)
+                            x = float2{fmaf(x.x, cs.x, x.y * cs.y), fmaf(x.y, cs.x, -(x.x * cs.y))};
+                        }
+                    const unsigned row = (unsigned)i % (unsigned)D, col = (unsigned)i / (unsigned)D;
+                    cond_lds[row * (unsigned)rowlen + col] = x;
+                }
+        }
+    __syncthreads();
+
+    // lanes past the end of a short tile read the last output's samples and store nothing
+    int j[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) j[r] = min(tid + r * GC_COND_THREADS, tn - 1);
+    float2 acc[R];
+    int row = (T - 1) % D, q = (T - 1) / D;
+    {
+        const float h = job.taps[0];
+        const float2* p = cond_lds + row * rowlen + q;
+#pragma unroll
+        for (int r = 0; r < R; r++)
+            {
+                const float2 x = p[j[r]];
+                acc[r] = float2{h * x.x, h * x.y};
+            }
+    }
+    for (int k = 1; k < T; k++)
+        {
+            if (--row < 0)
+                {
+                    row = D - 1;
+                    q--;
+                }
+            const float h = job.taps[k];
+            const float2* p = cond_lds + row * rowlen + q;
+#pragma unroll
+            for (int r = 0; r < R; r++)
+                {
+                    const float2 x = p[j[r]];
+                    acc[r].x = fmaf(h, x.x, acc[r].x);
+                    acc[r].y = fmaf(h, x.y, acc[r].y);
+                }
+        }
+#pragma unroll
+    for (int r = 0; r < R; r++)
+        {
+            const int jj = tid + r * GC_COND_THREADS;
+            if (jj >= tn) continue;
+            const unsigned o = o0 + (unsigned)jj;
+            job.dst[o] = acc[r];
+            if (o < job.n_mirror) job.mirror_dst[o] = acc[r];  // the mirror is written here: no HBM-to-HBM copy follows
+        }
+}
+
+static int cond_rowlen(int decimation, int n_taps, int tile) { return (tile + (n_taps - 1) / decimation) | 1; }
+
+int cond_tile_outputs(int decimation, int n_taps, unsigned n_out, int want_groups)
+{
+    int tile = 1024;
+    while (tile > 64 && decimation * cond_rowlen(decimation, n_taps, tile) > GC_COND_LDS_SAMPLES) tile /= 2;
+    while (tile > GC_COND_THREADS && (n_out + (unsigned)tile - 1) / (unsigned)tile < (unsigned)want_groups) tile /= 2;
+    return tile;
+}
+
+template <int FMT, int R>
+static void cond_launch_r(bool mix, dim3 grid, size_t lds_bytes, hipStream_t st, const CondJob& job, int tile, int rowlen)
+{
+    if (mix)
+        hipLaunchKernelGGL((cond_fir_decim_kernel<FMT, R, true>), grid, dim3(GC_COND_THREADS), lds_bytes, st, job, tile, rowlen);
+    else
+        hipLaunchKernelGGL((cond_fir_decim_kernel<FMT, R, false>), grid, dim3(GC_COND_THREADS), lds_bytes, st, job, tile, rowlen);
+}
+
+template <int FMT>
+static void cond_launch_fmt(dim3 grid, size_t lds_bytes, hipStream_t st, const CondJob& job, int tile, int rowlen)
+{
+    const bool mix = job.phase_inc != 0;
+    if (tile <= GC_COND_THREADS)
+        cond_launch_r<FMT, 1>(mix, grid, lds_bytes, st, job, tile, rowlen);
+    else if (tile <= 2 * GC_COND_THREADS)
+        cond_launch_r<FMT, 2>(mix, grid, lds_bytes, st, job, tile, rowlen);
+    else
+        cond_launch_r<FMT, 4>(mix, grid, lds_bytes, st, job, tile, rowlen);
+}
+
+hipError_t cond_launch(int iq_format, hipStream_t st, const CondJob& job, int tile)
+{
+    if (job.n_out == 0) return hipSuccess;
+    if (job.decimation < 1 || job.decimation > GC_COND_MAX_DECIMATION || job.n_taps < 1 || job.n_taps > GC_COND_MAX_TAPS || tile < 64 ||
+        tile > 4 * GC_COND_THREADS || (job.raw_cap & 7u) != 0)
+        return hipErrorInvalidValue;
+    const int rowlen = cond_rowlen(job.decimation, job.n_taps, tile);
+    const size_t lds_samples = (size_t)job.decimation * rowlen;
+    // a tile's inputs (plus one vector of slack on each side) must fit in the raw ring without lapping it
+    if (lds_samples > GC_COND_LDS_SAMPLES || (size_t)tile * job.decimation + job.n_taps + 16 >= job.raw_cap) return hipErrorInvalidValue;
+    const dim3 grid((job.n_out + (unsigned)tile - 1) / (unsigned)tile);
+    const size_t lds_bytes = lds_samples * sizeof(float2);
+    switch (iq_format)
+        {
+        case GC_IQ_F32: cond_launch_fmt<GC_IQ_F32>(grid, lds_bytes, st, job, tile, rowlen); break;
+        case GC_IQ_I16: cond_launch_fmt<GC_IQ_I16>(grid, lds_bytes, st, job, tile, rowlen); break;
+        case GC_IQ_I8: cond_launch_fmt<GC_IQ_I8>(grid, lds_bytes, st, job, tile, rowlen); break;
+        default: return hipErrorInvalidValue;
+        }
+    return hipGetLastError();
+}

@@ -41,7 +41,26 @@ struct gc_stream
     std::mutex mtx;
     std::mutex push_mtx;  // one push at a time (a push may release mtx while it waits for readers)
     std::atomic<int> refs{1};  // the creator's reference + one per batch channel that reads the ring
+    bool kernel_fed = false;   // a signal conditioner writes the ring (gc_conditioner.hip): gc_stream_push is refused
 };
+
+// Who writes the samples of a push.  gc_stream_produce does the ring's bookkeeping -- one push at a time, the wait for launches that
+// still read what the push evicts, the split at the wrap point, the mirror, the `pushed` event, the head -- and asks the writer to
+// enqueue, on the ring's copy stream, whatever puts each contiguous piece in place: a copy from host memory (gc_stream_push) or a
+// kernel (the signal conditioner).
+struct gc_ring_writer
+{
+    virtual ~gc_ring_writer() {}
+    // samples [idx, idx + *len) go to ring position pos (no wrap inside); the writer may shorten *len (> 0)
+    virtual gc_status write(gc_stream* s, uint64_t idx, uint64_t pos, uint64_t* len) = 0;
+    // the piece and its mirror part have been enqueued
+    virtual gc_status written(gc_stream*) { return GC_OK; }
+    // true: write() stores the part that falls in the first max_window samples behind the ring as well
+    virtual bool writes_mirror() const { return false; }
+};
+// Appends n_samples (<= capacity) through `w`; first_index (optional) receives the absolute number of the first of them.
+// `kernel_fed` says which kind of producer calls: the other kind is refused with GC_ERR_STATE.
+gc_status gc_stream_produce(gc_stream* s, uint64_t n_samples, uint64_t* first_index, gc_ring_writer& w, bool kernel_fed);
 
 void gc_stream_keep(gc_stream* s);
 void gc_stream_drop(gc_stream* s);

@@ -157,13 +157,13 @@ gc_status gc_stream_broadcast_pinned(gc_stream* const* rings, int n_rings, const
 
 }  // extern "C"
 
-static gc_status stream_push(gc_stream* s, const void* host_iq, uint64_t n_samples, uint64_t* first_index, bool pinned)
+gc_status gc_stream_produce(gc_stream* s, uint64_t n_samples, uint64_t* first_index, gc_ring_writer& w, bool kernel_fed)
 {
-    GC_REQUIRE(s && host_iq, "gc_stream_push: NULL argument");
-    GC_REQUIRE(n_samples <= s->capacity, "gc_stream_push: at most capacity = %llu samples per push", (unsigned long long)s->capacity);
     gc_device_guard g(s->ctx->device);
     std::lock_guard<std::mutex> one_push(s->push_mtx);
     std::unique_lock<std::mutex> lk(s->mtx);
+    if (s->kernel_fed != kernel_fed)
+        return gc_fail(GC_ERR_STATE, kernel_fed ? "the ring has no signal conditioner" : "gc_stream_push: a signal conditioner writes this ring (gc_conditioner_push)");
     if (first_index) *first_index = s->head;
     if (n_samples == 0) return GC_OK;
     const uint64_t new_head = s->head + n_samples;
@@ -175,40 +175,22 @@ static gc_status stream_push(gc_stream* s, const void* host_iq, uint64_t n_sampl
     // back-pressure that keeps the producer at most one ring ahead of the consumers.
     if (new_oldest > s->evicting_below) s->evicting_below = new_oldest;
     s->readers.wait_evictable(lk, new_oldest);
-    const char* src = static_cast<const char*>(host_iq);
     uint64_t idx = s->head, left = n_samples;
     while (left > 0)
         {
             const uint64_t pos = idx % s->capacity;
             uint64_t len = std::min<uint64_t>(left, s->capacity - pos);
-            int k = -1;
-            if (pinned)
-                {
-                    // page-locked caller memory: DMA straight from it (the caller keeps it until gc_stream_synchronize)
-                    GC_HIP(hipMemcpyAsync(s->d_ring + pos * s->elem, src, (size_t)len * s->elem, hipMemcpyHostToDevice, s->copy_stream));
-                }
-            else
-                {
-                    len = std::min<uint64_t>(len, s->slot_bytes / s->elem);
-                    k = s->next_slot;
-                    s->next_slot = (k + 1) % gc_stream::kSlots;
-                    if (s->slot_busy[k]) GC_HIP(hipEventSynchronize(s->slot_done[k]));
-                    std::memcpy(s->h_slot[k], src, (size_t)len * s->elem);
-                    GC_HIP(hipMemcpyAsync(s->d_ring + pos * s->elem, s->h_slot[k], (size_t)len * s->elem, hipMemcpyHostToDevice, s->copy_stream));
-                }
-            if (pos < s->mirror)
+            gc_status st = w.write(s, idx, pos, &len);
+            if (st != GC_OK) return st;
+            if (pos < s->mirror && !w.writes_mirror())
                 {
                     // the part that lands in the first max_window samples is repeated behind the ring (HBM to HBM)
                     const uint64_t mlen = std::min<uint64_t>(len, s->mirror - pos);
                     GC_HIP(hipMemcpyAsync(s->d_ring + (s->capacity + pos) * s->elem, s->d_ring + pos * s->elem, (size_t)mlen * s->elem,
                         hipMemcpyDeviceToDevice, s->copy_stream));
                 }
-            if (k >= 0)
-                {
-                    GC_HIP(hipEventRecord(s->slot_done[k], s->copy_stream));
-                    s->slot_busy[k] = true;
-                }
-            src += (size_t)len * s->elem;
+            st = w.written(s);
+            if (st != GC_OK) return st;
             idx += len;
             left -= len;
         }
@@ -216,6 +198,57 @@ static gc_status stream_push(gc_stream* s, const void* host_iq, uint64_t n_sampl
     s->has_pushed = true;
     s->head = new_head;
     return GC_OK;
+}
+
+namespace
+{
+// gc_stream_push / gc_stream_push_pinned: every piece is one H2D copy, from the caller's page-locked memory or through a staging slot
+struct host_copy_writer : gc_ring_writer
+{
+    const char* src;
+    bool pinned;
+    int k = -1;
+    host_copy_writer(const void* host_iq, bool pinned_) : src(static_cast<const char*>(host_iq)), pinned(pinned_) {}
+    gc_status write(gc_stream* s, uint64_t, uint64_t pos, uint64_t* plen) override
+    {
+        uint64_t len = *plen;
+        k = -1;
+        if (pinned)
+            {
+                // page-locked caller memory: DMA straight from it (the caller keeps it until gc_stream_synchronize)
+                GC_HIP(hipMemcpyAsync(s->d_ring + pos * s->elem, src, (size_t)len * s->elem, hipMemcpyHostToDevice, s->copy_stream));
+            }
+        else
+            {
+                len = std::min<uint64_t>(len, s->slot_bytes / s->elem);
+                k = s->next_slot;
+                s->next_slot = (k + 1) % gc_stream::kSlots;
+                if (s->slot_busy[k]) GC_HIP(hipEventSynchronize(s->slot_done[k]));
+                std::memcpy(s->h_slot[k], src, (size_t)len * s->elem);
+                GC_HIP(hipMemcpyAsync(s->d_ring + pos * s->elem, s->h_slot[k], (size_t)len * s->elem, hipMemcpyHostToDevice, s->copy_stream));
+            }
+        src += (size_t)len * s->elem;
+        *plen = len;
+        return GC_OK;
+    }
+    gc_status written(gc_stream* s) override
+    {
+        if (k >= 0)
+            {
+                GC_HIP(hipEventRecord(s->slot_done[k], s->copy_stream));
+                s->slot_busy[k] = true;
+            }
+        return GC_OK;
+    }
+};
+}  // namespace
+
+static gc_status stream_push(gc_stream* s, const void* host_iq, uint64_t n_samples, uint64_t* first_index, bool pinned)
+{
+    GC_REQUIRE(s && host_iq, "gc_stream_push: NULL argument");
+    GC_REQUIRE(n_samples <= s->capacity, "gc_stream_push: at most capacity = %llu samples per push", (unsigned long long)s->capacity);
+    host_copy_writer w(host_iq, pinned);
+    return gc_stream_produce(s, n_samples, first_index, w, false);
 }
 
 extern "C" {
@@ -227,6 +260,34 @@ gc_status gc_stream_info(gc_stream* s, uint64_t* oldest_index, uint64_t* head_in
     if (oldest_index) *oldest_index = gc_stream_oldest(s);
     if (head_index) *head_index = s->head;
     if (capacity_samples) *capacity_samples = s->capacity;
+    return GC_OK;
+}
+
+gc_status gc_stream_read(gc_stream* s, uint64_t first_index, uint64_t n_samples, void* host_out)
+{
+    GC_REQUIRE(s && (host_out || n_samples == 0), "gc_stream_read: NULL argument");
+    gc_device_guard g(s->ctx->device);
+    // no push starts while the window is copied (a push in progress has finished its bookkeeping: its samples count as resident)
+    std::lock_guard<std::mutex> no_push(s->push_mtx);
+    {
+        std::lock_guard<std::mutex> lk(s->mtx);
+        if (first_index < gc_stream_oldest(s) || first_index + n_samples > s->head || first_index + n_samples < first_index)
+            return gc_fail(GC_ERR_STATE, "gc_stream_read: samples [%llu, %llu) are not resident: the ring holds [%llu, %llu)",
+                (unsigned long long)first_index, (unsigned long long)(first_index + n_samples), (unsigned long long)gc_stream_oldest(s),
+                (unsigned long long)s->head);
+    }
+    GC_HIP(hipStreamSynchronize(s->copy_stream));
+    char* dst = static_cast<char*>(host_out);
+    uint64_t idx = first_index, left = n_samples;
+    while (left > 0)
+        {
+            const uint64_t pos = idx % s->capacity;
+            const uint64_t len = std::min<uint64_t>(left, s->capacity - pos);
+            GC_HIP(hipMemcpy(dst, s->d_ring + pos * s->elem, (size_t)len * s->elem, hipMemcpyDeviceToHost));
+            dst += (size_t)len * s->elem;
+            idx += len;
+            left -= len;
+        }
     return GC_OK;
 }
 

@@ -147,6 +147,17 @@ class LoopSyncConf(C.Structure):
 assert LOOP_RECORD_DTYPE.itemsize == 168 and C.sizeof(LoopConf) == 144 and C.sizeof(LoopSyncConf) == 360
 
 
+class ConditionerConf(C.Structure):
+    """gc_conditioner_conf: the frequency-translating FIR decimator in front of a ring."""
+    _fields_ = [
+        ("fs_in", C.c_double), ("translate_hz", C.c_double), ("decimation", C.c_uint32), ("n_taps", C.c_uint32),
+        ("in_format", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+assert C.sizeof(ConditionerConf) == 32
+
+
 # every symbol include/gnsscorr.h declares: name -> (restype, argtypes)
 _vp = C.c_void_p
 _fp = C.POINTER(C.c_float)
@@ -184,6 +195,14 @@ API = {
     "gc_stream_broadcast_pinned": (C.c_int, [C.POINTER(_vp), C.c_int, _vp, C.c_uint64]),
     "gc_stream_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gc_stream_synchronize": (C.c_int, [_vp]),
+    "gc_stream_read": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp]),
+    "gc_conditioner_conf_size": (C.c_size_t, []),
+    "gc_conditioner_create": (C.c_int, [_vp, C.POINTER(ConditionerConf), _fp, _vp, C.POINTER(_vp)]),
+    "gc_conditioner_destroy": (C.c_int, [_vp]),
+    "gc_conditioner_push": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "gc_conditioner_push_pinned": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "gc_conditioner_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "gc_fir_low_pass": (C.c_int, [C.c_double] * 4 + [_fp, C.c_int, C.POINTER(C.c_int)]),
     "gc_trk_loop_set_input_format": (C.c_int, [_vp, C.c_int]),
     "gc_trk_loop_set_input_stream": (C.c_int, [_vp, C.c_int, _vp]),
     "gc_trk_batch_set_input_stream": (C.c_int, [_vp, C.c_int, _vp]),
@@ -278,6 +297,9 @@ def load_library():
         st = lib.gc_abi_check(C.sizeof(EpochParams), C.sizeof(LoopConf), LOOP_RECORD_DTYPE.itemsize, C.sizeof(LoopSyncConf), C.sizeof(AcqConf), C.sizeof(AcqResult))
         if st != 0:
             raise GnsscorrError(st, lib.gc_last_error().decode() + " -- rebuild with __graft_entry__.build()")
+        if lib.gc_conditioner_conf_size() != C.sizeof(ConditionerConf):
+            raise GnsscorrError(GC_ERR_INVALID, "gc_conditioner_conf is %d bytes in the library, %d here -- rebuild with __graft_entry__.build()"
+                % (lib.gc_conditioner_conf_size(), C.sizeof(ConditionerConf)))
         _lib = lib
     return _lib
 
@@ -513,9 +535,72 @@ class IqStream:
     def synchronize(self):
         _check(load_library().gc_stream_synchronize(self._h))
 
+    def read(self, first_index, n):
+        """gc_stream_read: the resident window [first_index, first_index + n) in the ring's format -- complex64 [n] or
+        int16 / int8 [n, 2].  Synchronous; GC_ERR_STATE when the window is not resident."""
+        dt, per = self._DTYPES[self.iq_format]
+        out = np.zeros(int(n) if per == 1 else (int(n), per), dt)
+        _check(load_library().gc_stream_read(self._h, int(first_index), int(n), out.ctypes.data_as(_vp)))
+        return out
+
     def close(self):
         if self._h:
             load_library().gc_stream_destroy(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def fir_low_pass(gain, fs, cutoff_hz, transition_hz):
+    """gc_fir_low_pass: Hamming-windowed sinc of odd length (int)(53 fs / (22 transition_hz)) | 1 with sum(h) = gain; float32 taps."""
+    n = C.c_int(0)
+    _check(load_library().gc_fir_low_pass(gain, fs, cutoff_hz, transition_hz, None, 0, C.byref(n)))
+    taps = np.zeros(n.value, np.float32)
+    _check(load_library().gc_fir_low_pass(gain, fs, cutoff_hz, transition_hz, _f32p(taps), n.value, C.byref(n)))
+    return taps
+
+
+class Conditioner:
+    """gc_conditioner: raw samples of any gc_iq_format at fs_in are mixed down by translate_hz, filtered with `taps` and decimated
+    on the device into `out_ring` (an empty GC_IQ_F32 IqStream), which consumers then read at fs_in / decimation.  The filter's
+    group delay, (len(taps) - 1) / 2 input samples, is the caller's to account for."""
+
+    def __init__(self, ctx, out_ring, fs_in, translate_hz, decimation, taps, in_format=GC_IQ_F32):
+        self._ctx = ctx
+        self._ring = out_ring
+        self.in_format = in_format
+        self.taps = np.ascontiguousarray(taps, np.float32)
+        self.conf = ConditionerConf(float(fs_in), float(translate_hz), int(decimation), int(self.taps.size), int(in_format), 0)
+        self._h = _vp()
+        _check(load_library().gc_conditioner_create(ctx._h, C.byref(self.conf), _f32p(self.taps), out_ring._h, C.byref(self._h)))
+
+    def push(self, block):
+        """block: complex64 [n] (GC_IQ_F32) or int16 / int8 [n, 2].  Returns (number of the first new output, new outputs)."""
+        dt, per = IqStream._DTYPES[self.in_format]
+        block = np.ascontiguousarray(block, dt)
+        first, n_out = C.c_uint64(0), C.c_uint64(0)
+        _check(load_library().gc_conditioner_push(self._h, block.ctypes.data_as(_vp), block.size // per, C.byref(first), C.byref(n_out)))
+        return int(first.value), int(n_out.value)
+
+    def push_pinned(self, host_ptr, n_in):
+        """host_ptr: address of page-locked host memory; it stays untouched until the output ring is synchronised."""
+        first, n_out = C.c_uint64(0), C.c_uint64(0)
+        _check(load_library().gc_conditioner_push_pinned(self._h, _vp(host_ptr), int(n_in), C.byref(first), C.byref(n_out)))
+        return int(first.value), int(n_out.value)
+
+    def info(self):
+        """(raw samples pushed, output ring head)."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        _check(load_library().gc_conditioner_info(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def close(self):
+        if self._h:
+            load_library().gc_conditioner_destroy(self._h)
             self._h = _vp()
 
     def __del__(self):

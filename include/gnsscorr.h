@@ -185,6 +185,74 @@ gc_status gc_stream_broadcast_pinned(gc_stream* const* rings, int n_rings, const
 gc_status gc_stream_info(gc_stream* s, uint64_t* oldest_index, uint64_t* head_index, uint64_t* capacity_samples);
 /* Waits until every push so far has landed in HBM. */
 gc_status gc_stream_synchronize(gc_stream* s);
+/* Copies the resident window [first_index, first_index + n_samples) to host memory in the ring's format (tests, failure dumps).
+ * Synchronous: waits for the pushes so far.  GC_ERR_STATE when the window is not resident. */
+gc_status gc_stream_read(gc_stream* s, uint64_t first_index, uint64_t n_samples, void* host_out);
+
+/* ------------------------------------------------------------------------ */
+/* Signal conditioner: a frequency-translating FIR decimator in front of a      */
+/* ring.  The reference puts a signal conditioner (data-type adapter, input      */
+/* filter, resampler) between every source and its channels                      */
+/* (gnss_flowgraph.cc:496-499 connects the channels to its output); this is the   */
+/* input filter Freq_Xlating_Fir_Filter                                          */
+/* (src/algorithms/input_filter/adapters/freq_xlating_fir_filter.cc: keys IF,      */
+/* sampling_frequency, decimation_factor, taps) with the data-type adapter folded  */
+/* in.  Raw samples x[n] (n = absolute number, x[n] = 0 for n < 0) are pushed to   */
+/* the conditioner; a kernel writes                                              */
+/*                                                                            */
+/*   y[m] = sum_{k=0}^{T-1} h[k] * x[mD - k] * exp(-j 2 pi phi(mD - k))          */
+/*   phi(n) = ((n * inc) mod 2^64) >> 32, a fraction of a turn in units of 2^-32  */
+/*   inc    = round(translate_hz / fs_in * 2^64) mod 2^64   (IEEE double, ties to even) */
+/*                                                                            */
+/* into the output ring (GC_IQ_F32), which acquisition, tracking batches and     */
+/* closed-loop engines read like any other ring, addressing it by absolute sample */
+/* number AT THE OUTPUT RATE fs_in / D.  Mix-then-filter, the same mathematics as  */
+/* GNU Radio's rotated-taps form.  The phase is a closed form of the sample number: */
+/* it does not drift, needs no state and does not depend on the push sizes;         */
+/* translate_hz = 0 skips the mixer, and T = 1, h = {1}, D = 1 is then a bit-exact   */
+/* copy of the converted input.  Integer input is converted with a plain cast;       */
+/* products and sums are float32, in tap order.  Output m exists once input mD has   */
+/* been pushed: after N inputs the ring's head is ceil(N / D).  The filter delays the */
+/* signal by its group delay, (T - 1) / 2 INPUT samples for symmetric taps, which is  */
+/* the caller's to account for (e.g. in the code phase of a pseudorange), as in the   */
+/* reference.                                                                  */
+/* ------------------------------------------------------------------------ */
+typedef struct
+{
+    double fs_in;          /* rate of the raw samples [Hz] */
+    double translate_hz;   /* frequency moved to 0 (the reference's IF); |translate_hz| <= fs_in / 2 */
+    uint32_t decimation;   /* D, 1..64 */
+    uint32_t n_taps;       /* T, 1..1024 */
+    int32_t in_format;     /* gc_iq_format of the raw samples */
+    int32_t reserved;
+} gc_conditioner_conf; /* 32 bytes */
+/* sizeof(gc_conditioner_conf) as the library sees it (layout check of a binding; gc_abi_check covers the older structures) */
+size_t gc_conditioner_conf_size(void);
+
+typedef struct gc_conditioner gc_conditioner;
+/* taps: n_taps real float32 (copied).  out_ring: an empty GC_IQ_F32 ring of the same context; the conditioner keeps a reference on
+ * it (the ring handle may be destroyed first) and is its only producer from here on: gc_stream_push / gc_stream_push_pinned on the
+ * ring return GC_ERR_STATE.  The configuration and the taps are checked before anything touches a device. */
+gc_status gc_conditioner_create(gc_ctx* ctx, const gc_conditioner_conf* conf, const float* taps, gc_stream* out_ring,
+    gc_conditioner** out);
+gc_status gc_conditioner_destroy(gc_conditioner* c);
+/* Appends n_in raw samples (host memory, in_format) and enqueues the kernel for the outputs they complete.  first_out / n_out
+ * (optional): the absolute number of the first new output and their count (0 when the push completes none).  The last T - 1 raw
+ * samples stay in HBM for the next push: results do not depend on how the input is cut into pushes.  Asynchronous like
+ * gc_stream_push (the output ring's copy stream; gc_stream_synchronize waits for it); at most capacity outputs per call. */
+gc_status gc_conditioner_push(gc_conditioner* c, const void* host_raw, uint64_t n_in, uint64_t* first_out, uint64_t* n_out);
+/* Same for a PAGE-LOCKED host buffer: no staging copy; the buffer stays untouched until gc_stream_synchronize() on the output ring. */
+gc_status gc_conditioner_push_pinned(gc_conditioner* c, const void* pinned_host_raw, uint64_t n_in, uint64_t* first_out, uint64_t* n_out);
+/* Raw samples pushed so far and the output ring's head, ceil(in_head / D) (any pointer may be NULL). */
+gc_status gc_conditioner_info(gc_conditioner* c, uint64_t* in_head, uint64_t* out_head);
+/* Low-pass design for the conditioner (the reference's filter blocks take taps from the configuration or design them with
+ * gr::filter::firdes::low_pass; Remez designs stay with the caller, who passes taps): a Hamming-windowed sinc of odd length
+ *   T = (int)(53 fs / (22 transition_hz)), plus 1 when that is even              (53 dB: the Hamming window's attenuation)
+ *   h[i] = g(i - M) * (0.54 - 0.46 cos(2 pi i / (T - 1))),  M = (T - 1) / 2,  w0 = 2 pi cutoff_hz / fs
+ *   g(0) = w0 / pi,  g(k) = sin(k w0) / (k pi)
+ * scaled so that sum(h) = gain (the response at DC); computed in double, returned as float32.  *n_taps receives T; taps may be
+ * NULL to ask for T alone; GC_ERR_INVALID when T > capacity. */
+gc_status gc_fir_low_pass(double gain, double fs, double cutoff_hz, double transition_hz, float* taps, int capacity, int* n_taps);
 
 /* ------------------------------------------------------------------------ */
 /* Level 2 -- batched tracking engine: all channels of a GPU, many epochs,    */
