@@ -15,15 +15,27 @@
  *                              gr::filter::firdes::low_pass(1.0, sampling_frequency, bw, tw)); anything else: the caller passes
  *                              the taps (e.g. a Remez design from the band keys) to the constructor
  *   bw, tw               [Hz]  cut-off and transition width                   (defaults (sampling_frequency / D) / 2 and bw / 10)
+ *   pulse_blanking             true: the reference's Pulse_Blanking_Filter (src/algorithms/input_filter/adapters/
+ *                              pulse_blanking_filter.cc) on the raw samples   (default false), with that adapter's keys
+ *   pfa                        false-alarm probability of a segment           (default 0.04)
+ *   length                     samples per segment                            (default 32)
+ *   segments_est               segments of a noise-floor estimate             (default 12500)
+ *   segments_reset             segments after which the floor is re-estimated (default 5000000)
  * -- owns a GC_IQ_F32 ring at sampling_frequency / D plus the device conditioner (gc_conditioner) that writes it, and hands the ring to
  * the acquisition bank and the tracking group.  The output item type is always gr_complex.  general_work of the source-side block
  * calls push(items, n); everything downstream addresses the ring by sample number at the OUTPUT rate.  The filter delays the signal
  * by group_delay_samples() output samples; as in the reference, that is left in the observables.
+ *
+ * Order: blanking acts on the raw samples BEFORE the translating filter, so that a pulse is removed before the low-pass smears it over
+ * its neighbours.  The reference's Pulse_Blanking_Filter adapter with IF != 0 translates and filters first and blanks second; for
+ * IF = 0 the two are the same definition.  With blanking on, the ring's head advances by whole segments: head() is
+ * ceil(floor(items / length) * length / D).
  */
 #ifndef GNSSCORR_HIP_SIGNAL_CONDITIONER_H_
 #define GNSSCORR_HIP_SIGNAL_CONDITIONER_H_
 
 #include "gnss_sdr_types.h"
+#include "gnsscorr.h"
 #include <string>
 #include <vector>
 
@@ -73,8 +85,25 @@ public:
         c.n_taps = static_cast<uint32_t>(d_taps.size());
         c.in_format = format;
         c.reserved = 0;
+        d_blanking = configuration->property(role + ".pulse_blanking", false);
+        gc_blanking_conf b;
+        b.pfa = configuration->property(role + ".pfa", 0.04f);
+        b.threshold = 0.0f;  // from pfa and length
+        const int32_t length = configuration->property(role + ".length", static_cast<int32_t>(32));
+        const int32_t segments_est = configuration->property(role + ".segments_est", static_cast<int32_t>(12500));
+        const int32_t segments_reset = configuration->property(role + ".segments_reset", static_cast<int32_t>(5000000));
+        if (d_blanking && (length < 1 || segments_est < 1 || segments_reset < 0))
+            {
+                d_status = GC_ERR_INVALID;
+                return;
+            }
+        b.length = static_cast<uint32_t>(length);
+        b.segments_est = static_cast<uint32_t>(segments_est);
+        b.segments_reset = static_cast<uint32_t>(segments_reset);
+        b.reserved = 0;
         d_status = gc_stream_create(ctx, GC_IQ_F32, ring_capacity, max_window, &d_ring);
         if (d_status == GC_OK) d_status = gc_conditioner_create(ctx, &c, d_taps.data(), d_ring, &d_cond);
+        if (d_status == GC_OK && d_blanking) d_status = gc_conditioner_set_pulse_blanking(d_cond, &b);
     }
     ~hip_signal_conditioner()
     {
@@ -111,6 +140,21 @@ public:
         if (d_cond) gc_conditioner_info(d_cond, nullptr, &h);
         return h;
     }
+    bool pulse_blanking() const { return d_blanking; }
+    //! segments zeroed so far (0 without pulse_blanking); waits for the pushes so far
+    uint64_t blanked_segments() const
+    {
+        uint64_t n = 0;
+        if (d_cond && d_blanking) gc_conditioner_blanking_info(d_cond, nullptr, &n, nullptr, nullptr, nullptr);
+        return n;
+    }
+    //! the blanking stage's noise-floor estimate, power per real component in raw units (0 without pulse_blanking); waits likewise
+    float noise_power() const
+    {
+        float p = 0.0f;
+        if (d_cond && d_blanking) gc_conditioner_blanking_info(d_cond, nullptr, nullptr, &p, nullptr, nullptr);
+        return p;
+    }
     gc_status last_status() const { return d_status; }
 
 private:
@@ -118,6 +162,7 @@ private:
     std::vector<float> d_taps;
     double d_if = 0.0, d_fs_in = 0.0;
     int32_t d_decimation = 1;
+    bool d_blanking = false;
     gc_stream* d_ring = nullptr;
     gc_conditioner* d_cond = nullptr;
     gc_status d_status = GC_OK;

@@ -7,6 +7,12 @@
 // host and nothing is moved on the device, so the outputs do not depend on how the input is cut into pushes.  The H2D copy and the
 // kernel are enqueued on the OUTPUT ring's copy stream, in that order, inside the ring's own push bookkeeping (gc_stream_produce):
 // readers of the ring wait for the kernel exactly as they wait for the copy of a plain push.
+//
+// Pulse blanking (gc_conditioner_set_pulse_blanking) acts on the raw ring between the two: once a chunk's copy is enqueued, the
+// segments it completes get their energies, their decisions and -- the flagged ones -- zeros in place (cond_blank_kernels.hip), and
+// the FIR launch covers the outputs whose newest input those segments decide.  The undecided tail (< L samples) waits in the raw
+// ring for the next push, in front of the T - 1 samples of history.
+#include "cond_blank_kernels.h"
 #include "cond_kernels.h"
 #include "gc_stream.h"
 #include <algorithm>
@@ -27,6 +33,14 @@ struct gc_conditioner
     uint64_t chunk = 0;        // raw samples per H2D copy + launch
     float* d_taps = nullptr;
     uint64_t in_head = 0;      // raw samples pushed so far
+    // pulse blanking: off until gc_conditioner_set_pulse_blanking
+    bool blanking = false;
+    gc_blanking_conf blank_conf;
+    BlankParams blank_params;
+    BlankState* d_blank_state = nullptr;
+    float* d_blank_energy = nullptr;        // one chunk's segments
+    unsigned char* d_blank_flags = nullptr;
+    uint64_t blank_max_seg = 0;             // segments one chunk can complete
     // pinned staging for pageable caller buffers (as in gc_stream)
     static const int kSlots = 2;
     char* h_slot[kSlots] = {nullptr, nullptr};
@@ -86,6 +100,35 @@ gc_status cond_check_conf(const gc_conditioner_conf* conf, const float* taps)
     return GC_OK;
 }
 
+void cond_blank_free(gc_conditioner* c)
+{
+    (void)hipFree(c->d_blank_state);
+    (void)hipFree(c->d_blank_energy);
+    (void)hipFree(c->d_blank_flags);
+    c->d_blank_state = nullptr;
+    c->d_blank_energy = nullptr;
+    c->d_blank_flags = nullptr;
+    c->blanking = false;
+}
+
+// raw samples whose fate is known: all of them without blanking, whole segments with it
+uint64_t cond_decided(const gc_conditioner* c, uint64_t in_head)
+{
+    return c->blanking ? in_head / c->blank_conf.length * c->blank_conf.length : in_head;
+}
+
+gc_status cond_check_blanking(const gc_blanking_conf* b)
+{
+    GC_REQUIRE(b, "gc_conditioner_set_pulse_blanking: NULL configuration");
+    GC_REQUIRE(b->length >= 1 && b->length <= GC_COND_MAX_BLANK_LENGTH, "gc_conditioner_set_pulse_blanking: length %u is outside 1..%d", b->length,
+        GC_COND_MAX_BLANK_LENGTH);
+    GC_REQUIRE(b->pfa > 0.0f && b->pfa < 1.0f, "gc_conditioner_set_pulse_blanking: pfa %g is outside (0, 1)", (double)b->pfa);
+    GC_REQUIRE(b->segments_est >= 1, "gc_conditioner_set_pulse_blanking: segments_est must be at least 1");
+    GC_REQUIRE(b->threshold == 0.0f || (std::isfinite(b->threshold) && b->threshold > 0.0f),
+        "gc_conditioner_set_pulse_blanking: threshold %g is neither 0 (from pfa and length) nor finite and positive", (double)b->threshold);
+    return GC_OK;
+}
+
 void cond_release(gc_conditioner* c)
 {
     if (c->out)
@@ -98,6 +141,7 @@ void cond_release(gc_conditioner* c)
         }
     (void)hipFree(c->d_raw);
     (void)hipFree(c->d_taps);
+    cond_blank_free(c);
     for (int i = 0; i < gc_conditioner::kSlots; i++)
         {
             if (c->h_slot[i]) (void)hipHostFree(c->h_slot[i]);
@@ -112,8 +156,8 @@ gc_status cond_push(gc_conditioner* c, const void* host_raw, uint64_t n_in, uint
     gc_stream* s = c->out;
     const uint64_t D = c->conf.decimation;
     std::lock_guard<std::mutex> one_push(c->mtx);
-    const uint64_t out_before = (c->in_head + D - 1) / D;
-    const uint64_t out_after = (c->in_head + n_in + D - 1) / D;
+    const uint64_t out_before = (cond_decided(c, c->in_head) + D - 1) / D;
+    const uint64_t out_after = (cond_decided(c, c->in_head + n_in) + D - 1) / D;
     GC_REQUIRE(out_after - out_before <= s->capacity, "gc_conditioner_push: the push makes %llu outputs, the ring holds %llu",
         (unsigned long long)(out_after - out_before), (unsigned long long)s->capacity);
     if (first_out) *first_out = out_before;
@@ -145,8 +189,25 @@ gc_status cond_push(gc_conditioner* c, const void* host_raw, uint64_t n_in, uint
                     GC_HIP(hipEventRecord(c->slot_done[k], s->copy_stream));
                     c->slot_busy[k] = true;
                 }
-            const uint64_t m0 = (c->in_head + D - 1) / D, m1 = (c->in_head + n + D - 1) / D;
+            const uint64_t dec0 = cond_decided(c, c->in_head), dec1 = cond_decided(c, c->in_head + n);
+            const uint64_t m0 = (dec0 + D - 1) / D, m1 = (dec1 + D - 1) / D;
             c->in_head += n;
+            if (dec1 > dec0 && c->blanking)
+                {
+                    // the segments this chunk completes (the first may have begun in an earlier copy), before the FIR reads them
+                    BlankJob job;
+                    job.raw = c->d_raw;
+                    job.raw_cap = (unsigned)c->raw_cap;
+                    job.length = c->blank_conf.length;
+                    job.seg0 = dec0 / c->blank_conf.length;
+                    job.n_seg = (unsigned)((dec1 - dec0) / c->blank_conf.length);
+                    job.energies = c->d_blank_energy;
+                    job.flags = c->d_blank_flags;
+                    job.state = c->d_blank_state;
+                    job.params = c->blank_params;
+                    if (job.n_seg > c->blank_max_seg) return gc_fail(GC_ERR_STATE, "gc_conditioner_push: %u segments in one chunk", job.n_seg);
+                    GC_HIP(cond_blank_launch(c->conf.in_format, s->copy_stream, job));
+                }
             if (m1 > m0)
                 {
                     cond_writer w(c);
@@ -196,7 +257,8 @@ gc_status gc_conditioner_create(gc_ctx* ctx, const gc_conditioner_conf* conf, co
     c->chunk = slot_bytes / c->elem;
     // a chunk, the T - 1 samples before it, and room for the largest tile's vector slack; a multiple of 8 samples (16 bytes in
     // every format) so that aligned vectors do not straddle the end
-    c->raw_cap = (c->chunk + GC_COND_MAX_TAPS + (uint64_t)4 * GC_COND_THREADS * GC_COND_MAX_DECIMATION + 64 + 7) & ~(uint64_t)7;
+    // and the undecided tail of a blanked stream (< GC_COND_MAX_BLANK_LENGTH samples) in front of that history
+    c->raw_cap = (c->chunk + GC_COND_MAX_TAPS + GC_COND_MAX_BLANK_LENGTH + (uint64_t)4 * GC_COND_THREADS * GC_COND_MAX_DECIMATION + 64 + 7) & ~(uint64_t)7;
     hipError_t e = hipMalloc(&c->d_raw, (size_t)c->raw_cap * c->elem);
     if (e == hipSuccess) e = hipMemset(c->d_raw, 0, (size_t)c->raw_cap * c->elem);
     if (e == hipSuccess) e = hipMalloc(&c->d_taps, sizeof(float) * conf->n_taps);
@@ -241,7 +303,132 @@ gc_status gc_conditioner_info(gc_conditioner* c, uint64_t* in_head, uint64_t* ou
     std::lock_guard<std::mutex> lk(c->mtx);
     const uint64_t D = c->conf.decimation;
     if (in_head) *in_head = c->in_head;
-    if (out_head) *out_head = (c->in_head + D - 1) / D;
+    if (out_head) *out_head = (cond_decided(c, c->in_head) + D - 1) / D;
+    return GC_OK;
+}
+
+size_t gc_blanking_conf_size(void) { return sizeof(gc_blanking_conf); }
+
+gc_status gc_conditioner_set_pulse_blanking(gc_conditioner* c, const gc_blanking_conf* conf)
+{
+    // the configuration first, before anything that needs a device
+    gc_status st = cond_check_blanking(conf);
+    if (st != GC_OK) return st;
+    float threshold = conf->threshold;
+    if (threshold == 0.0f)
+        {
+            double q = 0.0;
+            st = gc_chi2_upper_quantile(2.0 * conf->length, (double)conf->pfa, &q);
+            if (st != GC_OK) return st;
+            threshold = (float)q;
+        }
+    GC_REQUIRE(c, "gc_conditioner_set_pulse_blanking: NULL handle");
+    std::lock_guard<std::mutex> one_push(c->mtx);
+    if (c->in_head != 0) return gc_fail(GC_ERR_STATE, "gc_conditioner_set_pulse_blanking: samples have been pushed already");
+    gc_device_guard g(c->ctx->device);
+    cond_blank_free(c);
+    c->blank_conf = *conf;
+    c->blank_conf.threshold = threshold;
+    c->blank_params.threshold = threshold;
+    c->blank_params.dof = (float)(2u * conf->length);
+    c->blank_params.segments_est = conf->segments_est;
+    c->blank_params.segments_reset = conf->segments_reset;
+    c->blank_max_seg = c->chunk / conf->length + 1;
+    hipError_t e = hipMalloc(&c->d_blank_state, sizeof(BlankState));
+    if (e == hipSuccess) e = hipMemset(c->d_blank_state, 0, sizeof(BlankState));
+    if (e == hipSuccess) e = hipMalloc(&c->d_blank_energy, sizeof(float) * c->blank_max_seg);
+    if (e == hipSuccess) e = hipMalloc(&c->d_blank_flags, c->blank_max_seg);
+    if (e != hipSuccess)
+        {
+            cond_blank_free(c);
+            return gc_fail(GC_ERR_HIP, "gc_conditioner_set_pulse_blanking: %s", hipGetErrorString(e));
+        }
+    c->blanking = true;
+    return GC_OK;
+}
+
+gc_status gc_conditioner_blanking_info(gc_conditioner* c, uint64_t* segments_decided, uint64_t* segments_blanked, float* noise_power, uint32_t* n_segments,
+    float* threshold)
+{
+    GC_REQUIRE(c, "gc_conditioner_blanking_info: NULL handle");
+    std::lock_guard<std::mutex> one_push(c->mtx);
+    if (!c->blanking) return gc_fail(GC_ERR_STATE, "gc_conditioner_blanking_info: pulse blanking is not configured");
+    gc_device_guard g(c->ctx->device);
+    BlankState st;
+    GC_HIP(hipStreamSynchronize(c->out->copy_stream));
+    GC_HIP(hipMemcpy(&st, c->d_blank_state, sizeof st, hipMemcpyDeviceToHost));
+    if (segments_decided) *segments_decided = st.decided;
+    if (segments_blanked) *segments_blanked = st.blanked;
+    if (noise_power) *noise_power = st.noise;
+    if (n_segments) *n_segments = st.n;
+    if (threshold) *threshold = c->blank_params.threshold;
+    return GC_OK;
+}
+
+namespace
+{
+// log of the gamma function's regularised incomplete pair: P by its series (x < a + 1), Q by Lentz's continued fraction otherwise
+double chi2_gamma_q(double a, double x)
+{
+    if (x <= 0.0) return 1.0;
+    const double lead = std::exp(a * std::log(x) - x - std::lgamma(a));
+    if (x < a + 1.0)
+        {
+            double term = 1.0 / a, sum = term;
+            for (int k = 1; k < 1000000; k++)
+                {
+                    term *= x / (a + k);
+                    sum += term;
+                    if (term < sum * 1e-17) break;
+                }
+            return 1.0 - lead * sum;
+        }
+    const double tiny = 1e-300;
+    double b = x + 1.0 - a, cc = 1.0 / tiny, d = 1.0 / b, h = d;
+    for (int k = 1; k < 1000000; k++)
+        {
+            const double an = -(double)k * ((double)k - a);
+            b += 2.0;
+            d = an * d + b;
+            if (std::fabs(d) < tiny) d = tiny;
+            cc = b + an / cc;
+            if (std::fabs(cc) < tiny) cc = tiny;
+            d = 1.0 / d;
+            const double del = d * cc;
+            h *= del;
+            if (std::fabs(del - 1.0) < 1e-16) break;
+        }
+    return lead * h;
+}
+}  // namespace
+
+gc_status gc_chi2_upper_quantile(double dof, double pfa, double* out)
+{
+    if (out) *out = 0.0;
+    GC_REQUIRE(out, "gc_chi2_upper_quantile: NULL result");
+    GC_REQUIRE(dof > 0.0 && std::isfinite(dof), "gc_chi2_upper_quantile: dof %g is not positive", dof);
+    GC_REQUIRE(pfa > 0.0 && pfa < 1.0, "gc_chi2_upper_quantile: pfa %g is outside (0, 1)", pfa);
+    // Q(a, x) = pfa for x = q / 2, a = dof / 2: Newton steps on Q (dQ/dx = -x^(a-1) e^-x / Gamma(a)) kept inside a bracket that
+    // every evaluation tightens, bisection whenever a step leaves it
+    const double a = 0.5 * dof;
+    double lo = 0.0, hi = a + 1.0;
+    while (chi2_gamma_q(a, hi) > pfa) hi *= 2.0;
+    double x = 0.5 * (lo + hi);
+    for (int it = 0; it < 300; it++)
+        {
+            const double f = chi2_gamma_q(a, x) - pfa;
+            if (f > 0.0)
+                lo = x;
+            else
+                hi = x;
+            const double pdf = std::exp((a - 1.0) * std::log(x) - x - std::lgamma(a));
+            double xn = x + f / pdf;
+            if (!(xn > lo && xn < hi)) xn = 0.5 * (lo + hi);
+            const bool done = std::fabs(xn - x) <= 2e-16 * x || hi - lo <= 2e-16 * hi;
+            x = xn;
+            if (done) break;
+        }
+    *out = 2.0 * x;
     return GC_OK;
 }
 

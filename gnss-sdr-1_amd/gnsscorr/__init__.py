@@ -158,6 +158,17 @@ class ConditionerConf(C.Structure):
 assert C.sizeof(ConditionerConf) == 32
 
 
+class BlankingConf(C.Structure):
+    """gc_blanking_conf: pulse blanking on the conditioner's raw samples (the reference's Pulse_Blanking_Filter)."""
+    _fields_ = [
+        ("pfa", C.c_float), ("threshold", C.c_float), ("length", C.c_uint32), ("segments_est", C.c_uint32),
+        ("segments_reset", C.c_uint32), ("reserved", C.c_uint32),
+    ]
+
+
+assert C.sizeof(BlankingConf) == 24
+
+
 # every symbol include/gnsscorr.h declares: name -> (restype, argtypes)
 _vp = C.c_void_p
 _fp = C.POINTER(C.c_float)
@@ -203,6 +214,10 @@ API = {
     "gc_conditioner_push_pinned": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gc_conditioner_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gc_fir_low_pass": (C.c_int, [C.c_double] * 4 + [_fp, C.c_int, C.POINTER(C.c_int)]),
+    "gc_blanking_conf_size": (C.c_size_t, []),
+    "gc_conditioner_set_pulse_blanking": (C.c_int, [_vp, C.POINTER(BlankingConf)]),
+    "gc_conditioner_blanking_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _fp, C.POINTER(C.c_uint32), _fp]),
+    "gc_chi2_upper_quantile": (C.c_int, [C.c_double, C.c_double, C.POINTER(C.c_double)]),
     "gc_trk_loop_set_input_format": (C.c_int, [_vp, C.c_int]),
     "gc_trk_loop_set_input_stream": (C.c_int, [_vp, C.c_int, _vp]),
     "gc_trk_batch_set_input_stream": (C.c_int, [_vp, C.c_int, _vp]),
@@ -300,6 +315,9 @@ def load_library():
         if lib.gc_conditioner_conf_size() != C.sizeof(ConditionerConf):
             raise GnsscorrError(GC_ERR_INVALID, "gc_conditioner_conf is %d bytes in the library, %d here -- rebuild with __graft_entry__.build()"
                 % (lib.gc_conditioner_conf_size(), C.sizeof(ConditionerConf)))
+        if lib.gc_blanking_conf_size() != C.sizeof(BlankingConf):
+            raise GnsscorrError(GC_ERR_INVALID, "gc_blanking_conf is %d bytes in the library, %d here -- rebuild with __graft_entry__.build()"
+                % (lib.gc_blanking_conf_size(), C.sizeof(BlankingConf)))
         _lib = lib
     return _lib
 
@@ -564,6 +582,13 @@ def fir_low_pass(gain, fs, cutoff_hz, transition_hz):
     return taps
 
 
+def chi2_upper_quantile(dof, pfa):
+    """gc_chi2_upper_quantile: x with P(chi-squared with `dof` degrees of freedom > x) = pfa (float64)."""
+    out = C.c_double(0.0)
+    _check(load_library().gc_chi2_upper_quantile(float(dof), float(pfa), C.byref(out)))
+    return float(out.value)
+
+
 class Conditioner:
     """gc_conditioner: raw samples of any gc_iq_format at fs_in are mixed down by translate_hz, filtered with `taps` and decimated
     on the device into `out_ring` (an empty GC_IQ_F32 IqStream), which consumers then read at fs_in / decimation.  The filter's
@@ -597,6 +622,22 @@ class Conditioner:
         a, b = C.c_uint64(0), C.c_uint64(0)
         _check(load_library().gc_conditioner_info(self._h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
+
+    def set_pulse_blanking(self, pfa=0.04, length=32, segments_est=12500, segments_reset=5000000, threshold=None):
+        """gc_conditioner_set_pulse_blanking (defaults: the reference adapter's): segments of `length` raw samples whose energy
+        exceeds `threshold` times the estimated noise floor are zeroed before the mixer and the filter.  threshold None: the
+        upper-pfa chi-squared quantile with 2 * length degrees of freedom.  Only before the first push."""
+        self.blanking = BlankingConf(float(pfa), 0.0 if threshold is None else float(threshold), int(length), int(segments_est),
+            int(segments_reset), 0)
+        _check(load_library().gc_conditioner_set_pulse_blanking(self._h, C.byref(self.blanking)))
+
+    def blanking_info(self):
+        """gc_conditioner_blanking_info (synchronous): dict(segments_decided, segments_blanked, noise_power, n_segments, threshold)."""
+        d, b, n = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
+        noise, thr = C.c_float(0.0), C.c_float(0.0)
+        _check(load_library().gc_conditioner_blanking_info(self._h, C.byref(d), C.byref(b), C.byref(noise), C.byref(n), C.byref(thr)))
+        return dict(segments_decided=int(d.value), segments_blanked=int(b.value), noise_power=float(noise.value), n_segments=int(n.value),
+            threshold=float(thr.value))
 
     def close(self):
         if self._h:

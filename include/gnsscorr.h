@@ -243,7 +243,8 @@ gc_status gc_conditioner_destroy(gc_conditioner* c);
 gc_status gc_conditioner_push(gc_conditioner* c, const void* host_raw, uint64_t n_in, uint64_t* first_out, uint64_t* n_out);
 /* Same for a PAGE-LOCKED host buffer: no staging copy; the buffer stays untouched until gc_stream_synchronize() on the output ring. */
 gc_status gc_conditioner_push_pinned(gc_conditioner* c, const void* pinned_host_raw, uint64_t n_in, uint64_t* first_out, uint64_t* n_out);
-/* Raw samples pushed so far and the output ring's head, ceil(in_head / D) (any pointer may be NULL). */
+/* Raw samples pushed so far and the output ring's head, ceil(in_head / D) -- with pulse blanking ceil(decided / D), see below
+ * (any pointer may be NULL). */
 gc_status gc_conditioner_info(gc_conditioner* c, uint64_t* in_head, uint64_t* out_head);
 /* Low-pass design for the conditioner (the reference's filter blocks take taps from the configuration or design them with
  * gr::filter::firdes::low_pass; Remez designs stay with the caller, who passes taps): a Hamming-windowed sinc of odd length
@@ -253,6 +254,54 @@ gc_status gc_conditioner_info(gc_conditioner* c, uint64_t* in_head, uint64_t* ou
  * scaled so that sum(h) = gain (the response at DC); computed in double, returned as float32.  *n_taps receives T; taps may be
  * NULL to ask for T alone; GC_ERR_INVALID when T > capacity. */
 gc_status gc_fir_low_pass(double gain, double fs, double cutoff_hz, double transition_hz, float* taps, int capacity, int* n_taps);
+
+/* Pulse blanking in the conditioner: the reference's interference mitigation Pulse_Blanking_Filter
+ * (src/algorithms/input_filter/gnuradio_blocks/pulse_blanking_cc.cc, adapter .../adapters/pulse_blanking_filter.cc) on the device.
+ * It acts on the RAW samples, by absolute sample number, BEFORE the mixer and the FIR: a pulse is removed before the low-pass smears
+ * it over its neighbours (mixing does not change a segment's energy).  The reference's adapter with IF != 0 filters first and blanks
+ * second; for IF = 0 the two orders are the same definition.
+ *
+ * Segment s is the raw samples [sL, (s + 1)L); E[s] is the sum of re^2 + im^2 over it (float32, plain cast of integer input).  The
+ * state machine is the reference's, statement for statement, in float32:
+ *
+ *   state: n = 0, last_filtered = false, noise = 0
+ *   for s = 0, 1, 2, ...:
+ *     if n < segments_est and not last_filtered:
+ *         noise = (float(n) * noise + E[s] / float(2L)) / float(n + 1);           pass
+ *     else if E[s] / noise > threshold:  blank segment s (all L samples read as zero);  last_filtered = true
+ *     else:  pass;  last_filtered = false;  if n > segments_reset: n = 0
+ *     n = n + 1
+ *
+ * Quirk kept from the reference: after a reset n becomes 1, not 0, so the re-estimate starts as the mean of the OLD floor and one
+ * new segment, and takes segments_est - 1 segments.  n is a uint32 and wraps where the reference's int32 overflows.
+ * threshold: the upper pfa quantile of a chi-squared distribution with 2L degrees of freedom, rounded to float32
+ * (gc_chi2_upper_quantile; the reference takes it from Boost), unless the caller supplies one.
+ *
+ * A segment is decided only once all L of its samples have been pushed (the reference never processes a partial segment either).
+ * With blanking on, decided = floor(in_head / L) * L; output m exists once raw sample mD is decided; the ring's head is
+ * ceil(decided / D), and gc_conditioner_info and the first_out / n_out of a push report exactly that.  Outputs, state and counters do
+ * not depend on how the input is cut into pushes.  A conditioner on which blanking was never configured behaves exactly as without
+ * this section: the same launches in the same order, the same bits. */
+typedef struct
+{
+    float pfa;               /* false-alarm probability of one segment, 0 < pfa < 1 */
+    float threshold;         /* 0: computed from pfa and length; otherwise finite and > 0, used as is */
+    uint32_t length;         /* L, samples per segment, 1..4096 */
+    uint32_t segments_est;   /* segments of a noise-floor estimate, >= 1 */
+    uint32_t segments_reset; /* a passing segment with n above this starts a new estimate */
+    uint32_t reserved;
+} gc_blanking_conf; /* 24 bytes */
+size_t gc_blanking_conf_size(void);
+/* Only before the first push (GC_ERR_STATE afterwards).  The limits are checked before anything touches a device
+ * (GC_ERR_INVALID). */
+gc_status gc_conditioner_set_pulse_blanking(gc_conditioner* c, const gc_blanking_conf* conf);
+/* Segments decided and blanked so far, the noise floor, n and the threshold in use (any pointer may be NULL).  Synchronous: waits
+ * for the pushes so far and copies the state back from the device.  GC_ERR_STATE when blanking is not configured. */
+gc_status gc_conditioner_blanking_info(gc_conditioner* c, uint64_t* segments_decided, uint64_t* segments_blanked, float* noise_power,
+    uint32_t* n_segments, float* threshold);
+/* x with P(chi-squared with dof degrees of freedom > x) = pfa, in double: the regularised upper incomplete gamma function (series /
+ * continued fraction) inverted by safeguarded Newton steps.  dof > 0, 0 < pfa < 1. */
+gc_status gc_chi2_upper_quantile(double dof, double pfa, double* out);
 
 /* ------------------------------------------------------------------------ */
 /* Level 2 -- batched tracking engine: all channels of a GPU, many epochs,    */
