@@ -9,14 +9,23 @@
  * shared by the satellites), and returns a Gnss_Synchro with the Acq_* fields of every satellite above the threshold, ready for
  * hip_tracking_group::start_tracking.  Sizes, thresholds and the result mapping are those of the reference adapters
  * (pcps_acquisition_adapters.h); GPS L1 C/A, L5I, Galileo E1 B / C, E5a, BeiDou B1I, B3I.
+ *
+ * use_acquisition_resampler (GNSS-SDR.use_acquisition_resampler, gnss_flowgraph.cc:375-499): the bank derives a decimated ring from
+ * `ring` on the device (hip_ring_decimator.h) at about the signal's optimal search rate -- GPS_L1_CA_OPT_ACQ_FS_HZ 1 000 000,
+ * GPS_L5_OPT_ACQ_FS_HZ 10 000 000, GALILEO_E1_OPT_ACQ_FS_HZ 2 000 000, GALILEO_E5A_OPT_ACQ_FS_HZ 10 000 000, none for BeiDou -- builds
+ * engine and replicas at that rate, and scales delay and sample stamp back to the ring's rate as pcps_acquisition.cc:756-762 does.
+ * Everything the caller sees stays at the ring's rate; tracking stays on `ring`.  When the plan's decimation is 1 the flag does
+ * nothing.  Deviation: the reference switches the resampler off for item types other than gr_complex; here every ring format works.
  */
 #ifndef GNSSCORR_HIP_ACQUISITION_BANK_H_
 #define GNSSCORR_HIP_ACQUISITION_BANK_H_
 
 #include "gnss_sdr_types.h"
+#include "hip_ring_decimator.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -26,21 +35,37 @@ public:
     /*! system / signal: 'G' "1C" | "L5", 'E' "1B" | "5X", 'C' "B1" | "B3"; prns: the satellites searched; fs_in: the ring's sampling rate;
      *  doppler_max / doppler_step [Hz]; threshold on the block's statistic (pcps_acquisition.cc:565-665); max_dwells non-coherent dwells */
     hip_acquisition_bank(gc_ctx* ctx, gc_stream* ring, char system, const std::string& signal, const std::vector<uint32_t>& prns, int64_t fs_in, uint32_t doppler_max,
-        uint32_t doppler_step, float threshold, uint32_t max_dwells = 1, bool use_cfar = true, int iq_format = GC_IQ_F32)
-        : d_ring(ring), d_system(system), d_signal(signal), d_prns(prns), d_threshold(threshold), d_max_dwells(std::max(1u, max_dwells))
+        uint32_t doppler_step, float threshold, uint32_t max_dwells = 1, bool use_cfar = true, int iq_format = GC_IQ_F32, bool use_acquisition_resampler = false)
+        : d_ring(ring), d_acq_ring(ring), d_system(system), d_signal(signal), d_prns(prns), d_threshold(threshold), d_max_dwells(std::max(1u, max_dwells))
     {
         double code_rate = 1.023e6, code_len = 1023.0;
-        uint32_t ms_per_code = 1;
-        if (system == 'G' && signal == "1C") {}
-        else if (system == 'G' && signal == "L5") { code_rate = 10.23e6; code_len = 10230.0; }
-        else if (system == 'E' && signal == "1B") { code_len = 4092.0; ms_per_code = 4; }
-        else if (system == 'E' && signal == "5X") { code_rate = 1.023e7; code_len = 10230.0; }
+        uint32_t ms_per_code = 1, opt_acq_fs = 0;
+        if (system == 'G' && signal == "1C") { opt_acq_fs = 1000000; }
+        else if (system == 'G' && signal == "L5") { code_rate = 10.23e6; code_len = 10230.0; opt_acq_fs = 10000000; }
+        else if (system == 'E' && signal == "1B") { code_len = 4092.0; ms_per_code = 4; opt_acq_fs = 2000000; }
+        else if (system == 'E' && signal == "5X") { code_rate = 1.023e7; code_len = 10230.0; opt_acq_fs = 10000000; }
         else if (system == 'C' && signal == "B1") { code_rate = 2.046e6; code_len = 2046.0; }
         else if (system == 'C' && signal == "B3") { code_rate = 10.23e6; code_len = 10230.0; }
         else
             {
                 d_status = GC_ERR_INVALID;
                 return;
+            }
+        if (use_acquisition_resampler)
+            {
+                // the search runs on a derived ring at resampled_fs, gr_complex whatever the source's item type
+                d_resampler.reset(new hip_ring_decimator(ctx, ring, fs_in, opt_acq_fs));
+                d_status = d_resampler->last_status();
+                if (d_status != GC_OK) return;
+                if (d_resampler->enabled())
+                    {
+                        d_ratio = d_resampler->decimation();
+                        d_latency = d_resampler->latency();
+                        fs_in = d_resampler->resampled_fs();
+                        iq_format = GC_IQ_F32;
+                    }
+                else
+                    d_resampler.reset();
             }
         gc_acq_conf c;
         std::memset(&c, 0, sizeof c);
@@ -69,6 +94,12 @@ public:
         uint32_t fft = 0, consumed = 0, bins = 0;
         gc_acq_fft_size(d_acq, &fft, &consumed, &bins);
         d_consumed = consumed;
+        if (d_resampler)
+            {
+                d_status = d_resampler->open(static_cast<uint64_t>(consumed) * (d_max_dwells + 1), consumed);
+                if (d_status != GC_OK) return;
+                d_acq_ring = d_resampler->ring();
+            }
         d_samples_per_code = static_cast<uint32_t>(std::floor(static_cast<double>(fs_in) / (code_rate / code_len)));
         // replicas: one code period at fs, tiled over the coherent time (the adapters' set_local_code)
         std::vector<float> one(2 * (d_samples_per_code + 16)), tiled(2 * static_cast<size_t>(consumed));
@@ -99,22 +130,43 @@ public:
     hip_acquisition_bank(const hip_acquisition_bank&) = delete;
     hip_acquisition_bank& operator=(const hip_acquisition_bank&) = delete;
 
-    //! samples one dwell consumes (pcps_acquisition: d_consumed_samples)
-    uint32_t consumed_samples() const { return d_consumed; }
+    //! samples of the ring one dwell consumes (pcps_acquisition: d_consumed_samples, times the resampler's decimation)
+    uint32_t consumed_samples() const { return d_consumed * d_ratio; }
+
+    /*! With use_acquisition_resampler: lets the derived ring catch up with the ring (asynchronous; GC_OK and nothing to do
+     *  without the resampler).  search() does this itself, but the decimator needs the ring samples from its last output on: call
+     *  update() after every push -- or at least once per ring capacity of pushed samples -- when searches are sporadic.  Once the
+     *  ring has run more than its capacity ahead of the derived ring, update() and every later search() return GC_ERR_STATE: the
+     *  derived ring cannot skip samples (derived sample m is ring sample m * ratio), and the bank has to be built anew. */
+    gc_status update()
+    {
+        if (d_resampler) d_status = d_resampler->update();
+        return d_resampler ? d_status : GC_OK;
+    }
 
     /*! One search of every satellite on ring samples [first_index, first_index + max_dwells * consumed_samples()): max_dwells
      *  non-coherent dwells, then the detections (statistic > threshold), strongest first.  Acq_samplestamp_samples is the stream
-     *  index of the LAST dwell's first sample, as the block stamps it (pcps_acquisition.cc:768). */
+     *  index of the LAST dwell's first sample, as the block stamps it (pcps_acquisition.cc:768).  With the resampler the search
+     *  starts at the next multiple of the decimation at or above first_index, so up to ratio - 1 further ring samples must have been
+     *  pushed, and Acq_samplestamp_samples counts from that multiple. */
     std::vector<Gnss_Synchro> search(uint64_t first_index)
     {
         std::vector<Gnss_Synchro> found;
-        if (d_acq == nullptr || !d_ready) return found;  // construction failed; a failed search is NOT sticky
+        // construction failed; a failed search is NOT sticky -- except a resampler that fell behind the ring, see update()
+        if (d_acq == nullptr || !d_ready) return found;
+        if (d_resampler)
+            {
+                // the derived ring catches up with the source; derived sample m is source sample m * ratio
+                d_status = d_resampler->update();
+                if (d_status != GC_OK) return found;
+                first_index = (first_index + d_ratio - 1) / d_ratio;
+            }
         d_status = gc_acq_reset(d_acq);
         uint64_t stamp = first_index;
         for (uint32_t dwell = 0; dwell < d_max_dwells && d_status == GC_OK; dwell++)
             {
                 stamp = first_index + static_cast<uint64_t>(dwell) * d_consumed;
-                d_status = gc_acq_dwell_stream(d_acq, d_ring, stamp, d_results.data());
+                d_status = gc_acq_dwell_stream(d_acq, d_acq_ring, stamp, d_results.data());
             }
         if (d_status != GC_OK) return found;
         std::vector<size_t> order;
@@ -128,9 +180,21 @@ public:
                 g.Signal[0] = d_signal[0];
                 g.Signal[1] = d_signal[1];
                 g.PRN = d_prns[s];
-                g.Acq_delay_samples = d_results[s].acq_delay_samples;
-                g.Acq_doppler_hz = d_results[s].acq_doppler_hz;
-                g.Acq_samplestamp_samples = stamp;
+                if (d_resampler)
+                    {
+                        // take into account the acquisition resampler ratio and the filter's latency (pcps_acquisition.cc:756-762);
+                        // the delay may come out negative, as in the reference
+                        g.Acq_delay_samples = static_cast<double>(d_results[s].acq_delay_samples) * static_cast<double>(d_ratio);
+                        g.Acq_delay_samples -= static_cast<double>(d_latency);
+                        g.Acq_doppler_hz = d_results[s].acq_doppler_hz;
+                        g.Acq_samplestamp_samples = static_cast<uint64_t>(std::rint(static_cast<double>(stamp) * static_cast<double>(d_ratio)));
+                    }
+                else
+                    {
+                        g.Acq_delay_samples = d_results[s].acq_delay_samples;
+                        g.Acq_doppler_hz = d_results[s].acq_doppler_hz;
+                        g.Acq_samplestamp_samples = stamp;
+                    }
                 g.Flag_valid_acquisition = true;
                 found.push_back(g);
             }
@@ -140,9 +204,15 @@ public:
     //! the statistic of every searched satellite in the last search (same order as `prns`)
     float statistic(size_t sat) const { return d_results[sat].test_statistics; }
     gc_status last_status() const { return d_status; }
+    //! acquisition resampler: decimation in use (1: none), its latency in ring samples, and the rate the search runs at
+    uint32_t resampler_ratio() const { return d_ratio; }
+    uint32_t resampler_latency_samples() const { return d_latency; }
 
 private:
     gc_stream* d_ring;
+    gc_stream* d_acq_ring;            // the ring the dwells read: d_ring, or the resampler's derived ring
+    std::unique_ptr<hip_ring_decimator> d_resampler;
+    uint32_t d_ratio = 1, d_latency = 0;
     gc_acq* d_acq = nullptr;
     bool d_ready = false;  // construction went through (every replica installed)
     char d_system;

@@ -11,6 +11,7 @@
 // spreads the D rows a wave's mixed samples are written to over the banks.  The taps are read with uniform (scalar) loads; every
 // output accumulates in float32 in tap order k = 0 .. T-1, so an output's bits do not depend on the tile it falls in.
 #include "cond_kernels.h"
+#include "cond_fir_accum.h"
 
 typedef float cond_f32x4 __attribute__((ext_vector_type(4)));
 typedef short cond_i16x8 __attribute__((ext_vector_type(8)));
@@ -115,34 +116,7 @@ __global__ __launch_bounds__(GC_COND_THREADS) void cond_fir_decim_kernel(const C
 #pragma unroll
     for (int r = 0; r < R; r++) j[r] = min(tid + r * GC_COND_THREADS, tn - 1);
     float2 acc[R];
-    int row = (T - 1) % D, q = (T - 1) / D;
-    {
-        const float h = job.taps[0];
-        const float2* p = cond_lds + row * rowlen + q;
-#pragma unroll
-        for (int r = 0; r < R; r++)
-            {
-                const float2 x = p[j[r]];
-                acc[r] = float2{h * x.x, h * x.y};
-            }
-    }
-    for (int k = 1; k < T; k++)
-        {
-            if (--row < 0)
-                {
-                    row = D - 1;
-                    q--;
-                }
-            const float h = job.taps[k];
-            const float2* p = cond_lds + row * rowlen + q;
-#pragma unroll
-            for (int r = 0; r < R; r++)
-                {
-                    const float2 x = p[j[r]];
-                    acc[r].x = fmaf(h, x.x, acc[r].x);
-                    acc[r].y = fmaf(h, x.y, acc[r].y);
-                }
-        }
+    cond_fir_accumulate<R>(cond_lds, rowlen, D, T, job.taps, j, acc);
 #pragma unroll
     for (int r = 0; r < R; r++)
         {
@@ -154,7 +128,7 @@ __global__ __launch_bounds__(GC_COND_THREADS) void cond_fir_decim_kernel(const C
         }
 }
 
-static int cond_rowlen(int decimation, int n_taps, int tile) { return (tile + (n_taps - 1) / decimation) | 1; }
+static int cond_rowlen(int decimation, int n_taps, int tile) { return cond_fir_rowlen(decimation, n_taps, tile); }
 
 int cond_tile_outputs(int decimation, int n_taps, unsigned n_out, int want_groups)
 {

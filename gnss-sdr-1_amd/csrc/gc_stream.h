@@ -41,7 +41,7 @@ struct gc_stream
     std::mutex mtx;
     std::mutex push_mtx;  // one push at a time (a push may release mtx while it waits for readers)
     std::atomic<int> refs{1};  // the creator's reference + one per batch channel that reads the ring
-    bool kernel_fed = false;   // a signal conditioner writes the ring (gc_conditioner.hip): gc_stream_push is refused
+    bool kernel_fed = false;   // a kernel writes the ring (gc_conditioner.hip, gc_ring_decimator.hip): gc_stream_push is refused
 };
 
 // Who writes the samples of a push.  gc_stream_produce does the ring's bookkeeping -- one push at a time, the wait for launches that

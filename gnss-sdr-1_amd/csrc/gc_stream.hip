@@ -163,7 +163,7 @@ gc_status gc_stream_produce(gc_stream* s, uint64_t n_samples, uint64_t* first_in
     std::lock_guard<std::mutex> one_push(s->push_mtx);
     std::unique_lock<std::mutex> lk(s->mtx);
     if (s->kernel_fed != kernel_fed)
-        return gc_fail(GC_ERR_STATE, kernel_fed ? "the ring has no signal conditioner" : "gc_stream_push: a signal conditioner writes this ring (gc_conditioner_push)");
+        return gc_fail(GC_ERR_STATE, kernel_fed ? "the ring has no producer on the device" : "gc_stream_push: a signal conditioner or a ring decimator writes this ring");
     if (first_index) *first_index = s->head;
     if (n_samples == 0) return GC_OK;
     const uint64_t new_head = s->head + n_samples;

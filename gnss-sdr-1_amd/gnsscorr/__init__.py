@@ -282,6 +282,12 @@ API = {
     "gc_acq_flush": (C.c_int, [_vp, _vp]),
     "gc_acq_get_grid": (C.c_int, [_vp, C.c_int, _fp]),
     "gc_acq_peek": (C.c_int, [_vp, C.c_int, C.c_int, _fp]),
+    "gc_ring_decimator_create": (C.c_int, [_vp, _vp, C.c_uint32, _fp, C.c_uint32, _vp, C.POINTER(_vp)]),
+    "gc_ring_decimator_destroy": (C.c_int, [_vp]),
+    "gc_ring_decimator_update": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "gc_ring_decimator_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "gc_acq_resampler_plan": (C.c_int, [C.c_int64, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int64), _fp, C.c_int, C.POINTER(C.c_int),
+        C.POINTER(C.c_uint32)]),
 }
 
 _lib = None
@@ -649,6 +655,56 @@ class Conditioner:
             self.close()
         except Exception:
             pass
+
+
+class RingDecimator:
+    """gc_ring_decimator: y[m] = sum_k taps[k] x[m decimation - k] from the ring `src` (any format; pushed, or fed by a Conditioner)
+    into `out_ring` (an empty GC_IQ_F32 IqStream), on the device.  update() appends what the source's samples so far complete."""
+
+    def __init__(self, ctx, src, decimation, taps, out_ring):
+        self._ctx = ctx
+        self._src = src
+        self._ring = out_ring
+        self.decimation = int(decimation)
+        self.taps = np.ascontiguousarray(taps, np.float32)
+        self._h = _vp()
+        _check(load_library().gc_ring_decimator_create(ctx._h, src._h, self.decimation, _f32p(self.taps), int(self.taps.size), out_ring._h,
+            C.byref(self._h)))
+
+    def update(self):
+        """Returns (number of the first new output, new outputs).  Asynchronous on the output ring's copy stream."""
+        first, n_out = C.c_uint64(0), C.c_uint64(0)
+        _check(load_library().gc_ring_decimator_update(self._h, C.byref(first), C.byref(n_out)))
+        return int(first.value), int(n_out.value)
+
+    def info(self):
+        """(source head the newest update saw, output ring head)."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        _check(load_library().gc_ring_decimator_info(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def close(self):
+        if self._h:
+            load_library().gc_ring_decimator_destroy(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def acq_resampler_plan(fs_in, opt_acq_fs_hz):
+    """gc_acq_resampler_plan: (decimation, resampled_fs, taps, latency_samples) of the acquisition resampler for a ring at fs_in and a
+    signal whose optimal search rate is opt_acq_fs_hz; decimation 1 with no taps when the reference would disable the resampler."""
+    lib = load_library()
+    d, rfs, n, lat = C.c_uint32(0), C.c_int64(0), C.c_int(0), C.c_uint32(0)
+    _check(lib.gc_acq_resampler_plan(int(fs_in), int(opt_acq_fs_hz), C.byref(d), C.byref(rfs), None, 0, C.byref(n), C.byref(lat)))
+    taps = np.zeros(n.value, np.float32)
+    if n.value:
+        _check(lib.gc_acq_resampler_plan(int(fs_in), int(opt_acq_fs_hz), C.byref(d), C.byref(rfs), _f32p(taps), n.value, C.byref(n), C.byref(lat)))
+    return int(d.value), int(rfs.value), taps, int(lat.value)
 
 
 class HipMulticorrelatorRealCodes:

@@ -693,6 +693,56 @@ gc_status gc_acq_get_grid(gc_acq* a, int sat, float* host_grid);
 enum { GC_ACQ_PEEK_WIPEOFF = 0, GC_ACQ_PEEK_SPECTRUM = 1, GC_ACQ_PEEK_CODE = 2, GC_ACQ_PEEK_ROW_MAX = 3 };
 gc_status gc_acq_peek(gc_acq* a, int what, int index, float* host_out);
 
+/* ------------------------------------------------------------------------ */
+/* Ring decimator: a decimated ring derived ON THE DEVICE from another ring -- */
+/* the acquisition resampler.  With GNSS-SDR.use_acquisition_resampler=true    */
+/* the reference puts one decimating low-pass FIR (fir_filter_ccf) per signal   */
+/* between the conditioner and the acquisition blocks                          */
+/* (src/core/receiver/gnss_flowgraph.cc:375-499): GPS L1 C/A is searched at     */
+/* about 1 Msps whatever the channels' rate, tracking stays on the full-rate    */
+/* stream, and the block scales delay and sample stamp back                    */
+/* (pcps_acquisition.cc:756-762).  Here the source is a gc_stream ring in any   */
+/* format -- pushed from the host or written by a gc_conditioner -- and         */
+/*                                                                            */
+/*   y[m] = sum_{k=0}^{T-1} h[k] * x[mD - k]      x[n] = 0 for n < 0            */
+/*                                                                            */
+/* (plain cast, float32 products and sums in tap order: the conditioner's        */
+/* definition with translate_hz = 0, and its bits) is appended to a GC_IQ_F32   */
+/* ring.  Output m is source sample mD, delayed by the filter's (T - 1) / 2      */
+/* source samples.  An output's bits are a function of the source samples alone: */
+/* never of the update, the tile or how the source was pushed.                  */
+/* ------------------------------------------------------------------------ */
+typedef struct gc_ring_decimator gc_ring_decimator;
+/* src_ring: a ring of the context in any format, empty or still holding sample 0 (GC_ERR_STATE otherwise).  out_ring: an empty
+ * GC_IQ_F32 ring of the same context; the decimator is its only producer from here on (gc_stream_push* on it return GC_ERR_STATE).
+ * decimation 1..64; taps: n_taps = 1..1024 real float32 (copied).  The decimator keeps a reference on both rings.  The arguments
+ * are checked before anything touches a device (GC_ERR_INVALID). */
+gc_status gc_ring_decimator_create(gc_ctx* ctx, gc_stream* src_ring, uint32_t decimation, const float* taps, uint32_t n_taps,
+    gc_stream* out_ring, gc_ring_decimator** out);
+gc_status gc_ring_decimator_destroy(gc_ring_decimator* d);
+/* Appends every output the source's samples so far complete: afterwards the output ring's head is ceil(src_head / D).  first_out /
+ * n_out (optional): the absolute number of the first new output and their count (0 when none is complete).  Asynchronous on the
+ * output ring's copy stream (gc_stream_synchronize waits for it); the launch waits for the newest source push, and no source push
+ * evicts what it reads.  GC_ERR_STATE, with nothing changed, when source sample max(0, m0 D - (T - 1)) (m0 = the output head) is no
+ * longer resident: the source ran more than its capacity ahead.  More outputs than the output ring holds are appended in order, in
+ * several pieces.  One update runs at a time; the call may come from another thread than the source's pushes. */
+gc_status gc_ring_decimator_update(gc_ring_decimator* d, uint64_t* first_out, uint64_t* n_out);
+/* The source head the newest successful update saw, and the output ring's head (any pointer may be NULL). */
+gc_status gc_ring_decimator_info(gc_ring_decimator* d, uint64_t* src_consumed, uint64_t* out_head);
+/* The reference's rule for the acquisition resampler of a signal whose optimal search rate is opt_acq_fs_hz
+ * (GPS_L1_CA_OPT_ACQ_FS_HZ = 1 000 000 ...), restated on the host:
+ *   decimation   = floor(fs_in / opt), stepped down while fs_in % decimation != 0
+ *   resampled_fs = fs_in / decimation
+ *   taps         = gc_fir_low_pass(1.0, fs_in, resampled_fs / 2.1, resampled_fs / 10)
+ *   latency      = (T - 1) / 2          source samples: set_resampler_latency
+ * plus ONE rule of this library: the stepping down goes on to the next divisor of fs_in while decimation > 64 or T > 1024 (the
+ * kernel's limits; T is about 24.1 x decimation, so in effect decimation <= 42).  opt >= fs_in, or a decimation that ends at 1, gives
+ * decimation = 1, resampled_fs = fs_in, n_taps = 0, latency = 0: the reference's "Disabled acquisition resampler because the input
+ * sampling frequency is too low".  taps may be NULL to ask for the sizes alone (any other pointer may be NULL too);
+ * GC_ERR_INVALID when T > capacity. */
+gc_status gc_acq_resampler_plan(int64_t fs_in, uint32_t opt_acq_fs_hz, uint32_t* decimation, int64_t* resampled_fs, float* taps,
+    int capacity, int* n_taps, uint32_t* latency_samples);
+
 #define GC_ABI_CHECK() \
     gc_abi_check(sizeof(gc_epoch_params), sizeof(gc_loop_conf), sizeof(gc_loop_record), sizeof(gc_loop_sync_conf), sizeof(gc_acq_conf), sizeof(gc_acq_result))
 
