@@ -10,7 +10,11 @@
  *   IF                   [Hz]  frequency moved to 0                           (default 0)
  *   sampling_frequency   [Hz]  rate of the raw samples                        (default 4000000)
  *   decimation_factor          D, 1..64                                       (default 1)
- *   input_item_type            "gr_complex" | "cshort" | "cbyte"              (default "gr_complex")
+ *   input_item_type            "gr_complex" | "cshort" | "cbyte": complex samples, 8 / 4 / 2 bytes each (default "gr_complex");
+ *                              "float" | "short" | "byte": REAL samples at an intermediate frequency, 4 / 2 / 1 bytes each, the
+ *                              reference adapter's other three item types (GC_RAW_REAL_F32 / _I16 / _I8);
+ *                              "2bit": real samples packed four to a byte, least-significant pair first, two's complement -- the
+ *                              input of the reference's unpack_byte_2bit_samples block, taken packed (GC_RAW_REAL_2BIT)
  *   filter_type                "lowpass": a windowed-sinc design from bw / tw (gc_fir_low_pass, the counterpart of
  *                              gr::filter::firdes::low_pass(1.0, sampling_frequency, bw, tw)); anything else: the caller passes
  *                              the taps (e.g. a Remez design from the band keys) to the constructor
@@ -23,7 +27,8 @@
  *   segments_reset             segments after which the floor is re-estimated (default 5000000)
  * -- owns a GC_IQ_F32 ring at sampling_frequency / D plus the device conditioner (gc_conditioner) that writes it, and hands the ring to
  * the acquisition bank and the tracking group.  The output item type is always gr_complex.  general_work of the source-side block
- * calls push(items, n); everything downstream addresses the ring by sample number at the OUTPUT rate.  The filter delays the signal
+ * calls push(items, n) with n counted in SAMPLES for every item type (a multiple of 4 for "2bit": samples_per_byte() is 4 there,
+ * which item_size() cannot express); pulse_blanking is not available with "2bit".  Everything downstream addresses the ring by sample number at the OUTPUT rate.  The filter delays the signal
  * by group_delay_samples() output samples; as in the reference, that is left in the observables.
  *
  * Order: blanking acts on the raw samples BEFORE the translating filter, so that a pulse is removed before the low-pass smears it over
@@ -57,6 +62,10 @@ public:
         if (d_item_type == "gr_complex") format = GC_IQ_F32;
         else if (d_item_type == "cshort") format = GC_IQ_I16;
         else if (d_item_type == "cbyte") format = GC_IQ_I8;
+        else if (d_item_type == "float") format = GC_RAW_REAL_F32;
+        else if (d_item_type == "short") format = GC_RAW_REAL_I16;
+        else if (d_item_type == "byte") format = GC_RAW_REAL_I8;
+        else if (d_item_type == "2bit") format = GC_RAW_REAL_2BIT;
         else
             {
                 d_status = GC_ERR_INVALID;
@@ -84,6 +93,7 @@ public:
         c.decimation = static_cast<uint32_t>(d_decimation);
         c.n_taps = static_cast<uint32_t>(d_taps.size());
         c.in_format = format;
+        d_format = format;
         c.reserved = 0;
         d_blanking = configuration->property(role + ".pulse_blanking", false);
         gc_blanking_conf b;
@@ -104,6 +114,12 @@ public:
         d_status = gc_stream_create(ctx, GC_IQ_F32, ring_capacity, max_window, &d_ring);
         if (d_status == GC_OK) d_status = gc_conditioner_create(ctx, &c, d_taps.data(), d_ring, &d_cond);
         if (d_status == GC_OK && d_blanking) d_status = gc_conditioner_set_pulse_blanking(d_cond, &b);
+        if (d_status != GC_OK && d_cond != nullptr)
+            {
+                // a half-configured conditioner takes no samples: push() keeps reporting the construction failure
+                gc_conditioner_destroy(d_cond);
+                d_cond = nullptr;
+            }
     }
     ~hip_signal_conditioner()
     {
@@ -122,11 +138,28 @@ public:
     const std::vector<float>& taps() const { return d_taps; }
     //! delay of a symmetric filter, in output samples
     double group_delay_samples() const { return d_taps.empty() ? 0.0 : (static_cast<double>(d_taps.size()) - 1.0) / 2.0 / d_decimation; }
-    size_t item_size() const { return d_item_type == "gr_complex" ? 8 : d_item_type == "cshort" ? 4 : 2; }
+    //! bytes of one raw item; for "2bit" an item is a byte of four samples: see samples_per_byte()
+    size_t item_size() const
+    {
+        switch (d_format)
+            {
+            case GC_IQ_F32: return 8;
+            case GC_IQ_I16:
+            case GC_RAW_REAL_F32: return 4;
+            case GC_IQ_I8:
+            case GC_RAW_REAL_I16: return 2;
+            default: return 1;
+            }
+    }
+    //! raw samples in one byte: 4 for "2bit", 0 for every type whose samples are whole bytes (item_size() of them)
+    int samples_per_byte() const { return d_format == GC_RAW_REAL_2BIT ? 4 : 0; }
+    //! true when the raw samples are real ("float", "short", "byte", "2bit")
+    bool real_input() const { return d_format >= GC_RAW_REAL_F32; }
     std::string role() const { return d_role; }
     std::string implementation() const { return "Freq_Xlating_Fir_Filter"; }
 
-    /*! n_items raw items of input_item_type; first_out / n_out (optional): the outputs they completed.  Asynchronous. */
+    /*! n_items raw SAMPLES of input_item_type (for "2bit" a multiple of 4, in n_items / 4 bytes); first_out / n_out (optional): the
+     *  outputs they completed.  Asynchronous. */
     gc_status push(const void* items, uint64_t n_items, uint64_t* first_out = nullptr, uint64_t* n_out = nullptr)
     {
         if (d_cond == nullptr) return d_status;  // construction failed
@@ -162,6 +195,7 @@ private:
     std::vector<float> d_taps;
     double d_if = 0.0, d_fs_in = 0.0;
     int32_t d_decimation = 1;
+    int d_format = GC_IQ_F32;
     bool d_blanking = false;
     gc_stream* d_ring = nullptr;
     gc_conditioner* d_cond = nullptr;

@@ -36,7 +36,7 @@ struct BlankState
 struct BlankParams
 {
     float threshold;
-    float dof;  // float(2L)
+    float dof;  // float(2L); float(L) for real raw samples
     unsigned segments_est;
     unsigned segments_reset;
 };

@@ -13,7 +13,7 @@
 struct BlankJob
 {
     void* raw;                // raw ring (HBM), as in CondJob; flagged segments are zeroed in place
-    unsigned raw_cap;         // multiple of 8 samples, > length + 16
+    unsigned raw_cap;         // multiple of 8 samples and > length + 16 (gc_iq_format), of 64 and > length + 128 (real formats)
     unsigned length;          // L, 1..GC_COND_MAX_BLANK_LENGTH
     unsigned long long seg0;  // absolute number of the first segment
     unsigned n_seg;
@@ -24,6 +24,7 @@ struct BlankJob
 };
 
 // Lanes that share one segment (a power of two, 1..64): a function of the format and L alone, like the whole summation order.
+// 0 for a format that is not blanked (GC_RAW_REAL_2BIT, unknown values).
 int cond_blank_lanes(int iq_format, unsigned length);
 // Enqueues the three stages for the job on `st`: energies, decisions (one wave), apply.  iq_format: format of the raw ring.
 hipError_t cond_blank_launch(int iq_format, hipStream_t st, const BlankJob& job);

@@ -2,13 +2,13 @@
 // Pulse_Blanking_Filter (src/algorithms/input_filter/gnuradio_blocks/pulse_blanking_cc.cc).  Three launches per chunk of raw samples,
 // on the output ring's copy stream, between the H2D copy and the FIR decimator:
 //
-//   1. energies   E[s] = sum over the segment of re^2 + im^2 (float32, plain cast).  G lanes share a segment (G: a power of two
-//                 fixed by the format and L).  The segment is covered by ALIGNED 16-byte vectors of the ring, counted from the one
-//                 that holds its first sample; lane g takes vectors g, g + G, ... and adds the samples of each that belong to the
-//                 segment in ascending order; the G partial sums meet in a fixed xor butterfly.  An aligned vector never
-//                 straddles the ring's wrap (raw_cap is a multiple of 8 samples), and the alignment of sample n is n % S
-//                 whatever the pushes were: the order of the sum is a function of the segment alone, so E[s] has the same bits
-//                 however the stream was cut into pushes and chunks.
+//   1. energies   E[s] = sum over the segment of re^2 + im^2 (x^2 for the real formats; float32, plain cast).  G lanes share a
+//                 segment (G: a power of two fixed by the format and L).  The segment is covered by ALIGNED 16-byte vectors of
+//                 the ring, counted from the one that holds its first sample; lane g takes vectors g, g + G, ... and adds the
+//                 samples of each that belong to the segment in ascending order; the G partial sums meet in a fixed xor
+//                 butterfly.  An aligned vector never straddles the ring's wrap (raw_cap is a multiple of 8 samples, of 64 for
+//                 the real formats), and the alignment of sample n is n % S whatever the pushes were: the order of the sum is a
+//                 function of the segment alone, so E[s] has the same bits however the stream was cut into pushes and chunks.
 //   2. decisions  one wave walks the new segments with the state (noise floor, n, last_filtered, counters) in HBM
 //                 (cond_blank_decide.h: 64 segments per step in steady mode, the dependent float32 mean by one walk otherwise).
 //   3. apply      zeroes the flagged segments in the ring, whole vectors inside, single samples at ragged edges; the FIR kernel
@@ -45,6 +45,29 @@ struct BlankRaw<GC_IQ_I8>
     typedef blank_i8x2 one;
     static constexpr int N = 8, ELEM = 2;
 };
+// real samples: one component each, E = sum of x^2 (the 2-bit packed format is not blanked: see include/gnsscorr.h)
+template <>
+struct BlankRaw<GC_RAW_REAL_F32>
+{
+    typedef blank_f32x4 vec;
+    typedef float one;
+    static constexpr int N = 4, ELEM = 4;
+};
+template <>
+struct BlankRaw<GC_RAW_REAL_I16>
+{
+    typedef blank_i16x8 vec;
+    typedef short one;
+    static constexpr int N = 8, ELEM = 2;
+};
+template <>
+struct BlankRaw<GC_RAW_REAL_I8>
+{
+    typedef blank_i8x16 vec;
+    typedef signed char one;
+    static constexpr int N = 16, ELEM = 1;
+};
+static constexpr bool blank_is_real(int fmt) { return fmt >= GC_RAW_REAL_F32; }
 
 // where a thread's segment lies: samples [a, b), aligned vectors 0 .. nvec - 1 from ring position pos0
 struct BlankSpan
@@ -79,7 +102,7 @@ __global__ __launch_bounds__(GC_BLANK_THREADS) void cond_blank_energy_kernel(con
             const BlankSpan sp = blank_span<S>(job, sl);
             for (unsigned v = g; v < sp.nvec; v += (unsigned)G)
                 {
-                    unsigned pos = sp.pos0 + v * S;  // L + 16 < raw_cap: at most one wrap
+                    unsigned pos = sp.pos0 + v * S;  // L + two vectors of slack < raw_cap (cond_blank_launch): at most one wrap
                     if (pos >= job.raw_cap) pos -= job.raw_cap;
                     const vec raw = *reinterpret_cast<const vec*>(static_cast<const char*>(job.raw) + (size_t)pos * BlankRaw<FMT>::ELEM);
                     const unsigned long long nv = sp.av + (unsigned long long)v * S;
@@ -88,8 +111,16 @@ __global__ __launch_bounds__(GC_BLANK_THREADS) void cond_blank_energy_kernel(con
                         {
                             const unsigned long long n = nv + e;
                             if (n < sp.a || n >= sp.b) continue;
-                            const float re = (float)raw[2 * e], im = (float)raw[2 * e + 1];
-                            acc += re * re + im * im;
+                            if constexpr (blank_is_real(FMT))
+                                {
+                                    const float x = (float)raw[e];
+                                    acc += x * x;
+                                }
+                            else
+                                {
+                                    const float re = (float)raw[2 * e], im = (float)raw[2 * e + 1];
+                                    acc += re * re + im * im;
+                                }
                         }
                 }
         }
@@ -163,15 +194,31 @@ __global__ __launch_bounds__(GC_BLANK_THREADS) void cond_blank_apply_kernel(cons
                     for (int e = 0; e < S; e++)
                         {
                             const unsigned long long n = nv + e;
-                            if (n >= sp.a && n < sp.b) reinterpret_cast<one*>(at)[e] = one{0, 0};
+                            if (n >= sp.a && n < sp.b) reinterpret_cast<one*>(at)[e] = one{};
                         }
                 }
         }
 }
 
+// samples in a 16-byte vector; 0: the format is not blanked
+static unsigned blank_vec_samples(int iq_format)
+{
+    switch (iq_format)
+        {
+        case GC_IQ_F32: return 2u;
+        case GC_IQ_I16:
+        case GC_RAW_REAL_F32: return 4u;
+        case GC_IQ_I8:
+        case GC_RAW_REAL_I16: return 8u;
+        case GC_RAW_REAL_I8: return 16u;
+        default: return 0u;
+        }
+}
+
 int cond_blank_lanes(int iq_format, unsigned length)
 {
-    const unsigned S = iq_format == GC_IQ_F32 ? 2u : iq_format == GC_IQ_I16 ? 4u : 8u;
+    const unsigned S = blank_vec_samples(iq_format);
+    if (S == 0) return 0;
     const unsigned vecs = (length + S - 1) / S;
     int G = 1;
     while (G < 64 && (unsigned)G < vecs) G *= 2;
@@ -191,13 +238,20 @@ static void cond_blank_launch_fmt(hipStream_t st, const BlankJob& job, int G)
 hipError_t cond_blank_launch(int iq_format, hipStream_t st, const BlankJob& job)
 {
     if (job.n_seg == 0) return hipSuccess;
-    if (job.length < 1 || job.length > GC_COND_MAX_BLANK_LENGTH || (job.raw_cap & 7u) != 0 || job.length + 16u >= job.raw_cap) return hipErrorInvalidValue;
+    // the raw ring's alignment and the slack of one vector on each side of a segment, per format as in cond_launch
+    const unsigned align = blank_is_real(iq_format) ? 64u : 8u;
+    if (blank_vec_samples(iq_format) == 0 || job.length < 1 || job.length > GC_COND_MAX_BLANK_LENGTH || job.raw_cap % align != 0 ||
+        job.length + 2u * align >= job.raw_cap)
+        return hipErrorInvalidValue;
     const int G = cond_blank_lanes(iq_format, job.length);
     switch (iq_format)
         {
         case GC_IQ_F32: cond_blank_launch_fmt<GC_IQ_F32>(st, job, G); break;
         case GC_IQ_I16: cond_blank_launch_fmt<GC_IQ_I16>(st, job, G); break;
         case GC_IQ_I8: cond_blank_launch_fmt<GC_IQ_I8>(st, job, G); break;
+        case GC_RAW_REAL_F32: cond_blank_launch_fmt<GC_RAW_REAL_F32>(st, job, G); break;
+        case GC_RAW_REAL_I16: cond_blank_launch_fmt<GC_RAW_REAL_I16>(st, job, G); break;
+        case GC_RAW_REAL_I8: cond_blank_launch_fmt<GC_RAW_REAL_I8>(st, job, G); break;
         default: return hipErrorInvalidValue;
         }
     return hipGetLastError();

@@ -1,5 +1,5 @@
-// gc_conditioner.hip -- gc_conditioner_*: the signal conditioner in front of an RF stream ring.  Raw samples (any gc_iq_format, any
-// intermediate frequency, any integer multiple of the channels' rate) are pushed here; a kernel (cond_kernels.hip) mixes them down,
+// gc_conditioner.hip -- gc_conditioner_*: the signal conditioner in front of an RF stream ring.  Raw samples (any gc_iq_format or
+// gc_raw_real_format, any intermediate frequency, any integer multiple of the channels' rate) are pushed here; a kernel (cond_kernels.hip) mixes them down,
 // low-pass filters and decimates them into the output ring, which acquisition and tracking read like any other gc_stream.
 //
 // Raw samples live in a small ring of their own in HBM (raw sample n at n % raw_cap): a push copies its block behind the previous
@@ -27,7 +27,7 @@ struct gc_conditioner
     gc_stream* out = nullptr;  // holds a reference
     gc_conditioner_conf conf;
     uint64_t phase_inc = 0;
-    size_t elem = 8;           // bytes per raw sample
+    unsigned bits = 64;        // bits per raw sample (2 for GC_RAW_REAL_2BIT: counts of samples become bytes through raw_bytes())
     char* d_raw = nullptr;     // raw ring: raw_cap samples
     uint64_t raw_cap = 0;
     uint64_t chunk = 0;        // raw samples per H2D copy + launch
@@ -52,6 +52,10 @@ struct gc_conditioner
 
 namespace
 {
+// bytes of n raw samples; n is a multiple of 4 wherever the format is GC_RAW_REAL_2BIT (pushes, ring positions and chunks all are)
+inline size_t raw_bytes(const gc_conditioner* c, uint64_t n) { return (size_t)(n * c->bits / 8u); }
+inline bool cond_real(int fmt) { return fmt == GC_RAW_REAL_F32 || fmt == GC_RAW_REAL_I16 || fmt == GC_RAW_REAL_I8 || fmt == GC_RAW_REAL_2BIT; }
+
 // writes the outputs of one chunk of raw samples: one launch per contiguous piece of the output ring
 struct cond_writer : gc_ring_writer
 {
@@ -94,8 +98,8 @@ gc_status cond_check_conf(const gc_conditioner_conf* conf, const float* taps)
     GC_REQUIRE(conf->fs_in > 0.0 && std::isfinite(conf->fs_in), "gc_conditioner_create: fs_in must be positive");
     GC_REQUIRE(std::isfinite(conf->translate_hz) && std::fabs(conf->translate_hz) <= 0.5 * conf->fs_in,
         "gc_conditioner_create: |translate_hz| = %g exceeds fs_in / 2 = %g", std::fabs(conf->translate_hz), 0.5 * conf->fs_in);
-    GC_REQUIRE(conf->in_format == GC_IQ_F32 || conf->in_format == GC_IQ_I16 || conf->in_format == GC_IQ_I8, "gc_conditioner_create: unknown input format %d",
-        conf->in_format);
+    GC_REQUIRE(conf->in_format == GC_IQ_F32 || conf->in_format == GC_IQ_I16 || conf->in_format == GC_IQ_I8 || cond_real(conf->in_format),
+        "gc_conditioner_create: unknown input format %d", conf->in_format);
     for (uint32_t k = 0; k < conf->n_taps; k++) GC_REQUIRE(std::isfinite(taps[k]), "gc_conditioner_create: tap %u is not finite", k);
     return GC_OK;
 }
@@ -155,6 +159,8 @@ gc_status cond_push(gc_conditioner* c, const void* host_raw, uint64_t n_in, uint
     GC_REQUIRE(c && (host_raw || n_in == 0), "gc_conditioner_push: NULL argument");
     gc_stream* s = c->out;
     const uint64_t D = c->conf.decimation;
+    GC_REQUIRE(c->conf.in_format != GC_RAW_REAL_2BIT || (n_in & 3u) == 0, "gc_conditioner_push: %llu samples of GC_RAW_REAL_2BIT are not whole bytes",
+        (unsigned long long)n_in);
     std::lock_guard<std::mutex> one_push(c->mtx);
     const uint64_t out_before = (cond_decided(c, c->in_head) + D - 1) / D;
     const uint64_t out_after = (cond_decided(c, c->in_head + n_in) + D - 1) / D;
@@ -175,15 +181,15 @@ gc_status cond_push(gc_conditioner* c, const void* host_raw, uint64_t n_in, uint
                     k = c->next_slot;
                     c->next_slot = (k + 1) % gc_conditioner::kSlots;
                     if (c->slot_busy[k]) GC_HIP(hipEventSynchronize(c->slot_done[k]));
-                    std::memcpy(c->h_slot[k], src, (size_t)n * c->elem);
+                    std::memcpy(c->h_slot[k], src, raw_bytes(c, n));
                     from = c->h_slot[k];
                 }
             // behind the previous block in the raw ring (two copies when the block crosses the ring's end); the samples it overwrites
             // are older than any output still to be made needs, and the copy stream orders it behind the kernels that read them
             const uint64_t pos = c->in_head % c->raw_cap;
             const uint64_t n1 = std::min(n, c->raw_cap - pos);
-            GC_HIP(hipMemcpyAsync(c->d_raw + pos * c->elem, from, (size_t)n1 * c->elem, hipMemcpyHostToDevice, s->copy_stream));
-            if (n1 < n) GC_HIP(hipMemcpyAsync(c->d_raw, from + (size_t)n1 * c->elem, (size_t)(n - n1) * c->elem, hipMemcpyHostToDevice, s->copy_stream));
+            GC_HIP(hipMemcpyAsync(c->d_raw + raw_bytes(c, pos), from, raw_bytes(c, n1), hipMemcpyHostToDevice, s->copy_stream));
+            if (n1 < n) GC_HIP(hipMemcpyAsync(c->d_raw, from + raw_bytes(c, n1), raw_bytes(c, n - n1), hipMemcpyHostToDevice, s->copy_stream));
             if (k >= 0)
                 {
                     GC_HIP(hipEventRecord(c->slot_done[k], s->copy_stream));
@@ -217,7 +223,7 @@ gc_status cond_push(gc_conditioner* c, const void* host_raw, uint64_t n_in, uint
                     if (first != m0) return gc_fail(GC_ERR_STATE, "gc_conditioner_push: the ring's head %llu is not the conditioner's output %llu",
                         (unsigned long long)first, (unsigned long long)m0);
                 }
-            src += (size_t)n * c->elem;
+            src += raw_bytes(c, n);
             left -= n;
         }
     return GC_OK;
@@ -252,15 +258,18 @@ gc_status gc_conditioner_create(gc_ctx* ctx, const gc_conditioner_conf* conf, co
     gc_stream_keep(out_ring);
     c->conf = *conf;
     c->phase_inc = cond_phase_inc(conf->translate_hz, conf->fs_in);
-    c->elem = conf->in_format == GC_IQ_F32 ? 8 : conf->in_format == GC_IQ_I16 ? 4 : 2;
+    c->bits = cond_raw_bits(conf->in_format);
     const size_t slot_bytes = (size_t)4 << 20;
-    c->chunk = slot_bytes / c->elem;
+    c->chunk = (uint64_t)slot_bytes * 8u / c->bits;
     // a chunk, the T - 1 samples before it, and room for the largest tile's vector slack; a multiple of 8 samples (16 bytes in
     // every format) so that aligned vectors do not straddle the end
     // and the undecided tail of a blanked stream (< GC_COND_MAX_BLANK_LENGTH samples) in front of that history
-    c->raw_cap = (c->chunk + GC_COND_MAX_TAPS + GC_COND_MAX_BLANK_LENGTH + (uint64_t)4 * GC_COND_THREADS * GC_COND_MAX_DECIMATION + 64 + 7) & ~(uint64_t)7;
-    hipError_t e = hipMalloc(&c->d_raw, (size_t)c->raw_cap * c->elem);
-    if (e == hipSuccess) e = hipMemset(c->d_raw, 0, (size_t)c->raw_cap * c->elem);
+    // the real formats: a multiple of 64 samples (16 bytes of the 2-bit format) and two such vectors of slack
+    const uint64_t align = cond_raw_align(conf->in_format);
+    c->raw_cap = (c->chunk + GC_COND_MAX_TAPS + GC_COND_MAX_BLANK_LENGTH + (uint64_t)4 * GC_COND_THREADS * GC_COND_MAX_DECIMATION + 8 * align + align - 1) &
+                 ~(align - 1);
+    hipError_t e = hipMalloc(&c->d_raw, raw_bytes(c, c->raw_cap));
+    if (e == hipSuccess) e = hipMemset(c->d_raw, 0, raw_bytes(c, c->raw_cap));
     if (e == hipSuccess) e = hipMalloc(&c->d_taps, sizeof(float) * conf->n_taps);
     if (e == hipSuccess) e = hipMemcpy(c->d_taps, taps, sizeof(float) * conf->n_taps, hipMemcpyHostToDevice);
     for (int i = 0; i < gc_conditioner::kSlots && e == hipSuccess; i++)
@@ -314,15 +323,18 @@ gc_status gc_conditioner_set_pulse_blanking(gc_conditioner* c, const gc_blanking
     // the configuration first, before anything that needs a device
     gc_status st = cond_check_blanking(conf);
     if (st != GC_OK) return st;
+    GC_REQUIRE(c, "gc_conditioner_set_pulse_blanking: NULL handle");
+    GC_REQUIRE(c->conf.in_format != GC_RAW_REAL_2BIT, "gc_conditioner_set_pulse_blanking: GC_RAW_REAL_2BIT samples cannot be blanked in place");
+    // degrees of freedom of a segment's energy: two components per complex sample, one per real sample
+    const uint32_t dof = cond_real(c->conf.in_format) ? conf->length : 2u * conf->length;
     float threshold = conf->threshold;
     if (threshold == 0.0f)
         {
             double q = 0.0;
-            st = gc_chi2_upper_quantile(2.0 * conf->length, (double)conf->pfa, &q);
+            st = gc_chi2_upper_quantile((double)dof, (double)conf->pfa, &q);
             if (st != GC_OK) return st;
             threshold = (float)q;
         }
-    GC_REQUIRE(c, "gc_conditioner_set_pulse_blanking: NULL handle");
     std::lock_guard<std::mutex> one_push(c->mtx);
     if (c->in_head != 0) return gc_fail(GC_ERR_STATE, "gc_conditioner_set_pulse_blanking: samples have been pushed already");
     gc_device_guard g(c->ctx->device);
@@ -330,7 +342,7 @@ gc_status gc_conditioner_set_pulse_blanking(gc_conditioner* c, const gc_blanking
     c->blank_conf = *conf;
     c->blank_conf.threshold = threshold;
     c->blank_params.threshold = threshold;
-    c->blank_params.dof = (float)(2u * conf->length);
+    c->blank_params.dof = (float)dof;
     c->blank_params.segments_est = conf->segments_est;
     c->blank_params.segments_reset = conf->segments_reset;
     c->blank_max_seg = c->chunk / conf->length + 1;

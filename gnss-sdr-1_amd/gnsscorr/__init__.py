@@ -20,6 +20,8 @@ LIB_PATH = os.environ.get("GNSSCORR_LIB", os.path.join(os.path.dirname(_HERE), "
 GC_OK, GC_ERR_INVALID, GC_ERR_NO_DEVICE, GC_ERR_HIP, GC_ERR_STATE = range(5)
 GC_MAX_TAPS = 8
 GC_IQ_F32, GC_IQ_I16, GC_IQ_I8 = range(3)
+# gc_raw_real_format: real raw samples, for Conditioner only (float32 / int16 / int8 one per sample; 2 bits, four samples per byte)
+GC_RAW_REAL_F32, GC_RAW_REAL_I16, GC_RAW_REAL_I8, GC_RAW_REAL_2BIT = range(16, 20)
 
 
 class GnsscorrError(RuntimeError):
@@ -588,6 +590,25 @@ def fir_low_pass(gain, fs, cutoff_hz, transition_hz):
     return taps
 
 
+def pack_2bit(values):
+    """GC_RAW_REAL_2BIT bytes (uint8 [n / 4]) from integers in {-2, -1, 0, 1} ([n], n a multiple of 4): sample 4b + i goes to bits
+    2i .. 2i + 1 of byte b, least-significant pair first, as a two's-complement 2-bit integer (-2 -> 0b10, -1 -> 0b11)."""
+    v = np.asarray(values)
+    if v.ndim != 1 or v.size % 4 != 0:
+        raise ValueError("pack_2bit: need a one-dimensional array whose length is a multiple of 4")
+    if v.size and (v.min() < -2 or v.max() > 1 or np.any(v != np.round(v))):
+        raise ValueError("pack_2bit: values must be integers in -2 .. 1")
+    q = (v.astype(np.int64) & 3).astype(np.uint8).reshape(-1, 4)
+    return (q[:, 0] | (q[:, 1] << 2) | (q[:, 2] << 4) | (q[:, 3] << 6)).astype(np.uint8)
+
+
+def unpack_2bit(packed):
+    """The samples of GC_RAW_REAL_2BIT bytes (uint8 or int8 [n / 4]) as int8 [n] in {-2, -1, 0, 1}: the inverse of pack_2bit."""
+    b = np.ascontiguousarray(packed).view(np.uint8).reshape(-1)
+    q = ((b[:, None] >> np.array([0, 2, 4, 6], np.uint8)) & 3).astype(np.int8)
+    return np.where(q >= 2, q - 4, q).astype(np.int8).reshape(-1)
+
+
 def chi2_upper_quantile(dof, pfa):
     """gc_chi2_upper_quantile: x with P(chi-squared with `dof` degrees of freedom > x) = pfa (float64)."""
     out = C.c_double(0.0)
@@ -596,9 +617,10 @@ def chi2_upper_quantile(dof, pfa):
 
 
 class Conditioner:
-    """gc_conditioner: raw samples of any gc_iq_format at fs_in are mixed down by translate_hz, filtered with `taps` and decimated
-    on the device into `out_ring` (an empty GC_IQ_F32 IqStream), which consumers then read at fs_in / decimation.  The filter's
-    group delay, (len(taps) - 1) / 2 input samples, is the caller's to account for."""
+    """gc_conditioner: raw samples of any gc_iq_format or gc_raw_real_format at fs_in are mixed down by translate_hz, filtered with
+    `taps` and decimated on the device into `out_ring` (an empty GC_IQ_F32 IqStream), which consumers then read at
+    fs_in / decimation.  The filter's group delay, (len(taps) - 1) / 2 input samples, is the caller's to account for."""
+    _REAL_DTYPES = {GC_RAW_REAL_F32: np.float32, GC_RAW_REAL_I16: np.int16, GC_RAW_REAL_I8: np.int8}
 
     def __init__(self, ctx, out_ring, fs_in, translate_hz, decimation, taps, in_format=GC_IQ_F32):
         self._ctx = ctx
@@ -609,12 +631,30 @@ class Conditioner:
         self._h = _vp()
         _check(load_library().gc_conditioner_create(ctx._h, C.byref(self.conf), _f32p(self.taps), out_ring._h, C.byref(self._h)))
 
-    def push(self, block):
-        """block: complex64 [n] (GC_IQ_F32) or int16 / int8 [n, 2].  Returns (number of the first new output, new outputs)."""
-        dt, per = IqStream._DTYPES[self.in_format]
-        block = np.ascontiguousarray(block, dt)
+    def push(self, block, n_samples=None):
+        """block: complex64 [n] (GC_IQ_F32) or int16 / int8 [n, 2]; float32 / int16 / int8 [n] for the real formats; uint8 or int8
+        [n / 4] for GC_RAW_REAL_2BIT (see pack_2bit).  n_samples: push only the first n_samples of the block.  Returns (number of
+        the first new output, new outputs)."""
+        if self.in_format == GC_RAW_REAL_2BIT:
+            block = np.ascontiguousarray(block)
+            if block.dtype not in (np.uint8, np.int8) or block.ndim != 1:
+                raise ValueError("GC_RAW_REAL_2BIT takes a uint8 or int8 array of shape [n / 4]")
+            n = 4 * block.size
+        elif self.in_format in self._REAL_DTYPES:
+            block = np.ascontiguousarray(block, self._REAL_DTYPES[self.in_format])
+            if block.ndim != 1:
+                raise ValueError("a real format takes an array of shape [n]")
+            n = block.size
+        else:
+            dt, per = IqStream._DTYPES[self.in_format]
+            block = np.ascontiguousarray(block, dt)
+            n = block.size // per
+        if n_samples is not None:
+            if not 0 <= int(n_samples) <= n:
+                raise ValueError("n_samples is outside the block")
+            n = int(n_samples)
         first, n_out = C.c_uint64(0), C.c_uint64(0)
-        _check(load_library().gc_conditioner_push(self._h, block.ctypes.data_as(_vp), block.size // per, C.byref(first), C.byref(n_out)))
+        _check(load_library().gc_conditioner_push(self._h, block.ctypes.data_as(_vp), n, C.byref(first), C.byref(n_out)))
         return int(first.value), int(n_out.value)
 
     def push_pinned(self, host_ptr, n_in):
@@ -632,7 +672,8 @@ class Conditioner:
     def set_pulse_blanking(self, pfa=0.04, length=32, segments_est=12500, segments_reset=5000000, threshold=None):
         """gc_conditioner_set_pulse_blanking (defaults: the reference adapter's): segments of `length` raw samples whose energy
         exceeds `threshold` times the estimated noise floor are zeroed before the mixer and the filter.  threshold None: the
-        upper-pfa chi-squared quantile with 2 * length degrees of freedom.  Only before the first push."""
+        upper-pfa chi-squared quantile with 2 * length degrees of freedom (length for the real formats; GC_RAW_REAL_2BIT is not
+        blanked: GC_ERR_INVALID).  Only before the first push."""
         self.blanking = BlankingConf(float(pfa), 0.0 if threshold is None else float(threshold), int(length), int(segments_est),
             int(segments_reset), 0)
         _check(load_library().gc_conditioner_set_pulse_blanking(self._h, C.byref(self.blanking)))

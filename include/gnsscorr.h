@@ -223,7 +223,7 @@ typedef struct
     double translate_hz;   /* frequency moved to 0 (the reference's IF); |translate_hz| <= fs_in / 2 */
     uint32_t decimation;   /* D, 1..64 */
     uint32_t n_taps;       /* T, 1..1024 */
-    int32_t in_format;     /* gc_iq_format of the raw samples */
+    int32_t in_format;     /* gc_iq_format or gc_raw_real_format of the raw samples */
     int32_t reserved;
 } gc_conditioner_conf; /* 32 bytes */
 /* sizeof(gc_conditioner_conf) as the library sees it (layout check of a binding; gc_abi_check covers the older structures) */
@@ -255,6 +255,32 @@ gc_status gc_conditioner_info(gc_conditioner* c, uint64_t* in_head, uint64_t* ou
  * NULL to ask for T alone; GC_ERR_INVALID when T > capacity. */
 gc_status gc_fir_low_pass(double gain, double fs, double cutoff_hz, double transition_hz, float* taps, int capacity, int* n_taps);
 
+/* Real raw samples: one real channel sampled at an intermediate frequency, the other half of what the reference's
+ * Freq_Xlating_Fir_Filter takes (freq_xlating_fir_filter.cc: input_item_type "float", "short", "byte" next to the complex types), and
+ * the output of its unpack_byte_2bit_samples block (signal_source/gnuradio_blocks) taken packed, four samples to a byte.  Values of
+ * gc_conditioner_conf.in_format for the conditioner ONLY: a gc_stream ring, the tracking engines and acquisition take the three
+ * gc_iq_format values and reject these like any unknown value.  3..15 are not used.
+ *
+ * For a real raw sample x[n] (n = absolute number, x[n] = 0 for n < 0) the mixer's output is
+ *
+ *   z[n] = ( x[n] * cos(2 pi phi(n)),  -( x[n] * sin(2 pi phi(n)) ) )     one float32 product each
+ *   z[n] = ( x[n], 0 )                                                     when inc = 0 (no mixer)
+ *   y[m] = sum_k h[k] z[mD - k]                                            the accumulation of the complex formats
+ *
+ * with the phi, inc, cosine / sine, plain cast of integer input and tap order of the complex formats: every output compares equal
+ * to what the matching complex format gives for the samples (x[n], 0) -- only the sign of a zero may differ -- while a sample takes
+ * 4, 2, 1 or 1/4 bytes on its way to the device instead of 8, 4 or 2.  n_in, in_head, first_out and n_out count SAMPLES in every
+ * format.  GC_RAW_REAL_2BIT: sample 4b + i is bits 2i .. 2i + 1 of byte b, least-significant pair first, read as a two's-complement
+ * 2-bit integer (-2, -1, 0 or 1: the reference's `signed two_bit_sample : 2`, DC bias included); a push whose n_in is not a multiple
+ * of 4 returns GC_ERR_INVALID before anything is enqueued (the reference's block works in whole bytes too); n_in = 0 stays legal. */
+typedef enum
+{
+    GC_RAW_REAL_F32 = 16, /* one float32 per sample: "float" */
+    GC_RAW_REAL_I16 = 17, /* one int16 per sample:   "short" */
+    GC_RAW_REAL_I8 = 18,  /* one int8 per sample:    "byte" */
+    GC_RAW_REAL_2BIT = 19 /* four samples per byte:  unpack_byte_2bit_samples */
+} gc_raw_real_format;
+
 /* Pulse blanking in the conditioner: the reference's interference mitigation Pulse_Blanking_Filter
  * (src/algorithms/input_filter/gnuradio_blocks/pulse_blanking_cc.cc, adapter .../adapters/pulse_blanking_filter.cc) on the device.
  * It acts on the RAW samples, by absolute sample number, BEFORE the mixer and the FIR: a pulse is removed before the low-pass smears
@@ -281,7 +307,13 @@ gc_status gc_fir_low_pass(double gain, double fs, double cutoff_hz, double trans
  * With blanking on, decided = floor(in_head / L) * L; output m exists once raw sample mD is decided; the ring's head is
  * ceil(decided / D), and gc_conditioner_info and the first_out / n_out of a push report exactly that.  Outputs, state and counters do
  * not depend on how the input is cut into pushes.  A conditioner on which blanking was never configured behaves exactly as without
- * this section: the same launches in the same order, the same bits. */
+ * this section: the same launches in the same order, the same bits.
+ *
+ * Real raw samples (GC_RAW_REAL_F32 / _I16 / _I8): the reference's blanking block takes gr_complex only, so this is the same
+ * definition applied to one real component per sample.  The state machine is the one above; E[s] is the sum of x^2 over the
+ * segment's L samples; the noise floor uses E[s] / float(L) in place of E[s] / float(2L); a threshold of 0 becomes the upper pfa
+ * quantile of a chi-squared distribution with L degrees of freedom.  GC_RAW_REAL_2BIT: gc_conditioner_set_pulse_blanking returns
+ * GC_ERR_INVALID -- zeroing a segment in place would need sub-byte read-modify-write across threads at its ragged edges. */
 typedef struct
 {
     float pfa;               /* false-alarm probability of one segment, 0 < pfa < 1 */
