@@ -4,19 +4,7 @@
 #include "gnsscorr.h"
 #include <hip/hip_runtime.h>
 #include "acq_phase_segments.h"
-
-#define ACQ_MAX_FACTORS 12
-#define ACQ_MAX_N1 64
-
-// N-point FFT as N = N1 x N2: N2-point row FFTs in LDS, N1-point column DFTs in registers
-struct AcqFftPlan
-{
-    int N, N1, N2;
-    int n_fac;
-    int fac[ACQ_MAX_FACTORS];  // radices of the N2-point row FFT, product = N2
-    int tw_off[ACQ_MAX_FACTORS];  // offset of each stage's twiddle table inside the stage-twiddle array
-    float2 w1[ACQ_MAX_N1];     // exp(-2*pi*j*k/N1), k < N1
-};
+#include "acq_plan.h"  // AcqFftPlan, acq_plan_make, acq_rows_lds_bytes, acq_cols_blocks
 
 // which array slice a cell reads: index = (cell / div) % mod
 struct AcqCellMap
@@ -48,8 +36,6 @@ struct AcqMagArgs
     int tmp_bin;          // bin whose single-dwell magnitudes are mirrored into tmp (accumulate only)
 };
 
-bool acq_plan_make(AcqFftPlan* plan, int N, size_t lds_limit_bytes);
-size_t acq_rows_lds_bytes(const AcqFftPlan& plan);
 // per-stage twiddles of the N2-point row FFT: stage f at out[tw_off[f] + (k-1)*m + q] = exp(-2*pi*j*q*k/n_f)
 // (N2 - 1 entries in total), followed by the plain table exp(-2*pi*j*i/N2), i < N2 (generic radices)
 void acq_stage_twiddles(const AcqFftPlan& plan, float2* out /* 2*N2 entries */);
@@ -66,8 +52,6 @@ hipError_t acq_launch_rows(hipStream_t st, bool inverse, const AcqFftPlan& plan,
 // columns pass + epilogue
 hipError_t acq_launch_cols(hipStream_t st, bool inverse, int epilogue, const AcqFftPlan& plan, int n_cells,
     const float2* Q, float2* out, const AcqMagArgs* mag);
-
-int acq_cols_blocks(const AcqFftPlan& plan);
 
 // The inverse row pass of one batch (arguments as acq_launch_rows, inverse) and the two-dwell column pass (epilogue ACQ_EPI_MAG2 /
 // _MAG2_ACC, n_cells_cols grid cells read from Qc) of the previous batch in ONE launch; only for plans acq_rows_cols_fusable() accepts

@@ -16,6 +16,7 @@
 // produce natural order, so every global access is a coalesced row.  The
 // element-wise product with conj(FFT(code)) is fused into the row load and
 // |.|^2 + non-coherent accumulation + row maximum into the column epilogue.
+#define ACQ_PLAN_DEFINE  // this unit holds the planner's definitions (acq_plan.h)
 #include "acq_kernels.h"
 #include "gc_internal.h"
 #include <cmath>
@@ -24,8 +25,6 @@
 #include <cstdio>
 #include <vector>
 #include <algorithm>
-
-#define ACQ_THREADS 256
 
 #ifndef ACQ_PK_CMUL
 #define ACQ_PK_CMUL 0  // 1: complex multiplies as two hand-written packed-FP32 instructions.  Measured: the compiler already emits the same
@@ -1302,7 +1301,7 @@ static __device__ __forceinline__ void acq_cols_body(const AcqFftPlan& plan, con
     // for the 82 spectra of a dwell pair.  The loads of the inter-pass buffer become strided, but it was written just before and sits in L2.
     constexpr bool PERM_EPI = (EPI == ACQ_EPI_PERM || EPI == ACQ_EPI_COMPLEX_CONJ_PERM);
     constexpr int PJ = ACQ_THREADS / N1;
-    const bool perm_map = PERM_EPI && N1 > 1 && PJ >= 4 && (N2 % (N1 * PJ)) == 0 && n_xblk * (N1 * PJ) == N2;
+    const bool perm_map = PERM_EPI && acq_cols_perm_map(N1, PJ, N2, n_xblk);
     int n2 = xblk * ACQ_THREADS + threadIdx.x;
     bool active = n2 < N2;
     if (perm_map)
@@ -2285,41 +2284,6 @@ __global__ __launch_bounds__(ACQ_FINAL_THREADS) void acq_final_kernel(AcqFinalAr
 // -----------------------------------------------------------------------------
 // host side: plan + launchers
 // -----------------------------------------------------------------------------
-static bool factor_rows(int N2, int* fac, int* n_fac)
-{
-    int n = N2, k = 0;
-    const int pref[] = {16, 10, 8, 5, 4, 3, 2};
-    while (n > 1)
-        {
-            int r = 0;
-            for (int p : pref)
-                if (n % p == 0)
-                    {
-                        r = p;
-                        break;
-                    }
-            if (!r)
-                {
-                    // any other prime factor: the generic O(R^2) butterfly (slow for large R, but every length the
-                    // LDS can hold is transformed -- the reference's FFTW takes any length)
-                    for (int p = 7; (long)p * p <= n; p += 2)
-                        if (n % p == 0)
-                            {
-                                r = p;
-                                break;
-                            }
-                    if (!r) r = n;  // n itself is prime
-                }
-            if (!r || k >= ACQ_MAX_FACTORS) return false;
-            fac[k++] = r;
-            n /= r;
-        }
-    *n_fac = k;
-    return true;
-}
-
-size_t acq_rows_lds_bytes(const AcqFftPlan& plan) { return (size_t)2 * plan.N2 * sizeof(float2); }
-
 void acq_stage_twiddles(const AcqFftPlan& plan, float2* out)
 {
     int n = plan.N2;
@@ -2340,53 +2304,6 @@ void acq_stage_twiddles(const AcqFftPlan& plan, float2* out)
             double ang = -2.0 * M_PI * (double)i / (double)plan.N2;
             out[plan.N2 + i] = make_float2((float)cos(ang), (float)sin(ang));
         }
-}
-
-bool acq_plan_make(AcqFftPlan* plan, int N, size_t lds_limit_bytes)
-{
-    std::memset(plan, 0, sizeof *plan);
-    if (N < 1) return false;
-    // N1 candidates (register DFT sizes that are instantiated); prefer rows of ~1000-2000 points:
-    // long enough to occupy a 256-thread workgroup, short enough for several workgroups per CU
-    const int cands[] = {1, 2, 3, 4, 5, 6, 8, 9, 10, 12, 15, 16, 20, 25, 32, 40, 50};  // 32-50: blocks of 256 k - 512 k samples
-    int best = 0;
-    long best_cost = -1;
-    for (int n1 : cands)
-        {
-            if (N % n1) continue;
-            int n2 = N / n1;
-            if ((size_t)2 * n2 * sizeof(float2) > lds_limit_bytes) continue;
-            int fac[ACQ_MAX_FACTORS], nf;
-            if (!factor_rows(n2, fac, &nf)) continue;
-            long cost = labs((long)n2 - 1024);
-            if (best_cost < 0 || cost < best_cost)
-                {
-                    best_cost = cost;
-                    best = n1;
-                }
-        }
-    if (!best) return false;
-    plan->N = N;
-    plan->N1 = best;
-    plan->N2 = N / best;
-    factor_rows(plan->N2, plan->fac, &plan->n_fac);
-    {
-        // offsets of the per-stage twiddle tables [k-1][q] (sizes sum to N2 - 1)
-        int n = plan->N2, off = 0;
-        for (int f = 0; f < plan->n_fac; f++)
-            {
-                const int R = plan->fac[f], m = n / R;
-                plan->tw_off[f] = off;
-                off += (R - 1) * m;
-                n = m;
-            }
-    }
-    for (int k = 0; k < best; k++)
-        {
-            double a = -2.0 * M_PI * (double)k / (double)best;
-            plan->w1[k] = make_float2((float)cos(a), (float)sin(a));
-        }
-    return true;
 }
 
 hipError_t acq_launch_permute(hipStream_t st, const float2* in, const float2* mul, float2* out,
@@ -2624,8 +2541,6 @@ hipError_t acq_launch_rows(hipStream_t st, bool inverse, const AcqFftPlan& plan,
         hipLaunchKernelGGL(acq_rows_kernel<false>, grid, dim3(nthr), lds, st, plan, A, mapA, B, mapB, Q, wN2, wN);
     return hipGetLastError();
 }
-
-int acq_cols_blocks(const AcqFftPlan& plan) { return (plan.N2 + ACQ_THREADS - 1) / ACQ_THREADS; }
 
 template <int N1>
 static hipError_t launch_cols_n1(hipStream_t st, bool inverse, int epilogue, const AcqFftPlan& plan, dim3 grid,
