@@ -789,22 +789,16 @@ gc_status gc_acq_dwell_stream(gc_acq* a, gc_stream* s, uint64_t first_index, gc_
     std::lock_guard<std::mutex> lk(a->ctx->mtx);
     hipStream_t st = a->ctx->stream;
     // the block is protected against eviction from here (reserved before the residency check and the launch)
-    gc_stream_ticket t;
-    gc_status rs = gc_stream_begin_read(s, st, first_index, &t);
+    gc_stream_read_set reads(st);
+    gc_status rs = reads.add(s, first_index);
     if (rs != GC_OK) return rs;
+    const gc_stream_ticket& t = reads.ticket(0);
     if (first_index + a->consumed > t.head)
-        {
-            gc_stream_cancel_read(s, t);
-            return gc_fail(GC_ERR_INVALID, "gc_acq_dwell_stream: block [%llu, +%u) is not inside the stream's resident samples [%llu, %llu)",
-                (unsigned long long)first_index, a->consumed, (unsigned long long)t.oldest, (unsigned long long)t.head);
-        }
+        return gc_fail(GC_ERR_INVALID, "gc_acq_dwell_stream: block [%llu, +%u) is not inside the stream's resident samples [%llu, %llu)",
+            (unsigned long long)first_index, a->consumed, (unsigned long long)t.oldest, (unsigned long long)t.head);
     rs = acq_enqueue(a, s->d_ring + (first_index % s->capacity) * s->elem, a->iq_format, st);
-    if (rs != GC_OK)
-        {
-            gc_stream_cancel_read(s, t);
-            return rs;
-        }
-    rs = gc_stream_end_read(s, st, t);
+    if (rs != GC_OK) return rs;
+    rs = reads.commit();
     if (rs != GC_OK) return rs;
     return acq_fetch(a, host_results, st);
 }

@@ -148,13 +148,14 @@ gc_status gc_ring_decimator_update(gc_ring_decimator* d, uint64_t* first_out, ui
     const uint64_t m0 = d->out_head;
     if (first_out) *first_out = m0;
     const uint64_t floor = m0 * D >= T - 1 ? m0 * D - (T - 1) : 0;
-    gc_stream_ticket t;
-    gc_status st = gc_stream_begin_read(d->src, d->out->copy_stream, floor, &t);
+    gc_stream_read_set reads(d->out->copy_stream);
+    gc_status st = reads.add(d->src, floor);
     if (st != GC_OK) return st;  // the floor is no longer resident: nothing reserved, nothing changed
+    const gc_stream_ticket& t = reads.ticket(0);
     const uint64_t m1 = (t.head + D - 1) / D;
     if (m1 <= m0)
         {
-            gc_stream_cancel_read(d->src, t);
+            // nothing to produce
             d->src_consumed = t.head;
             return GC_OK;
         }
@@ -172,14 +173,10 @@ gc_status gc_ring_decimator_update(gc_ring_decimator* d, uint64_t* first_out, ui
             if (st != GC_OK) break;
             m += n;
         }
-    if (m == m0)
-        {
-            gc_stream_cancel_read(d->src, t);
-            return st;
-        }
+    if (m == m0) return st;
     d->out_head = m;
     d->src_consumed = t.head;
-    const gc_status st_end = gc_stream_end_read(d->src, d->out->copy_stream, t);
+    const gc_status st_end = reads.commit();
     if (n_out) *n_out = m - m0;
     return st != GC_OK ? st : st_end;
 }

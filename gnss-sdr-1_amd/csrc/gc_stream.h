@@ -2,6 +2,7 @@
 #ifndef GC_STREAM_H
 #define GC_STREAM_H
 #include "gc_internal.h"
+#include "gc_read_set.h"
 #include "gc_reader_table.h"
 #include <vector>
 
@@ -88,5 +89,19 @@ gc_status gc_stream_begin_read(gc_stream* s, hipStream_t compute, uint64_t min_i
 gc_status gc_stream_end_read(gc_stream* s, hipStream_t compute, const gc_stream_ticket& t);
 // Nothing was enqueued after all (validation or launch failure).
 void gc_stream_cancel_read(gc_stream* s, const gc_stream_ticket& t);
+
+// The reads of one launch, cancelled on every way out that does not commit them (gc_read_set.h).
+struct gc_stream_read_ops
+{
+    typedef gc_stream ring_t;
+    typedef hipStream_t stream_t;
+    typedef gc_stream_ticket ticket_t;
+    static constexpr uint64_t FLOOR_OLDEST = GC_STREAM_FLOOR_OLDEST;
+    static gc_status begin(gc_stream* s, hipStream_t compute, uint64_t floor, gc_stream_ticket* t) { return gc_stream_begin_read(s, compute, floor, t); }
+    static gc_status end(gc_stream* s, hipStream_t compute, const gc_stream_ticket& t) { return gc_stream_end_read(s, compute, t); }
+    static void cancel(gc_stream* s, const gc_stream_ticket& t) { gc_stream_cancel_read(s, t); }
+    static gc_status too_many_rings(int bound) { return gc_fail(GC_ERR_INVALID, "one launch reads at most %d distinct stream rings", bound); }
+};
+typedef gc_read_set<gc_stream_read_ops> gc_stream_read_set;
 
 #endif

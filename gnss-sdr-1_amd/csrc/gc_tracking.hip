@@ -423,38 +423,22 @@ static gc_status batch_launch(gc_trk_batch* b, int n_epochs, const gc_epoch_para
                 }
         }
     const std::vector<gc_stream*> rings = batch_streams(b);
-    std::vector<gc_stream_ticket> tickets(rings.size());
-    auto cancel_all = [&]() {
-        for (size_t i = 0; i < rings.size(); i++) gc_stream_cancel_read(rings[i], tickets[i]);
-    };
+    gc_stream_read_set reads(st);
     for (size_t i = 0; i < rings.size(); i++)
         {
             // later pushes may evict everything below the floor while this launch is still running; the newest push must have landed
             const uint64_t floor = (floors && (*floors)[i] != ~0ull) ? (*floors)[i] : b->has_read_floor ? b->read_floor : GC_STREAM_FLOOR_OLDEST;
-            gc_status rs = gc_stream_begin_read(rings[i], st, floor, &tickets[i]);
-            if (rs == GC_OK && ends && (*ends)[i] > tickets[i].head)
-                rs = gc_fail(GC_ERR_INVALID, "gc_trk_batch_run: a window ends at sample %llu, the stream's resident samples are [%llu, %llu)",
-                    (unsigned long long)(*ends)[i], (unsigned long long)tickets[i].oldest, (unsigned long long)tickets[i].head);
-            if (rs != GC_OK)
-                {
-                    cancel_all();
-                    return rs;
-                }
+            const gc_status rs = reads.add(rings[i], floor);
+            if (rs != GC_OK) return rs;
+            const gc_stream_ticket& t = reads.ticket((int)i);
+            if (ends && (*ends)[i] > t.head)
+                return gc_fail(GC_ERR_INVALID, "gc_trk_batch_run: a window ends at sample %llu, the stream's resident samples are [%llu, %llu)",
+                    (unsigned long long)(*ends)[i], (unsigned long long)t.oldest, (unsigned long long)t.head);
         }
     hipError_t e = trk_launch(b->n_taps, b->mode, b->iq_format, st, b->d_chans, dev_params, static_cast<float2*>(dev_out), b->d_partial,
         b->n_channels, n_epochs, n_slices, lds_floats, true);
-    if (e != hipSuccess)
-        {
-            cancel_all();
-            return gc_fail(GC_ERR_HIP, "tracking kernel launch failed: %s", hipGetErrorString(e));
-        }
-    gc_status out = GC_OK;
-    for (size_t i = 0; i < rings.size(); i++)
-        {
-            gc_status rs = gc_stream_end_read(rings[i], st, tickets[i]);
-            if (rs != GC_OK) out = rs;
-        }
-    return out;
+    if (e != hipSuccess) return gc_fail(GC_ERR_HIP, "tracking kernel launch failed: %s", hipGetErrorString(e));
+    return reads.commit();
 }
 
 gc_status gc_trk_batch_run_dev(gc_trk_batch* b, int n_epochs, const gc_epoch_params* dev_params, void* dev_out, void* stream)

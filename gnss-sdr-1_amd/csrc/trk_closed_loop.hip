@@ -684,255 +684,169 @@ static hipError_t loop_launch_slices(gc_trk_loop* l, bool pilot, int n_epochs, g
     return loop_launch_slices_f<3, GC_IQ_F32>(l, pilot, hd, n_epochs, dev_records, st, n_slices, lds_table_floats, limits);
 }
 
+// slice buffers of the engine, grown on demand
+static hipError_t loop_slices_reserve(gc_trk_loop* l, int n_slices, hipStream_t st)
+{
+    if (l->d_prep && n_slices <= l->slice_cap) return hipSuccess;
+    hipError_t e = hipSuccess;
+    (void)hipFree(l->d_slice_partial);
+    l->d_slice_partial = nullptr;
+    if (!l->d_prep) e = hipMalloc(&l->d_prep, sizeof(LoopPrep) * l->n_channels);
+    if (e == hipSuccess && !l->d_tickets)
+        {
+            e = hipMalloc(&l->d_tickets, sizeof(unsigned) * l->n_channels);
+            if (e == hipSuccess) e = hipMemsetAsync(l->d_tickets, 0, sizeof(unsigned) * l->n_channels, st);
+        }
+    if (e == hipSuccess) e = hipMalloc(&l->d_slice_partial, sizeof(float2) * GC_MAX_TAPS * (size_t)l->n_channels * n_slices);
+    if (e == hipSuccess) l->slice_cap = n_slices;
+    return e;
+}
+
 #endif  // GNSSCORR_EXPERIMENTS
 
-extern "C" {
-
-static gc_status loop_launch(gc_trk_loop* l, int n_epochs, gc_loop_record* dev_records, hipStream_t st, bool positions_known)
+// The persistent kernel of a plain engine: one launch of n_channels workgroups.  Each runtime axis is switched in one function
+// below -- taps, sample format, data | pilot, threads | high-dynamics -- down to the instance's launch.
+struct LoopLaunch
 {
-    {
-        // channels that were never started (or were stopped) sit in standby: all-zero records, state 0
-        bool any = false;
-        for (int i = 0; i < l->n_channels; i++) any |= l->started[i] != 0;
-        if (!any) return gc_fail(GC_ERR_STATE, "gc_trk_loop_run: no channel has been started (gc_trk_loop_start)");
-    }
-    // ring inputs: this launch may use what has been pushed so far, and must not be overtaken by later pushes.  Reader slots
-    // are reserved (floor = the oldest sample a channel with a known position still needs, else the oldest resident one) before
-    // the residency check and the enqueue; the limits are the heads seen by those reservations.
-    std::vector<gc_stream*> rings;
-    std::vector<uint64_t> floors;
-    std::vector<char> floor_unknown;
-    std::vector<gc_stream_ticket> tickets;
-    bool any_ring = false;
-    // this launch's slot of the limits ring: free once the launch that used it last has finished
-    const int slot = l->limit_next;
-    if (l->limit_used[slot]) GC_HIP(hipEventSynchronize(l->limit_done[slot]));
-    unsigned long long* h_limits = l->h_limits[slot];
+    LoopChan* d_chans;
+    int n_channels, n_epochs;
+    gc_loop_record* dev_records;
+    hipStream_t st;
+    TrkLoopPlan plan;
+    const unsigned long long* limits;
+};
+template <int NT, int TH, int FM, bool DA, bool HD>
+static hipError_t loop_launch_k(const LoopLaunch& a)
+{
+    if (a.plan.lds_bytes > 48 * 1024)
+        {
+            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&trk_closed_loop_kernel<NT, TH, FM, DA, HD>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                (int)a.plan.lds_bytes);
+            if (ea != hipSuccess) return ea;
+        }
+    hipLaunchKernelGGL((trk_closed_loop_kernel<NT, TH, FM, DA, HD>), dim3(a.n_channels), dim3(TH), a.plan.lds_bytes, a.st, a.d_chans, a.dev_records, a.n_epochs,
+        a.plan.lds_table_floats, a.limits, a.plan.resident);
+    return hipGetLastError();
+}
+template <int NT, int FM, bool DA>
+static hipError_t loop_launch_t(const LoopLaunch& a, bool high_dyn)
+{
+    if (high_dyn) return loop_launch_k<NT, 256, FM, DA, true>(a);
+    if (a.plan.threads == 1024) return loop_launch_k<NT, 1024, FM, DA, false>(a);
+    if (a.plan.threads == 512) return loop_launch_k<NT, 512, FM, DA, false>(a);
+    return loop_launch_k<NT, 256, FM, DA, false>(a);
+}
+template <int NT, int FM>
+static hipError_t loop_launch_d(const LoopLaunch& a, bool pilot, bool high_dyn)
+{
+    return pilot ? loop_launch_t<NT, FM, true>(a, high_dyn) : loop_launch_t<NT, FM, false>(a, high_dyn);
+}
+template <int NT>
+static hipError_t loop_launch_f(const LoopLaunch& a, int iq_format, bool pilot, bool high_dyn)
+{
+    if (iq_format == GC_IQ_I16) return loop_launch_d<NT, GC_IQ_I16>(a, pilot, high_dyn);
+    if (iq_format == GC_IQ_I8) return loop_launch_d<NT, GC_IQ_I8>(a, pilot, high_dyn);
+    return loop_launch_d<NT, GC_IQ_F32>(a, pilot, high_dyn);
+}
+static hipError_t loop_launch_plain(const LoopLaunch& a, int n_taps, int iq_format, bool pilot, bool high_dyn)
+{
+    return n_taps == 5 ? loop_launch_f<5>(a, iq_format, pilot, high_dyn) : loop_launch_f<3>(a, iq_format, pilot, high_dyn);
+}
+
+// Ring inputs of a launch: the distinct rings its running channels read and the floor of each -- the oldest sample a channel with
+// a known position still needs; one channel with an unknown position pins it at the oldest resident sample.  Also presets the
+// limits: a buffer's length, 0 for a standby ring channel (never started, stopped, or lost lock: it reads nothing and holds
+// nothing back in the ring); those of running ring channels follow from the reservations.
+struct LoopRings
+{
+    gc_stream* ring[gc_stream_read_set::MAX_RINGS];
+    uint64_t floor[gc_stream_read_set::MAX_RINGS];
+    int n = 0;
+    bool any = false;  // a channel is bound to a ring, running or not
+};
+static gc_status loop_ring_floors(const gc_trk_loop* l, bool positions_known, unsigned long long* h_limits, LoopRings& rings)
+{
     for (int i = 0; i < l->n_channels; i++)
         {
             gc_stream* r = l->streams[i];
             h_limits[i] = l->n_iq[i];
             if (!r) continue;
-            any_ring = true;
-            // standby (never started, stopped, or lost lock): reads nothing, holds nothing back in the ring
-            if (!l->started[i] || l->idle[i]) continue;
-            const bool known = positions_known && l->pos_known[i];
-            size_t k = std::find(rings.begin(), rings.end(), r) - rings.begin();
-            if (k == rings.size())
-                {
-                    rings.push_back(r);
-                    floors.push_back(~0ull);
-                    floor_unknown.push_back(0);
-                }
-            // one channel with an unknown position pins the floor at the oldest resident sample
-            if (!known) floor_unknown[k] = 1;
-            floors[k] = std::min<uint64_t>(floors[k], known ? l->pos_host[i] : ~0ull);
-        }
-    auto cancel_all = [&]() {
-        for (size_t k = 0; k < tickets.size(); k++) gc_stream_cancel_read(rings[k], tickets[k]);
-    };
-    // Between the reservations below and their commit behind the launch NOTHING may return without releasing the reader slots: a slot
-    // left `pending` blocks every later push that would evict below its floor, and gc_stream_drop's drain, for ever.
-#define LOOP_HIP_OR_CANCEL(call)                                                                                              \
-    do                                                                                                                        \
-        {                                                                                                                     \
-            hipError_t e_ = (call);                                                                                           \
-            if (e_ != hipSuccess)                                                                                             \
-                {                                                                                                             \
-                    cancel_all();                                                                                             \
-                    return gc_fail(GC_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__);    \
-                }                                                                                                             \
-        }                                                                                                                     \
-    while (0)
-    tickets.resize(rings.size());
-    for (size_t k = 0; k < rings.size(); k++)
-        {
-            const bool pinned_oldest = floor_unknown[k] || floors[k] == ~0ull;
-            gc_status rs = gc_stream_begin_read(rings[k], st, pinned_oldest ? GC_STREAM_FLOOR_OLDEST : floors[k], &tickets[k]);
-            if (rs != GC_OK)
-                {
-                    cancel_all();
-                    if (!pinned_oldest)
-                        return gc_fail(GC_ERR_STATE, "gc_trk_loop_run: a channel (at sample %llu) fell behind the ring", (unsigned long long)floors[k]);
-                    return rs;
-                }
-        }
-    for (int i = 0; i < l->n_channels; i++)
-        {
-            gc_stream* r = l->streams[i];
-            if (!r) continue;
+            rings.any = true;
             if (!l->started[i] || l->idle[i])
                 {
                     h_limits[i] = 0;
                     continue;
                 }
-            const size_t k = std::find(rings.begin(), rings.end(), r) - rings.begin();
-            h_limits[i] = tickets[k].head;
-        }
-    if (any_ring)
-        {
-            hipError_t ce = hipMemcpyAsync(l->d_limits[slot], h_limits, sizeof(unsigned long long) * l->n_channels, hipMemcpyHostToDevice, st);
-            if (ce != hipSuccess)
+            const uint64_t floor = positions_known && l->pos_known[i] ? l->pos_host[i] : GC_STREAM_FLOOR_OLDEST;
+            const int k = (int)(std::find(rings.ring, rings.ring + rings.n, r) - rings.ring);
+            if (k == rings.n)
                 {
-                    cancel_all();
-                    return gc_fail(GC_ERR_HIP, "gc_trk_loop_run: %s", hipGetErrorString(ce));
+                    if (rings.n == gc_stream_read_set::MAX_RINGS) return gc_stream_read_ops::too_many_rings(rings.n);
+                    rings.ring[rings.n] = r;
+                    rings.floor[rings.n++] = floor;
                 }
+            else if (floor + 1 < rings.floor[k] + 1)  // GC_STREAM_FLOOR_OLDEST (~0) + 1 wraps to 0: below every floor
+                rings.floor[k] = floor;
         }
-    const unsigned long long* limits = any_ring ? l->d_limits[slot] : nullptr;
-    const bool pilot = l->pilot > 0;
-    // LDS code image: the doubled resident one (2 L + 64 floats per replica, loaded once per launch) when it fits beside the
-    // header, else the per-period window (L + 64)
-    // header, else the per-period window (L + 64).  With more channels than CUs several workgroups share a CU's 160 KB: the resident
-    // image is then taken only while two workgroups still fit (<= 64 KiB each; Galileo E1 with the pilot's data component is 131 KB:
-    // one workgroup per CU, which only costs nothing while every channel has a CU to itself)
-    const int n_cus = l->ctx->n_cus > 0 ? l->ctx->n_cus : 256;
-    int lds_table_floats = (2 * l->max_code_len + 64) * (pilot ? 2 : 1);
-    int window_floats = (l->max_code_len + 64) * (pilot ? 2 : 1);
-    if (l->mixed)
+    return GC_OK;
+}
+
+extern "C" {
+
+static gc_status loop_launch(gc_trk_loop* l, int n_epochs, gc_loop_record* dev_records, hipStream_t st, bool positions_known)
+{
+    // channels that were never started (or were stopped) sit in standby: all-zero records, state 0
+    if (std::find(l->started.begin(), l->started.end(), 1) == l->started.end())
+        return gc_fail(GC_ERR_STATE, "gc_trk_loop_run: no channel has been started (gc_trk_loop_start)");
+    // this launch's slot of the limits ring: free once the launch that used it last has finished
+    const int slot = l->limit_next;
+    if (l->limit_used[slot]) GC_HIP(hipEventSynchronize(l->limit_done[slot]));
+    unsigned long long* h_limits = l->h_limits[slot];
+    // ring inputs: this launch may use what has been pushed so far, and must not be overtaken by later pushes.  One reservation per
+    // ring, taken before the residency check and the enqueue; the limits are the heads seen by those reservations.
+    LoopRings rings;
+    const gc_status fs = loop_ring_floors(l, positions_known, h_limits, rings);
+    if (fs != GC_OK) return fs;
+    gc_stream_read_set reads(st);
+    for (int k = 0; k < rings.n; k++)
         {
-            // a mixed engine: the largest need among its started channels (longest code, pilot or not), by the same rule
-            lds_table_floats = window_floats = 0;
+            const gc_status rs = reads.add(rings.ring[k], rings.floor[k]);
+            if (rs != GC_OK && rings.floor[k] != GC_STREAM_FLOOR_OLDEST)
+                return gc_fail(GC_ERR_STATE, "gc_trk_loop_run: a channel (at sample %llu) fell behind the ring", (unsigned long long)rings.floor[k]);
+            if (rs != GC_OK) return rs;
+        }
+    if (rings.any)
+        {
             for (int i = 0; i < l->n_channels; i++)
-                if (l->started[i])
-                    {
-                        lds_table_floats = std::max(lds_table_floats, (2 * l->code_len[i] + 64) * (l->track_pilot[i] ? 2 : 1));
-                        window_floats = std::max(window_floats, (l->code_len[i] + 64) * (l->track_pilot[i] ? 2 : 1));
-                    }
+                if (l->streams[i] && l->started[i] && !l->idle[i]) h_limits[i] = reads.ticket(l->streams[i]).head;
+            hipError_t ce = hipMemcpyAsync(l->d_limits[slot], h_limits, sizeof(unsigned long long) * l->n_channels, hipMemcpyHostToDevice, st);
+            if (ce != hipSuccess) return gc_fail(GC_ERR_HIP, "gc_trk_loop_run: %s", hipGetErrorString(ce));
         }
-    int resident = 1;
-    const size_t resident_bytes = (size_t)(trk_hdr_floats(1024) + lds_table_floats) * sizeof(float);
-    if (resident_bytes > 150 * 1024 || (l->n_channels > n_cus && resident_bytes > 64 * 1024))
-        {
-            lds_table_floats = window_floats;
-            resident = 0;
-        }
-    // few channels: more threads each, so that a channel's epoch is spread over a whole CU (measured, 256 channels x 64
-    // epochs on 256 CUs: 0.89 / 0.65 / 0.69 ms with 256 / 512 / 1024 threads)
-    const int threads = l->forced_threads ? l->forced_threads : (2 * l->n_channels <= n_cus ? 1024 : l->n_channels <= 2 * n_cus ? 512 : 256);
-    const size_t lds_bytes = (size_t)(trk_hdr_floats(threads) + lds_table_floats) * sizeof(float);
+    const unsigned long long* limits = rings.any ? l->d_limits[slot] : nullptr;
+    const bool pilot = l->pilot > 0;
+    const TrkLoopPlan plan = trk_loop_plan(l->n_channels, l->ctx->n_cus, l->high_dyn != 0, l->forced_threads, l->mixed != 0, l->started.data(),
+        l->code_len.data(), l->track_pilot.data(), l->max_code_len, pilot);
+    const LoopLaunch a = {l->d_chans, l->n_channels, n_epochs, dev_records, st, plan, limits};
     // workgroups per channel-period: 1 = the persistent one-workgroup-per-channel kernel (always, in the product library); an
     // experiments build cuts the period into slices on request (gc_trk_loop_set_geometry), one launch per period: measured slower
-    int n_slices = 1;
+    hipError_t le;
 #ifdef GNSSCORR_EXPERIMENTS
-    n_slices = l->mixed ? 1 : std::max(1, l->forced_slices);
-    if (n_slices > 1)
+    if (!l->mixed && l->forced_slices > 1)
         {
-            if (!l->d_prep || n_slices > l->slice_cap)
-                {
-                    (void)hipFree(l->d_slice_partial);
-                    l->d_slice_partial = nullptr;
-                    if (!l->d_prep) LOOP_HIP_OR_CANCEL(hipMalloc(&l->d_prep, sizeof(LoopPrep) * l->n_channels));
-                    if (!l->d_tickets)
-                        {
-                            LOOP_HIP_OR_CANCEL(hipMalloc(&l->d_tickets, sizeof(unsigned) * l->n_channels));
-                            LOOP_HIP_OR_CANCEL(hipMemsetAsync(l->d_tickets, 0, sizeof(unsigned) * l->n_channels, st));
-                        }
-                    LOOP_HIP_OR_CANCEL(hipMalloc(&l->d_slice_partial, sizeof(float2) * GC_MAX_TAPS * (size_t)l->n_channels * n_slices));
-                    l->slice_cap = n_slices;
-                }
-            const hipError_t se = loop_launch_slices(l, pilot, n_epochs, dev_records, st, n_slices, (l->max_code_len + 64) * (pilot ? 2 : 1), limits);
-            if (se != hipSuccess)
-                {
-                    cancel_all();
-                    return gc_fail(GC_ERR_HIP, "gc_trk_loop_run: kernel launch failed: %s", hipGetErrorString(se));
-                }
-        }
-#endif
-    if (n_slices <= 1)
-    {
-#define LAUNCH_LOOP_D(NT, TH, FM, DA)                                                                                                             \
-    do                                                                                                                                        \
-        {                                                                                                                                     \
-            if (lds_bytes > 48 * 1024)                                                                                                        \
-                LOOP_HIP_OR_CANCEL(hipFuncSetAttribute(reinterpret_cast<const void*>(&trk_closed_loop_kernel<NT, TH, FM, DA>),                            \
-                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                                                             \
-            hipLaunchKernelGGL((trk_closed_loop_kernel<NT, TH, FM, DA>), dim3(l->n_channels), dim3(TH), lds_bytes, st, l->d_chans, dev_records, \
-                n_epochs, lds_table_floats, limits, resident);                                                                                          \
-        }                                                                                                                                     \
-    while (0)
-#define LAUNCH_LOOP(NT, TH, FM)                      \
-    do                                               \
-        {                                            \
-            if (pilot) LAUNCH_LOOP_D(NT, TH, FM, true); \
-            else LAUNCH_LOOP_D(NT, TH, FM, false);   \
-        }                                            \
-    while (0)
-#define LAUNCH_LOOP_FMT(NT, TH)                                           \
-    do                                                                    \
-        {                                                                 \
-            if (l->iq_format == GC_IQ_I16) LAUNCH_LOOP(NT, TH, GC_IQ_I16); \
-            else if (l->iq_format == GC_IQ_I8) LAUNCH_LOOP(NT, TH, GC_IQ_I8); \
-            else LAUNCH_LOOP(NT, TH, GC_IQ_F32);                          \
-        }                                                                 \
-    while (0)
-    if (l->mixed)
-        LOOP_HIP_OR_CANCEL(loop_launch_mixed(l->d_chans, l->n_channels, l->iq_format, l->high_dyn, threads, n_epochs, dev_records, st, lds_table_floats, limits, resident));
-    else if (l->high_dyn)
-        {
-            // high-dynamics kernels: 256 threads per channel (the per-sample exact rotator keeps a workgroup busy)
-#define LAUNCH_LOOP_HD_D(NT, FM, DA)                                                                                                              \
-    do                                                                                                                                        \
-        {                                                                                                                                     \
-            if (lds_bytes_hd > 48 * 1024)                                                                                                     \
-                LOOP_HIP_OR_CANCEL(hipFuncSetAttribute(reinterpret_cast<const void*>(&trk_closed_loop_kernel<NT, 256, FM, DA, true>),                     \
-                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes_hd));                                                          \
-            hipLaunchKernelGGL((trk_closed_loop_kernel<NT, 256, FM, DA, true>), dim3(l->n_channels), dim3(256), lds_bytes_hd, st, l->d_chans,  \
-                dev_records, n_epochs, lds_table_floats, limits, resident);                                                                             \
-        }                                                                                                                                     \
-    while (0)
-#define LAUNCH_LOOP_HD(NT, FM)                     \
-    do                                             \
-        {                                          \
-            if (pilot) LAUNCH_LOOP_HD_D(NT, FM, true); \
-            else LAUNCH_LOOP_HD_D(NT, FM, false);  \
-        }                                          \
-    while (0)
-            const size_t lds_bytes_hd = (size_t)(trk_hdr_floats(256) + lds_table_floats) * sizeof(float);
-            if (l->n_taps == 5)
-                {
-                    if (l->iq_format == GC_IQ_I16) LAUNCH_LOOP_HD(5, GC_IQ_I16);
-                    else if (l->iq_format == GC_IQ_I8) LAUNCH_LOOP_HD(5, GC_IQ_I8);
-                    else LAUNCH_LOOP_HD(5, GC_IQ_F32);
-                }
-            else
-                {
-                    if (l->iq_format == GC_IQ_I16) LAUNCH_LOOP_HD(3, GC_IQ_I16);
-                    else if (l->iq_format == GC_IQ_I8) LAUNCH_LOOP_HD(3, GC_IQ_I8);
-                    else LAUNCH_LOOP_HD(3, GC_IQ_F32);
-                }
-#undef LAUNCH_LOOP_HD
-#undef LAUNCH_LOOP_HD_D
-        }
-    else if (l->n_taps == 5)
-        {
-            if (threads == 1024) LAUNCH_LOOP_FMT(5, 1024);
-            else if (threads == 512) LAUNCH_LOOP_FMT(5, 512);
-            else LAUNCH_LOOP_FMT(5, 256);
+            GC_HIP(loop_slices_reserve(l, l->forced_slices, st));
+            le = loop_launch_slices(l, pilot, n_epochs, dev_records, st, l->forced_slices, (l->max_code_len + 64) * (pilot ? 2 : 1), limits);
         }
     else
-        {
-            if (threads == 1024) LAUNCH_LOOP_FMT(3, 1024);
-            else if (threads == 512) LAUNCH_LOOP_FMT(3, 512);
-            else LAUNCH_LOOP_FMT(3, 256);
-        }
-#undef LAUNCH_LOOP_FMT
-#undef LAUNCH_LOOP
-#undef LAUNCH_LOOP_D
-    }
-    {
-        hipError_t le = hipGetLastError();
-        if (le != hipSuccess)
-            {
-                cancel_all();
-                return gc_fail(GC_ERR_HIP, "gc_trk_loop_run: kernel launch failed: %s", hipGetErrorString(le));
-            }
-    }
-#undef LOOP_HIP_OR_CANCEL
-    // the kernel is enqueued: the tickets are committed whatever the event records below return (the error is reported afterwards)
+#endif
+    if (l->mixed)
+        le = loop_launch_mixed(l->d_chans, l->n_channels, l->iq_format, l->high_dyn, plan.threads, n_epochs, dev_records, st, plan.lds_table_floats, limits, plan.resident);
+    else
+        le = loop_launch_plain(a, l->n_taps, l->iq_format, pilot, l->high_dyn != 0);
+    if (le != hipSuccess) return gc_fail(GC_ERR_HIP, "gc_trk_loop_run: kernel launch failed: %s", hipGetErrorString(le));
     gc_status out = GC_OK;
     hipError_t ee = hipEventRecord(l->last_launch, st);
     l->launched = true;
-    if (ee == hipSuccess && any_ring)
+    if (ee == hipSuccess && rings.any)
         {
             ee = hipEventRecord(l->limit_done[slot], st);
             if (ee == hipSuccess)
@@ -943,16 +857,12 @@ static gc_status loop_launch(gc_trk_loop* l, int n_epochs, gc_loop_record* dev_r
         }
     if (ee != hipSuccess)
         {
-            // without its completion event the launch cannot be tracked: wait for it here, then commit
+            // without its completion event the launch cannot be tracked: wait for it here
             (void)hipStreamSynchronize(st);
             out = gc_fail(GC_ERR_HIP, "gc_trk_loop_run: hipEventRecord failed: %s", hipGetErrorString(ee));
         }
-    for (size_t k = 0; k < rings.size(); k++)
-        {
-            gc_status rs = gc_stream_end_read(rings[k], st, tickets[k]);
-            if (rs != GC_OK && out == GC_OK) out = rs;
-        }
-    return out;
+    const gc_status cs = reads.commit();
+    return out != GC_OK ? out : cs;
 }
 
 gc_status gc_trk_loop_run_dev(gc_trk_loop* l, int n_epochs, gc_loop_record* dev_records, void* stream)

@@ -5,6 +5,7 @@
 #define TRK_DEVICE_HPP
 #include "gnsscorr.h"
 #include "trk_kernels.h"
+#include "trk_loop_plan.h"  // trk_hdr_floats
 #include <hip/hip_runtime.h>
 #include <type_traits>
 
@@ -13,8 +14,6 @@
 #endif
 #define TRK_CHUNK (2 * TRK_THREADS)  // samples per workgroup iteration (2 per lane)
 #define TRK_HDR_FLOATS (TRK_THREADS / 64 * 16)
-// LDS header of a workgroup of `threads` threads: one (re, im) partial per wave and tap (GC_MAX_TAPS taps)
-static constexpr __host__ __device__ int trk_hdr_floats(int threads) { return threads / 64 * 16; }
 #define TRK_RESYNC 64  // iterations between exact re-evaluations of the carrier phase
 #ifndef TRK_PF
 #define TRK_PF 2  // chunks prefetched ahead of the one being processed (16-byte loads in flight per lane)

@@ -268,6 +268,33 @@ def test_closed_loop_workgroup_sizes_agree(gctx, oracle):
         assert np.max(np.abs(r["carrier_doppler_hz"] - base["carrier_doppler_hz"])) < 0.02
 
 
+def test_closed_loop_int8_input_equals_float_on_the_quantised_samples(gctx, oracle):
+    """GC_IQ_I8 on a plain (not mixed) engine: one channel, 8 code periods of 4000 samples; the records equal those of the float
+    engine on the same quantised samples cast to float (same arithmetic: block boundaries identical, sums to float rounding)."""
+    import gnsscorr
+    import torch
+    fs, n_ep = 4e6, 8
+    code, x = _signal(oracle, 9, fs, 4000 * (n_ep + 3), 321, 1210.0, 777.0)
+    conf = dict(GPS, acq_delay_samples=777.0, acq_doppler_hz=1200.0, acq_samplestamp_samples=0, sample_counter=0)
+    q = np.clip(np.round(x.view(np.float32).reshape(-1, 2) * 30), -128, 127).astype(np.int8)
+    recs = {}
+    for fmt, samples in ((gnsscorr.GC_IQ_F32, q.astype(np.float32)), (gnsscorr.GC_IQ_I8, q)):
+        d = torch.from_numpy(samples).cuda()
+        loop = gnsscorr.TrackingLoop(gctx, 1, 1023)
+        loop.set_input_format(fmt)
+        loop.set_input_dev(0, d.data_ptr(), q.shape[0])
+        loop.start(0, _conf(gnsscorr, **conf), code)
+        recs[fmt] = loop.run(n_ep)[0]
+        loop.close()
+    base, r = recs[gnsscorr.GC_IQ_F32], recs[gnsscorr.GC_IQ_I8]
+    assert np.all(base["valid"] == 1) and np.all(r["valid"] == 1)
+    assert np.array_equal(r["sample_counter"], base["sample_counter"])
+    assert np.array_equal(r["current_prn_length_samples"], base["current_prn_length_samples"])
+    err, top = np.max(np.abs(r["corr"] - base["corr"])), np.max(np.abs(base["corr"]))
+    print("int8 vs float corr: max error %g of max magnitude %g (%g)" % (err, top, err / top))
+    assert err <= 2e-5 * top
+
+
 def test_closed_loop_high_dynamics(gctx, oracle):
     """Dll_Pll_Conf::high_dyn on the device loop: the high-dynamics resampler / rotator kernels plus the carrier and code rate
     smoothers of update_tracking_vars (dll_pll_veml_tracking.cc:1016-1033, :1047-1064), on a signal whose Doppler ramps at
