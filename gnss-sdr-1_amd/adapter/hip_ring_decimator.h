@@ -6,8 +6,9 @@
  * With GNSS-SDR.use_acquisition_resampler=true the reference connects one fir_filter_ccf per signal between the signal conditioner
  * and the acquisition blocks (gnss_flowgraph.cc:375-499): decimation = floor(fs / opt_acq_fs) stepped down to a divisor of fs, taps
  * from firdes::low_pass(1.0, fs, acq_fs / 2.1, acq_fs / 10), and set_resampler_latency((taps - 1) / 2) on the acquisition.  This class
- * is that block: it plans with gc_acq_resampler_plan (the same rule, plus the library's limits D <= 64, T <= 1024), owns a GC_IQ_F32
- * ring at resampled_fs() and the device decimator (gc_ring_decimator) that writes it from `source`, and update() appends what the
+ * is that block: it plans with gc_acq_resampler_plan (the same rule, plus the library's limits D <= 64, T <= 1024), owns a ring
+ * at resampled_fs() -- gr_complex, or what the keys <role>.output_item_type ("gr_complex" | "cshort" | "cbyte") and <role>.output_scale
+ * (default 1; 127 for "cbyte" when the key is absent) of the second constructor ask for, with hip_signal_conditioner's meaning -- and the device decimator (gc_ring_decimator) that writes it from `source`, and update() appends what the
  * source's samples so far complete.  Derived sample m is source sample m * decimation(), delayed by latency() source samples.
  * Deviation: the reference switches the resampler off for item types other than gr_complex; this one reads every ring format.
  * enabled() is false -- and nothing is allocated -- when the plan's decimation is 1 ("Disabled acquisition resampler because the input
@@ -16,8 +17,10 @@
 #ifndef GNSSCORR_HIP_RING_DECIMATOR_H_
 #define GNSSCORR_HIP_RING_DECIMATOR_H_
 
+#include "gnss_sdr_types.h"
 #include "gnsscorr.h"
 #include <algorithm>
+#include <string>
 #include <vector>
 
 class hip_ring_decimator
@@ -32,6 +35,21 @@ public:
         if (d_status != GC_OK || d_decimation <= 1) return;
         d_taps.assign(static_cast<size_t>(n), 0.0f);
         d_status = gc_acq_resampler_plan(fs_in, opt_acq_fs_hz, &d_decimation, &d_resampled_fs, d_taps.data(), n, &n, &d_latency);
+    }
+    /*! The same with the derived ring's item type and scale taken from the configuration under `role`. */
+    hip_ring_decimator(gc_ctx* ctx, gc_stream* source, int64_t fs_in, uint32_t opt_acq_fs_hz, ConfigurationInterface* configuration, const std::string& role)
+        : hip_ring_decimator(ctx, source, fs_in, opt_acq_fs_hz)
+    {
+        const std::string type = configuration->property(role + ".output_item_type", std::string("gr_complex"));
+        if (type == "gr_complex") d_out_format = GC_IQ_F32;
+        else if (type == "cshort") d_out_format = GC_IQ_I16;
+        else if (type == "cbyte") d_out_format = GC_IQ_I8;
+        else
+            {
+                d_status = GC_ERR_INVALID;
+                return;
+            }
+        d_out_scale = configuration->property(role + ".output_scale", d_out_format == GC_IQ_I8 ? 127.0f : 1.0f);
     }
     ~hip_ring_decimator()
     {
@@ -52,9 +70,11 @@ public:
         d_status = gc_stream_info(d_source, nullptr, nullptr, &src_cap);
         if (d_status != GC_OK) return d_status;
         const uint64_t cap = std::max<uint64_t>(std::max<uint64_t>(ring_capacity, 2ull * max_window), src_cap / d_decimation + 1);
-        d_status = gc_stream_create(d_ctx, GC_IQ_F32, cap, max_window, &d_ring);
+        d_status = gc_stream_create(d_ctx, d_out_format, cap, max_window, &d_ring);
+        if (d_status == GC_OK && d_out_format != GC_IQ_F32) d_status = gc_stream_accept_quantised_output(d_ring);
         if (d_status == GC_OK)
             d_status = gc_ring_decimator_create(d_ctx, d_source, d_decimation, d_taps.data(), static_cast<uint32_t>(d_taps.size()), d_ring, &d_decim);
+        if (d_status == GC_OK && d_out_format != GC_IQ_F32) d_status = gc_ring_decimator_set_output_scale(d_decim, d_out_scale);
         return d_status;
     }
     //! appends the outputs the source's samples so far complete (asynchronous)
@@ -78,6 +98,16 @@ public:
         if (d_decim) gc_ring_decimator_info(d_decim, nullptr, &h);
         return h;
     }
+    //! gc_iq_format of the derived ring and the factor in front of its clamp (1 for gr_complex)
+    int output_format() const { return d_out_format; }
+    float output_scale() const { return d_out_format == GC_IQ_F32 ? 1.0f : d_out_scale; }
+    //! components of a cshort / cbyte ring that hit the clamp so far (0 for gr_complex); waits for the updates so far
+    uint64_t clipped_components() const
+    {
+        uint64_t n = 0;
+        if (d_decim) gc_ring_decimator_output_info(d_decim, nullptr, nullptr, &n);
+        return n;
+    }
     gc_status last_status() const { return d_status; }
 
 private:
@@ -89,6 +119,8 @@ private:
     gc_stream* d_ring = nullptr;
     gc_ring_decimator* d_decim = nullptr;
     gc_status d_status = GC_OK;
+    int d_out_format = GC_IQ_F32;
+    float d_out_scale = 1.0f;
 };
 
 #endif  // GNSSCORR_HIP_RING_DECIMATOR_H_

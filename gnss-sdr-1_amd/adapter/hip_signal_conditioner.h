@@ -25,8 +25,12 @@
  *   length                     samples per segment                            (default 32)
  *   segments_est               segments of a noise-floor estimate             (default 12500)
  *   segments_reset             segments after which the floor is re-estimated (default 5000000)
- * -- owns a GC_IQ_F32 ring at sampling_frequency / D plus the device conditioner (gc_conditioner) that writes it, and hands the ring to
- * the acquisition bank and the tracking group.  The output item type is always gr_complex.  general_work of the source-side block
+ *   output_item_type           "gr_complex" | "cshort" | "cbyte": the ring's format, GC_IQ_F32 / GC_IQ_I16 / GC_IQ_I8 -- 8 / 4 / 2 bytes
+ *                              per sample for everything that reads it           (default "gr_complex")
+ *   output_scale               factor in front of the clamp of a cshort / cbyte ring: q = rint(clamp(y * output_scale))
+ *                              (default 1; 127 for "cbyte" when the key is absent, the reference's complex_float_to_complex_byte)
+ * -- owns a ring of output_item_type at sampling_frequency / D plus the device conditioner (gc_conditioner) that writes it, and hands the
+ * ring to the acquisition bank and the tracking group.  general_work of the source-side block
  * calls push(items, n) with n counted in SAMPLES for every item type (a multiple of 4 for "2bit": samples_per_byte() is 4 there,
  * which item_size() cannot express); pulse_blanking is not available with "2bit".  Everything downstream addresses the ring by sample number at the OUTPUT rate.  The filter delays the signal
  * by group_delay_samples() output samples; as in the reference, that is left in the observables.
@@ -76,6 +80,16 @@ public:
                 d_status = GC_ERR_INVALID;
                 return;
             }
+        d_out_item_type = configuration->property(role + ".output_item_type", std::string("gr_complex"));
+        if (d_out_item_type == "gr_complex") d_out_format = GC_IQ_F32;
+        else if (d_out_item_type == "cshort") d_out_format = GC_IQ_I16;
+        else if (d_out_item_type == "cbyte") d_out_format = GC_IQ_I8;
+        else
+            {
+                d_status = GC_ERR_INVALID;
+                return;
+            }
+        d_out_scale = configuration->property(role + ".output_scale", d_out_format == GC_IQ_I8 ? 127.0f : 1.0f);
         if (filter_type == "lowpass")
             {
                 const double bw = configuration->property(role + ".bw", (d_fs_in / d_decimation) / 2.0);
@@ -111,8 +125,10 @@ public:
         b.segments_est = static_cast<uint32_t>(segments_est);
         b.segments_reset = static_cast<uint32_t>(segments_reset);
         b.reserved = 0;
-        d_status = gc_stream_create(ctx, GC_IQ_F32, ring_capacity, max_window, &d_ring);
+        d_status = gc_stream_create(ctx, d_out_format, ring_capacity, max_window, &d_ring);
+        if (d_status == GC_OK && d_out_format != GC_IQ_F32) d_status = gc_stream_accept_quantised_output(d_ring);
         if (d_status == GC_OK) d_status = gc_conditioner_create(ctx, &c, d_taps.data(), d_ring, &d_cond);
+        if (d_status == GC_OK && d_out_format != GC_IQ_F32) d_status = gc_conditioner_set_output_scale(d_cond, d_out_scale);
         if (d_status == GC_OK && d_blanking) d_status = gc_conditioner_set_pulse_blanking(d_cond, &b);
         if (d_status != GC_OK && d_cond != nullptr)
             {
@@ -155,6 +171,16 @@ public:
     int samples_per_byte() const { return d_format == GC_RAW_REAL_2BIT ? 4 : 0; }
     //! true when the raw samples are real ("float", "short", "byte", "2bit")
     bool real_input() const { return d_format >= GC_RAW_REAL_F32; }
+    //! gc_iq_format of the ring (output_item_type) and the factor in front of its clamp (1 for gr_complex)
+    int output_format() const { return d_out_format; }
+    float output_scale() const { return d_out_format == GC_IQ_F32 ? 1.0f : d_out_scale; }
+    //! components of a cshort / cbyte ring that hit the clamp so far (0 for gr_complex); waits for the pushes so far
+    uint64_t clipped_components() const
+    {
+        uint64_t n = 0;
+        if (d_cond) gc_conditioner_output_info(d_cond, nullptr, nullptr, &n);
+        return n;
+    }
     std::string role() const { return d_role; }
     std::string implementation() const { return "Freq_Xlating_Fir_Filter"; }
 
@@ -191,11 +217,12 @@ public:
     gc_status last_status() const { return d_status; }
 
 private:
-    std::string d_role, d_item_type;
+    std::string d_role, d_item_type, d_out_item_type;
     std::vector<float> d_taps;
     double d_if = 0.0, d_fs_in = 0.0;
     int32_t d_decimation = 1;
-    int d_format = GC_IQ_F32;
+    int d_format = GC_IQ_F32, d_out_format = GC_IQ_F32;
+    float d_out_scale = 1.0f;
     bool d_blanking = false;
     gc_stream* d_ring = nullptr;
     gc_conditioner* d_cond = nullptr;

@@ -23,9 +23,12 @@ struct CondJob
     unsigned long long phase_inc;  // turns per input sample in units of 2^-64; 0 = no mixer
     unsigned long long first_out;  // absolute number m of the first output of the piece
     unsigned n_out;                // outputs in the piece
-    float2* dst;                   // where output first_out goes (ring position first_out % capacity)
-    float2* mirror_dst;            // the same position behind the ring
+    void* dst;                     // where output first_out goes (ring position first_out % capacity), in the ring's format: the
+                                   // host computes it with the ring's bytes per sample (8 / 4 / 2)
+    void* mirror_dst;              // the same position behind the ring
     unsigned n_mirror;             // the first n_mirror outputs of the piece are stored to mirror_dst as well
+    float out_scale;               // GC_IQ_I16 / GC_IQ_I8 output rings: the factor in front of the clamp (cond_store_epilogue.h)
+    unsigned long long* clipped;   // GC_IQ_I16 / GC_IQ_I8 output rings: the conditioner's count of clipped components (HBM)
 };
 
 // Outputs per workgroup for a launch (a multiple of 64, at most 1024): as many as fit in GC_COND_LDS_SAMPLES, fewer when the
@@ -37,7 +40,8 @@ int cond_tile_outputs(int decimation, int n_taps, unsigned n_out, int want_group
 unsigned cond_raw_align(int iq_format);
 // Bits per raw sample: 64 / 32 / 16 for gr_complex / cshort / cbyte, 32 / 16 / 8 / 2 for the real formats; 0 for an unknown format.
 unsigned cond_raw_bits(int iq_format);
-// Enqueues the conditioner for one piece on `st`.  iq_format: format of the raw ring (gc_iq_format or gc_raw_real_format).
-hipError_t cond_launch(int iq_format, hipStream_t st, const CondJob& job, int tile_outputs);
+// Enqueues the conditioner for one piece on `st`.  iq_format: format of the raw ring (gc_iq_format or gc_raw_real_format);
+// out_format: gc_iq_format of the output ring.
+hipError_t cond_launch(int iq_format, int out_format, hipStream_t st, const CondJob& job, int tile_outputs);
 
 #endif

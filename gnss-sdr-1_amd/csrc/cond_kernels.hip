@@ -15,9 +15,11 @@
 // barrier: a 16-byte vector holds 4, 8, 16 or 64 of them, a sample is one field of one of its four dwords (shift and sign
 // extension in registers), and the mixer is two products, z = (x cos, -(x sin)) -- what the complex front end gives for (x, 0).
 // A lane walks its vector from a start that depends on the lane, so that the 16 lanes that share a ds_write_b64 pass spread over the
-// banks (cond_front_real).  The accumulation and the stores are the shared code below.
+// banks (cond_front_real).  The accumulation and the stores are shared code (cond_fir_accum.h, cond_store_epilogue.h); OUT is the
+// output ring's format, and the GC_IQ_F32 instantiation stores the accumulators as they are.
 #include "cond_kernels.h"
 #include "cond_fir_accum.h"
+#include "cond_store_epilogue.h"
 
 typedef float cond_f32x4 __attribute__((ext_vector_type(4)));
 typedef short cond_i16x8 __attribute__((ext_vector_type(8)));
@@ -219,7 +221,7 @@ static __device__ __forceinline__ void cond_front_real(const CondJob& job, float
         }
 }
 
-template <int FMT, int R, bool MIX>
+template <int FMT, int OUT, int R, bool MIX>
 __global__ __launch_bounds__(GC_COND_THREADS) void cond_fir_decim_kernel(const CondJob job, const int tile, const int rowlen)
 {
     extern __shared__ float2 cond_lds[];
@@ -241,15 +243,8 @@ __global__ __launch_bounds__(GC_COND_THREADS) void cond_fir_decim_kernel(const C
     for (int r = 0; r < R; r++) j[r] = min(tid + r * GC_COND_THREADS, tn - 1);
     float2 acc[R];
     cond_fir_accumulate<R>(cond_lds, rowlen, D, T, job.taps, j, acc);
-#pragma unroll
-    for (int r = 0; r < R; r++)
-        {
-            const int jj = tid + r * GC_COND_THREADS;
-            if (jj >= tn) continue;
-            const unsigned o = o0 + (unsigned)jj;
-            job.dst[o] = acc[r];
-            if (o < job.n_mirror) job.mirror_dst[o] = acc[r];  // the mirror is written here: no HBM-to-HBM copy follows
-        }
+    const CondStoreDst out = {job.dst, job.mirror_dst, job.n_mirror, job.out_scale, job.clipped};
+    cond_store_tile<OUT, R, GC_COND_THREADS>(cond_lds, acc, tn, o0, out);
 }
 
 static int cond_rowlen(int decimation, int n_taps, int tile) { return cond_fir_rowlen(decimation, n_taps, tile); }
@@ -262,25 +257,37 @@ int cond_tile_outputs(int decimation, int n_taps, unsigned n_out, int want_group
     return tile;
 }
 
-template <int FMT, int R>
+template <int FMT, int OUT, int R>
 static void cond_launch_r(bool mix, dim3 grid, size_t lds_bytes, hipStream_t st, const CondJob& job, int tile, int rowlen)
 {
     if (mix)
-        hipLaunchKernelGGL((cond_fir_decim_kernel<FMT, R, true>), grid, dim3(GC_COND_THREADS), lds_bytes, st, job, tile, rowlen);
+        hipLaunchKernelGGL((cond_fir_decim_kernel<FMT, OUT, R, true>), grid, dim3(GC_COND_THREADS), lds_bytes, st, job, tile, rowlen);
     else
-        hipLaunchKernelGGL((cond_fir_decim_kernel<FMT, R, false>), grid, dim3(GC_COND_THREADS), lds_bytes, st, job, tile, rowlen);
+        hipLaunchKernelGGL((cond_fir_decim_kernel<FMT, OUT, R, false>), grid, dim3(GC_COND_THREADS), lds_bytes, st, job, tile, rowlen);
 }
 
-template <int FMT>
-static void cond_launch_fmt(dim3 grid, size_t lds_bytes, hipStream_t st, const CondJob& job, int tile, int rowlen)
+template <int FMT, int OUT>
+static void cond_launch_out(dim3 grid, size_t lds_bytes, hipStream_t st, const CondJob& job, int tile, int rowlen)
 {
     const bool mix = job.phase_inc != 0;
     if (tile <= GC_COND_THREADS)
-        cond_launch_r<FMT, 1>(mix, grid, lds_bytes, st, job, tile, rowlen);
+        cond_launch_r<FMT, OUT, 1>(mix, grid, lds_bytes, st, job, tile, rowlen);
     else if (tile <= 2 * GC_COND_THREADS)
-        cond_launch_r<FMT, 2>(mix, grid, lds_bytes, st, job, tile, rowlen);
+        cond_launch_r<FMT, OUT, 2>(mix, grid, lds_bytes, st, job, tile, rowlen);
     else
-        cond_launch_r<FMT, 4>(mix, grid, lds_bytes, st, job, tile, rowlen);
+        cond_launch_r<FMT, OUT, 4>(mix, grid, lds_bytes, st, job, tile, rowlen);
+}
+
+template <int FMT>
+static bool cond_launch_fmt(int out_format, dim3 grid, size_t lds_bytes, hipStream_t st, const CondJob& job, int tile, int rowlen)
+{
+    switch (out_format)
+        {
+        case GC_IQ_F32: cond_launch_out<FMT, GC_IQ_F32>(grid, lds_bytes, st, job, tile, rowlen); return true;
+        case GC_IQ_I16: cond_launch_out<FMT, GC_IQ_I16>(grid, lds_bytes, st, job, tile, rowlen); return true;
+        case GC_IQ_I8: cond_launch_out<FMT, GC_IQ_I8>(grid, lds_bytes, st, job, tile, rowlen); return true;
+        default: return false;
+        }
 }
 
 unsigned cond_raw_align(int iq_format)
@@ -313,29 +320,32 @@ unsigned cond_raw_bits(int iq_format)
         }
 }
 
-hipError_t cond_launch(int iq_format, hipStream_t st, const CondJob& job, int tile)
+hipError_t cond_launch(int iq_format, int out_format, hipStream_t st, const CondJob& job, int tile)
 {
     if (job.n_out == 0) return hipSuccess;
     const unsigned align = cond_raw_align(iq_format);
     if (job.decimation < 1 || job.decimation > GC_COND_MAX_DECIMATION || job.n_taps < 1 || job.n_taps > GC_COND_MAX_TAPS || tile < 64 ||
         tile > 4 * GC_COND_THREADS || align == 0 || job.raw_cap % align != 0)
         return hipErrorInvalidValue;
+    if (out_format != GC_IQ_F32 && (job.clipped == nullptr || !(job.out_scale > 0.0f))) return hipErrorInvalidValue;
     const int rowlen = cond_rowlen(job.decimation, job.n_taps, tile);
     const size_t lds_samples = (size_t)job.decimation * rowlen;
     // a tile's inputs (plus one vector of slack on each side) must fit in the raw ring without lapping it
     if (lds_samples > GC_COND_LDS_SAMPLES || (size_t)tile * job.decimation + job.n_taps + 2 * align >= job.raw_cap) return hipErrorInvalidValue;
     const dim3 grid((job.n_out + (unsigned)tile - 1) / (unsigned)tile);
     const size_t lds_bytes = lds_samples * sizeof(float2);
+    bool ok = false;
     switch (iq_format)
         {
-        case GC_IQ_F32: cond_launch_fmt<GC_IQ_F32>(grid, lds_bytes, st, job, tile, rowlen); break;
-        case GC_IQ_I16: cond_launch_fmt<GC_IQ_I16>(grid, lds_bytes, st, job, tile, rowlen); break;
-        case GC_IQ_I8: cond_launch_fmt<GC_IQ_I8>(grid, lds_bytes, st, job, tile, rowlen); break;
-        case GC_RAW_REAL_F32: cond_launch_fmt<GC_RAW_REAL_F32>(grid, lds_bytes, st, job, tile, rowlen); break;
-        case GC_RAW_REAL_I16: cond_launch_fmt<GC_RAW_REAL_I16>(grid, lds_bytes, st, job, tile, rowlen); break;
-        case GC_RAW_REAL_I8: cond_launch_fmt<GC_RAW_REAL_I8>(grid, lds_bytes, st, job, tile, rowlen); break;
-        case GC_RAW_REAL_2BIT: cond_launch_fmt<GC_RAW_REAL_2BIT>(grid, lds_bytes, st, job, tile, rowlen); break;
+        case GC_IQ_F32: ok = cond_launch_fmt<GC_IQ_F32>(out_format, grid, lds_bytes, st, job, tile, rowlen); break;
+        case GC_IQ_I16: ok = cond_launch_fmt<GC_IQ_I16>(out_format, grid, lds_bytes, st, job, tile, rowlen); break;
+        case GC_IQ_I8: ok = cond_launch_fmt<GC_IQ_I8>(out_format, grid, lds_bytes, st, job, tile, rowlen); break;
+        case GC_RAW_REAL_F32: ok = cond_launch_fmt<GC_RAW_REAL_F32>(out_format, grid, lds_bytes, st, job, tile, rowlen); break;
+        case GC_RAW_REAL_I16: ok = cond_launch_fmt<GC_RAW_REAL_I16>(out_format, grid, lds_bytes, st, job, tile, rowlen); break;
+        case GC_RAW_REAL_I8: ok = cond_launch_fmt<GC_RAW_REAL_I8>(out_format, grid, lds_bytes, st, job, tile, rowlen); break;
+        case GC_RAW_REAL_2BIT: ok = cond_launch_fmt<GC_RAW_REAL_2BIT>(out_format, grid, lds_bytes, st, job, tile, rowlen); break;
         default: return hipErrorInvalidValue;
         }
+    if (!ok) return hipErrorInvalidValue;
     return hipGetLastError();
 }

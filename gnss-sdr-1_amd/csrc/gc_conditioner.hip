@@ -12,6 +12,9 @@
 // segments it completes get their energies, their decisions and -- the flagged ones -- zeros in place (cond_blank_kernels.hip), and
 // the FIR launch covers the outputs whose newest input those segments decide.  The undecided tail (< L samples) waits in the raw
 // ring for the next push, in front of the T - 1 samples of history.
+//
+// The output ring may have any gc_iq_format.  The kernel's store epilogue (cond_store_epilogue.h) scales, clamps and rounds into a
+// GC_IQ_I16 / GC_IQ_I8 ring and counts the clipped components in d_clipped; a GC_IQ_F32 ring has neither a scale nor a counter.
 #include "cond_blank_kernels.h"
 #include "cond_kernels.h"
 #include "gc_stream.h"
@@ -41,6 +44,9 @@ struct gc_conditioner
     float* d_blank_energy = nullptr;        // one chunk's segments
     unsigned char* d_blank_flags = nullptr;
     uint64_t blank_max_seg = 0;             // segments one chunk can complete
+    // GC_IQ_I16 / GC_IQ_I8 output rings (gc_conditioner_set_output_scale, gc_conditioner_output_info)
+    float out_scale = 1.0f;
+    unsigned long long* d_clipped = nullptr;  // clipped components so far; nullptr for a GC_IQ_F32 ring
     // pinned staging for pageable caller buffers (as in gc_stream)
     static const int kSlots = 2;
     char* h_slot[kSlots] = {nullptr, nullptr};
@@ -73,11 +79,13 @@ struct cond_writer : gc_ring_writer
         job.phase_inc = c->phase_inc;
         job.first_out = idx;
         job.n_out = (unsigned)*len;
-        job.dst = reinterpret_cast<float2*>(s->d_ring) + pos;
-        job.mirror_dst = reinterpret_cast<float2*>(s->d_ring) + s->capacity + pos;
+        job.dst = s->d_ring + pos * s->elem;
+        job.mirror_dst = s->d_ring + (s->capacity + pos) * s->elem;
         job.n_mirror = pos < s->mirror ? (unsigned)std::min<uint64_t>(*len, s->mirror - pos) : 0u;
+        job.out_scale = c->out_scale;
+        job.clipped = c->d_clipped;
         const int tile = cond_tile_outputs(job.decimation, job.n_taps, job.n_out, 2 * std::max(1, c->ctx->n_cus));
-        GC_HIP(cond_launch(c->conf.in_format, s->copy_stream, job, tile));
+        GC_HIP(cond_launch(c->conf.in_format, s->iq_format, s->copy_stream, job, tile));
         return GC_OK;
     }
 };
@@ -145,6 +153,7 @@ void cond_release(gc_conditioner* c)
         }
     (void)hipFree(c->d_raw);
     (void)hipFree(c->d_taps);
+    (void)hipFree(c->d_clipped);
     cond_blank_free(c);
     for (int i = 0; i < gc_conditioner::kSlots; i++)
         {
@@ -242,7 +251,8 @@ gc_status gc_conditioner_create(gc_ctx* ctx, const gc_conditioner_conf* conf, co
     if (st != GC_OK) return st;
     GC_REQUIRE(ctx && out_ring && out, "gc_conditioner_create: NULL argument");
     GC_REQUIRE(out_ring->ctx == ctx, "gc_conditioner_create: the output ring belongs to another context");
-    GC_REQUIRE(out_ring->iq_format == GC_IQ_F32, "gc_conditioner_create: the output ring must be GC_IQ_F32");
+    GC_REQUIRE(out_ring->iq_format == GC_IQ_F32 || out_ring->quantised_output,
+        "gc_conditioner_create: the output ring must be GC_IQ_F32, or an integer ring opened with gc_stream_accept_quantised_output");
     gc_device_guard g(ctx->device);
     {
         std::lock_guard<std::mutex> no_push(out_ring->push_mtx);
@@ -272,6 +282,8 @@ gc_status gc_conditioner_create(gc_ctx* ctx, const gc_conditioner_conf* conf, co
     if (e == hipSuccess) e = hipMemset(c->d_raw, 0, raw_bytes(c, c->raw_cap));
     if (e == hipSuccess) e = hipMalloc(&c->d_taps, sizeof(float) * conf->n_taps);
     if (e == hipSuccess) e = hipMemcpy(c->d_taps, taps, sizeof(float) * conf->n_taps, hipMemcpyHostToDevice);
+    if (e == hipSuccess && out_ring->iq_format != GC_IQ_F32) e = hipMalloc(&c->d_clipped, sizeof(unsigned long long));
+    if (e == hipSuccess && c->d_clipped) e = hipMemset(c->d_clipped, 0, sizeof(unsigned long long));
     for (int i = 0; i < gc_conditioner::kSlots && e == hipSuccess; i++)
         {
             e = hipHostMalloc(reinterpret_cast<void**>(&c->h_slot[i]), slot_bytes, hipHostMallocDefault);
@@ -313,6 +325,35 @@ gc_status gc_conditioner_info(gc_conditioner* c, uint64_t* in_head, uint64_t* ou
     const uint64_t D = c->conf.decimation;
     if (in_head) *in_head = c->in_head;
     if (out_head) *out_head = (cond_decided(c, c->in_head) + D - 1) / D;
+    return GC_OK;
+}
+
+gc_status gc_conditioner_set_output_scale(gc_conditioner* c, float scale)
+{
+    // the arguments first, before anything that needs a device
+    GC_REQUIRE(std::isfinite(scale) && scale > 0.0f, "gc_conditioner_set_output_scale: scale %g is not finite and positive", (double)scale);
+    GC_REQUIRE(c, "gc_conditioner_set_output_scale: NULL handle");
+    GC_REQUIRE(c->out->iq_format != GC_IQ_F32, "gc_conditioner_set_output_scale: a GC_IQ_F32 output ring has no scale");
+    std::lock_guard<std::mutex> one_push(c->mtx);
+    if (c->in_head != 0) return gc_fail(GC_ERR_STATE, "gc_conditioner_set_output_scale: samples have been pushed already");
+    c->out_scale = scale;
+    return GC_OK;
+}
+
+gc_status gc_conditioner_output_info(gc_conditioner* c, int32_t* out_format, float* scale, uint64_t* clipped_components)
+{
+    GC_REQUIRE(c, "gc_conditioner_output_info: NULL handle");
+    std::lock_guard<std::mutex> one_push(c->mtx);
+    unsigned long long n = 0;
+    if (c->d_clipped && clipped_components)
+        {
+            gc_device_guard g(c->ctx->device);
+            GC_HIP(hipStreamSynchronize(c->out->copy_stream));
+            GC_HIP(hipMemcpy(&n, c->d_clipped, sizeof n, hipMemcpyDeviceToHost));
+        }
+    if (out_format) *out_format = c->out->iq_format;
+    if (scale) *scale = c->d_clipped ? c->out_scale : 1.0f;
+    if (clipped_components) *clipped_components = n;
     return GC_OK;
 }
 

@@ -8,6 +8,9 @@
 // floor max(0, m0 D - (T - 1)) (m0 = the output ring's head), which makes the output ring's copy stream wait for the newest source
 // push and keeps later pushes from evicting what the launch reads, appends through gc_stream_produce with a kernel writer, and
 // commits the ticket behind the launches.  Output m is always source sample mD: the decimator starts at sample 0 of the source.
+//
+// The output ring may have any gc_iq_format: the kernel's store epilogue (cond_store_epilogue.h, the conditioner's) scales, clamps
+// and rounds into a GC_IQ_I16 / GC_IQ_I8 ring and counts the clipped components in d_clipped.
 #include "gc_stream.h"
 #include "ring_decim_kernels.h"
 #include <algorithm>
@@ -24,6 +27,9 @@ struct gc_ring_decimator
     float* d_taps = nullptr;
     uint64_t src_consumed = 0;  // source head the newest update saw
     uint64_t out_head = 0;      // outputs appended so far
+    bool updated = false;       // gc_ring_decimator_update has been called: the output scale is fixed
+    float out_scale = 1.0f;     // GC_IQ_I16 / GC_IQ_I8 output rings
+    unsigned long long* d_clipped = nullptr;  // clipped components so far; nullptr for a GC_IQ_F32 ring
     std::mutex mtx;             // one update at a time
 };
 
@@ -45,11 +51,13 @@ struct rdec_writer : gc_ring_writer
         job.decimation = (int)d->decimation;
         job.first_out = idx;
         job.n_out = (unsigned)*len;
-        job.dst = reinterpret_cast<float2*>(s->d_ring) + pos;
-        job.mirror_dst = reinterpret_cast<float2*>(s->d_ring) + s->capacity + pos;
+        job.dst = s->d_ring + pos * s->elem;
+        job.mirror_dst = s->d_ring + (s->capacity + pos) * s->elem;
         job.n_mirror = pos < s->mirror ? (unsigned)std::min<uint64_t>(*len, s->mirror - pos) : 0u;
+        job.out_scale = d->out_scale;
+        job.clipped = d->d_clipped;
         const int tile = ring_decim_tile_outputs(job.decimation, job.n_taps, job.n_out, std::max(1, d->ctx->n_cus));
-        GC_HIP(ring_decim_launch(d->src->iq_format, s->copy_stream, job, tile));
+        GC_HIP(ring_decim_launch(d->src->iq_format, s->iq_format, s->copy_stream, job, tile));
         return GC_OK;
     }
 };
@@ -63,6 +71,7 @@ void rdec_release(gc_ring_decimator* d)
             d->out->kernel_fed = false;
         }
     (void)hipFree(d->d_taps);
+    (void)hipFree(d->d_clipped);
     if (d->out) gc_stream_drop(d->out);
     if (d->src) gc_stream_drop(d->src);
 }
@@ -92,7 +101,8 @@ gc_status gc_ring_decimator_create(gc_ctx* ctx, gc_stream* src_ring, uint32_t de
     GC_REQUIRE(ctx && src_ring && out_ring && out, "gc_ring_decimator_create: NULL argument");
     GC_REQUIRE(src_ring != out_ring, "gc_ring_decimator_create: the source ring and the output ring are the same ring");
     GC_REQUIRE(src_ring->ctx == ctx && out_ring->ctx == ctx, "gc_ring_decimator_create: a ring belongs to another context");
-    GC_REQUIRE(out_ring->iq_format == GC_IQ_F32, "gc_ring_decimator_create: the output ring must be GC_IQ_F32");
+    GC_REQUIRE(out_ring->iq_format == GC_IQ_F32 || out_ring->quantised_output,
+        "gc_ring_decimator_create: the output ring must be GC_IQ_F32, or an integer ring opened with gc_stream_accept_quantised_output");
     {
         std::lock_guard<std::mutex> lk(src_ring->mtx);
         if (gc_stream_oldest(src_ring) != 0)
@@ -118,6 +128,8 @@ gc_status gc_ring_decimator_create(gc_ctx* ctx, gc_stream* src_ring, uint32_t de
     d->n_taps = n_taps;
     hipError_t e = hipMalloc(&d->d_taps, sizeof(float) * n_taps);
     if (e == hipSuccess) e = hipMemcpy(d->d_taps, taps, sizeof(float) * n_taps, hipMemcpyHostToDevice);
+    if (e == hipSuccess && out_ring->iq_format != GC_IQ_F32) e = hipMalloc(&d->d_clipped, sizeof(unsigned long long));
+    if (e == hipSuccess && d->d_clipped) e = hipMemset(d->d_clipped, 0, sizeof(unsigned long long));
     if (e != hipSuccess)
         {
             rdec_release(d);
@@ -143,6 +155,7 @@ gc_status gc_ring_decimator_update(gc_ring_decimator* d, uint64_t* first_out, ui
     if (n_out) *n_out = 0;
     GC_REQUIRE(d, "gc_ring_decimator_update: NULL handle");
     std::lock_guard<std::mutex> one_update(d->mtx);
+    d->updated = true;
     gc_device_guard g(d->ctx->device);
     const uint64_t D = d->decimation, T = d->n_taps;
     const uint64_t m0 = d->out_head;
@@ -179,6 +192,35 @@ gc_status gc_ring_decimator_update(gc_ring_decimator* d, uint64_t* first_out, ui
     const gc_status st_end = reads.commit();
     if (n_out) *n_out = m - m0;
     return st != GC_OK ? st : st_end;
+}
+
+gc_status gc_ring_decimator_set_output_scale(gc_ring_decimator* d, float scale)
+{
+    // the arguments first, before anything that needs a device
+    GC_REQUIRE(std::isfinite(scale) && scale > 0.0f, "gc_ring_decimator_set_output_scale: scale %g is not finite and positive", (double)scale);
+    GC_REQUIRE(d, "gc_ring_decimator_set_output_scale: NULL handle");
+    GC_REQUIRE(d->out->iq_format != GC_IQ_F32, "gc_ring_decimator_set_output_scale: a GC_IQ_F32 output ring has no scale");
+    std::lock_guard<std::mutex> one_update(d->mtx);
+    if (d->updated) return gc_fail(GC_ERR_STATE, "gc_ring_decimator_set_output_scale: the decimator has been updated already");
+    d->out_scale = scale;
+    return GC_OK;
+}
+
+gc_status gc_ring_decimator_output_info(gc_ring_decimator* d, int32_t* out_format, float* scale, uint64_t* clipped_components)
+{
+    GC_REQUIRE(d, "gc_ring_decimator_output_info: NULL handle");
+    std::lock_guard<std::mutex> one_update(d->mtx);
+    unsigned long long n = 0;
+    if (d->d_clipped && clipped_components)
+        {
+            gc_device_guard g(d->ctx->device);
+            GC_HIP(hipStreamSynchronize(d->out->copy_stream));
+            GC_HIP(hipMemcpy(&n, d->d_clipped, sizeof n, hipMemcpyDeviceToHost));
+        }
+    if (out_format) *out_format = d->out->iq_format;
+    if (scale) *scale = d->d_clipped ? d->out_scale : 1.0f;
+    if (clipped_components) *clipped_components = n;
+    return GC_OK;
 }
 
 gc_status gc_ring_decimator_info(gc_ring_decimator* d, uint64_t* src_consumed, uint64_t* out_head)

@@ -42,6 +42,7 @@ struct gc_stream
     std::mutex mtx;
     std::mutex push_mtx;  // one push at a time (a push may release mtx while it waits for readers)
     std::atomic<int> refs{1};  // the creator's reference + one per batch channel that reads the ring
+    bool quantised_output = false;  // gc_stream_accept_quantised_output: a conditioner / ring decimator may quantise into this integer ring
     bool kernel_fed = false;   // a kernel writes the ring (gc_conditioner.hip, gc_ring_decimator.hip): gc_stream_push is refused
 };
 

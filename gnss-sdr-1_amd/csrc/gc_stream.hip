@@ -263,6 +263,18 @@ gc_status gc_stream_info(gc_stream* s, uint64_t* oldest_index, uint64_t* head_in
     return GC_OK;
 }
 
+gc_status gc_stream_accept_quantised_output(gc_stream* s)
+{
+    GC_REQUIRE(s, "gc_stream_accept_quantised_output: NULL handle");
+    GC_REQUIRE(s->iq_format != GC_IQ_F32, "gc_stream_accept_quantised_output: a GC_IQ_F32 ring holds outputs as they are; nothing is quantised into it");
+    std::lock_guard<std::mutex> no_push(s->push_mtx);
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (s->kernel_fed) return gc_fail(GC_ERR_STATE, "gc_stream_accept_quantised_output: the ring already has a producer on the device");
+    if (s->head != 0) return gc_fail(GC_ERR_STATE, "gc_stream_accept_quantised_output: samples have been pushed into the ring already");
+    s->quantised_output = true;
+    return GC_OK;
+}
+
 gc_status gc_stream_read(gc_stream* s, uint64_t first_index, uint64_t n_samples, void* host_out)
 {
     GC_REQUIRE(s && (host_out || n_samples == 0), "gc_stream_read: NULL argument");

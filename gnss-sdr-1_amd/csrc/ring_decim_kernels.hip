@@ -8,10 +8,11 @@
 // of sample 0, at most two contiguous pieces of the source ring: the split is found once per tile (one modulo, uniform), and each
 // piece is loaded with 16-byte loads from its first 16-byte boundary on, with single-sample loads for the < 16 bytes at either
 // ragged end -- the ring's capacity need not be a multiple of anything, and nothing past the ring's end (its mirror) is read.
-// Samples go to LDS in the conditioner's polyphase order and are accumulated by the conditioner's code (cond_fir_accum.h), so an
-// output's bits are a function of the source samples alone.
+// Samples go to LDS in the conditioner's polyphase order, are accumulated by the conditioner's code (cond_fir_accum.h) and stored by
+// its epilogue (cond_store_epilogue.h; OUT is the output ring's format), so an output's bits are a function of the source samples alone.
 #include "ring_decim_kernels.h"
 #include "cond_fir_accum.h"
+#include "cond_store_epilogue.h"
 #include <algorithm>
 
 typedef float rdec_f32x4 __attribute__((ext_vector_type(4)));
@@ -82,7 +83,7 @@ static __device__ __forceinline__ void rdec_load_piece(float2* lds, int rowlen, 
         }
 }
 
-template <int FMT>
+template <int FMT, int OUT>
 __global__ __launch_bounds__(GC_RDEC_THREADS) void ring_decim_kernel(const RingDecimJob job, const int tile, const int rowlen)
 {
     extern __shared__ float2 rdec_lds[];
@@ -103,14 +104,16 @@ __global__ __launch_bounds__(GC_RDEC_THREADS) void ring_decim_kernel(const RingD
     rdec_load_piece<FMT>(rdec_lds, rowlen, (unsigned)D, ring, pos, n_zero, n1);
     rdec_load_piece<FMT>(rdec_lds, rowlen, (unsigned)D, ring, 0u, n_zero + n1, n - n1);
     __syncthreads();
-    if (tid >= tn) return;
+    // the integer epilogues hold barriers: there the lanes past the end of a short tile stay, read the last output's samples and
+    // store nothing
+    if constexpr (OUT == GC_IQ_F32)
+        if (tid >= tn) return;
 
-    int j[1] = {tid};
+    int j[1] = {min(tid, tn - 1)};
     float2 acc[1];
     cond_fir_accumulate<1>(rdec_lds, rowlen, D, T, job.taps, j, acc);
-    const unsigned o = o0 + (unsigned)tid;
-    job.dst[o] = acc[0];
-    if (o < job.n_mirror) job.mirror_dst[o] = acc[0];  // the mirror is written here: no HBM-to-HBM copy follows
+    const CondStoreDst out = {job.dst, job.mirror_dst, job.n_mirror, job.out_scale, job.clipped};
+    cond_store_tile<OUT, 1, GC_RDEC_THREADS>(rdec_lds, acc, tn, o0, out);
 }
 
 int ring_decim_tile_outputs(int decimation, int n_taps, unsigned n_out, int want_groups)
@@ -122,12 +125,25 @@ int ring_decim_tile_outputs(int decimation, int n_taps, unsigned n_out, int want
     return tile;
 }
 
-hipError_t ring_decim_launch(int iq_format, hipStream_t st, const RingDecimJob& job, int tile)
+template <int FMT>
+static bool ring_decim_launch_fmt(int out_format, dim3 grid, size_t lds_bytes, hipStream_t st, const RingDecimJob& job, int tile, int rowlen)
+{
+    switch (out_format)
+        {
+        case GC_IQ_F32: hipLaunchKernelGGL((ring_decim_kernel<FMT, GC_IQ_F32>), grid, dim3(GC_RDEC_THREADS), lds_bytes, st, job, tile, rowlen); return true;
+        case GC_IQ_I16: hipLaunchKernelGGL((ring_decim_kernel<FMT, GC_IQ_I16>), grid, dim3(GC_RDEC_THREADS), lds_bytes, st, job, tile, rowlen); return true;
+        case GC_IQ_I8: hipLaunchKernelGGL((ring_decim_kernel<FMT, GC_IQ_I8>), grid, dim3(GC_RDEC_THREADS), lds_bytes, st, job, tile, rowlen); return true;
+        default: return false;
+        }
+}
+
+hipError_t ring_decim_launch(int iq_format, int out_format, hipStream_t st, const RingDecimJob& job, int tile)
 {
     if (job.n_out == 0) return hipSuccess;
     if (job.decimation < 1 || job.decimation > GC_COND_MAX_DECIMATION || job.n_taps < 1 || job.n_taps > GC_COND_MAX_TAPS ||
         (tile != 64 && tile != 128 && tile != 256) || job.src_cap == 0 || job.src == nullptr || job.taps == nullptr)
         return hipErrorInvalidValue;
+    if (out_format != GC_IQ_F32 && (job.clipped == nullptr || !(job.out_scale > 0.0f))) return hipErrorInvalidValue;
     const int rowlen = cond_fir_rowlen(job.decimation, job.n_taps, tile);
     const size_t lds_samples = (size_t)job.decimation * rowlen;
     // the longest window of the launch, clipped at sample 0, must not lap the source ring
@@ -136,12 +152,14 @@ hipError_t ring_decim_launch(int iq_format, hipStream_t st, const RingDecimJob& 
     if (lds_samples > GC_COND_LDS_SAMPLES || std::min(widest, last_in + 1) > job.src_cap) return hipErrorInvalidValue;
     const dim3 grid((job.n_out + (unsigned)tile - 1) / (unsigned)tile);
     const size_t lds_bytes = lds_samples * sizeof(float2);
+    bool ok = false;
     switch (iq_format)
         {
-        case GC_IQ_F32: hipLaunchKernelGGL((ring_decim_kernel<GC_IQ_F32>), grid, dim3(GC_RDEC_THREADS), lds_bytes, st, job, tile, rowlen); break;
-        case GC_IQ_I16: hipLaunchKernelGGL((ring_decim_kernel<GC_IQ_I16>), grid, dim3(GC_RDEC_THREADS), lds_bytes, st, job, tile, rowlen); break;
-        case GC_IQ_I8: hipLaunchKernelGGL((ring_decim_kernel<GC_IQ_I8>), grid, dim3(GC_RDEC_THREADS), lds_bytes, st, job, tile, rowlen); break;
+        case GC_IQ_F32: ok = ring_decim_launch_fmt<GC_IQ_F32>(out_format, grid, lds_bytes, st, job, tile, rowlen); break;
+        case GC_IQ_I16: ok = ring_decim_launch_fmt<GC_IQ_I16>(out_format, grid, lds_bytes, st, job, tile, rowlen); break;
+        case GC_IQ_I8: ok = ring_decim_launch_fmt<GC_IQ_I8>(out_format, grid, lds_bytes, st, job, tile, rowlen); break;
         default: return hipErrorInvalidValue;
         }
+    if (!ok) return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -209,12 +209,15 @@ API = {
     "gc_stream_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gc_stream_synchronize": (C.c_int, [_vp]),
     "gc_stream_read": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp]),
+    "gc_stream_accept_quantised_output": (C.c_int, [_vp]),
     "gc_conditioner_conf_size": (C.c_size_t, []),
     "gc_conditioner_create": (C.c_int, [_vp, C.POINTER(ConditionerConf), _fp, _vp, C.POINTER(_vp)]),
     "gc_conditioner_destroy": (C.c_int, [_vp]),
     "gc_conditioner_push": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gc_conditioner_push_pinned": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gc_conditioner_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "gc_conditioner_set_output_scale": (C.c_int, [_vp, C.c_float]),
+    "gc_conditioner_output_info": (C.c_int, [_vp, C.POINTER(C.c_int32), _fp, C.POINTER(C.c_uint64)]),
     "gc_fir_low_pass": (C.c_int, [C.c_double] * 4 + [_fp, C.c_int, C.POINTER(C.c_int)]),
     "gc_blanking_conf_size": (C.c_size_t, []),
     "gc_conditioner_set_pulse_blanking": (C.c_int, [_vp, C.POINTER(BlankingConf)]),
@@ -288,6 +291,8 @@ API = {
     "gc_ring_decimator_destroy": (C.c_int, [_vp]),
     "gc_ring_decimator_update": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gc_ring_decimator_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "gc_ring_decimator_set_output_scale": (C.c_int, [_vp, C.c_float]),
+    "gc_ring_decimator_output_info": (C.c_int, [_vp, C.POINTER(C.c_int32), _fp, C.POINTER(C.c_uint64)]),
     "gc_acq_resampler_plan": (C.c_int, [C.c_int64, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int64), _fp, C.c_int, C.POINTER(C.c_int),
         C.POINTER(C.c_uint32)]),
 }
@@ -561,6 +566,12 @@ class IqStream:
     def synchronize(self):
         _check(load_library().gc_stream_synchronize(self._h))
 
+    def accept_quantised_output(self):
+        """gc_stream_accept_quantised_output: opens this empty GC_IQ_I16 / GC_IQ_I8 ring as the output ring of a Conditioner or
+        RingDecimator (which refuse an integer ring otherwise).  Returns self."""
+        _check(load_library().gc_stream_accept_quantised_output(self._h))
+        return self
+
     def read(self, first_index, n):
         """gc_stream_read: the resident window [first_index, first_index + n) in the ring's format -- complex64 [n] or
         int16 / int8 [n, 2].  Synchronous; GC_ERR_STATE when the window is not resident."""
@@ -618,8 +629,9 @@ def chi2_upper_quantile(dof, pfa):
 
 class Conditioner:
     """gc_conditioner: raw samples of any gc_iq_format or gc_raw_real_format at fs_in are mixed down by translate_hz, filtered with
-    `taps` and decimated on the device into `out_ring` (an empty GC_IQ_F32 IqStream), which consumers then read at
-    fs_in / decimation.  The filter's group delay, (len(taps) - 1) / 2 input samples, is the caller's to account for."""
+    `taps` and decimated on the device into `out_ring` (an empty GC_IQ_F32 IqStream, or an integer one after accept_quantised_output()), which consumers then read at
+    fs_in / decimation.  A GC_IQ_I16 / GC_IQ_I8 ring receives each component scaled, clamped and rounded (set_output_scale,
+    output_info).  The filter's group delay, (len(taps) - 1) / 2 input samples, is the caller's to account for."""
     _REAL_DTYPES = {GC_RAW_REAL_F32: np.float32, GC_RAW_REAL_I16: np.int16, GC_RAW_REAL_I8: np.int8}
 
     def __init__(self, ctx, out_ring, fs_in, translate_hz, decimation, taps, in_format=GC_IQ_F32):
@@ -669,6 +681,17 @@ class Conditioner:
         _check(load_library().gc_conditioner_info(self._h, C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
 
+    def set_output_scale(self, scale):
+        """gc_conditioner_set_output_scale: the factor in front of the clamp of a GC_IQ_I16 / GC_IQ_I8 output ring (default 1; 127
+        is the reference's translating filter with cbyte output).  Only before the first push; GC_ERR_INVALID on a GC_IQ_F32 ring."""
+        _check(load_library().gc_conditioner_set_output_scale(self._h, float(scale)))
+
+    def output_info(self):
+        """gc_conditioner_output_info (synchronous): (output ring's format, scale, clipped components so far)."""
+        fmt, scale, n = C.c_int32(0), C.c_float(0.0), C.c_uint64(0)
+        _check(load_library().gc_conditioner_output_info(self._h, C.byref(fmt), C.byref(scale), C.byref(n)))
+        return int(fmt.value), float(scale.value), int(n.value)
+
     def set_pulse_blanking(self, pfa=0.04, length=32, segments_est=12500, segments_reset=5000000, threshold=None):
         """gc_conditioner_set_pulse_blanking (defaults: the reference adapter's): segments of `length` raw samples whose energy
         exceeds `threshold` times the estimated noise floor are zeroed before the mixer and the filter.  threshold None: the
@@ -700,7 +723,9 @@ class Conditioner:
 
 class RingDecimator:
     """gc_ring_decimator: y[m] = sum_k taps[k] x[m decimation - k] from the ring `src` (any format; pushed, or fed by a Conditioner)
-    into `out_ring` (an empty GC_IQ_F32 IqStream), on the device.  update() appends what the source's samples so far complete."""
+    into `out_ring` (an empty GC_IQ_F32 IqStream, or an integer one after accept_quantised_output(), which receives the
+    conditioner's quantisation), on the device.
+    update() appends what the source's samples so far complete."""
 
     def __init__(self, ctx, src, decimation, taps, out_ring):
         self._ctx = ctx
@@ -717,6 +742,16 @@ class RingDecimator:
         first, n_out = C.c_uint64(0), C.c_uint64(0)
         _check(load_library().gc_ring_decimator_update(self._h, C.byref(first), C.byref(n_out)))
         return int(first.value), int(n_out.value)
+
+    def set_output_scale(self, scale):
+        """gc_ring_decimator_set_output_scale: as Conditioner.set_output_scale; only before the first update."""
+        _check(load_library().gc_ring_decimator_set_output_scale(self._h, float(scale)))
+
+    def output_info(self):
+        """gc_ring_decimator_output_info (synchronous): (output ring's format, scale, clipped components so far)."""
+        fmt, scale, n = C.c_int32(0), C.c_float(0.0), C.c_uint64(0)
+        _check(load_library().gc_ring_decimator_output_info(self._h, C.byref(fmt), C.byref(scale), C.byref(n)))
+        return int(fmt.value), float(scale.value), int(n.value)
 
     def info(self):
         """(source head the newest update saw, output ring head)."""

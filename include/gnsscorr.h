@@ -204,7 +204,8 @@ gc_status gc_stream_read(gc_stream* s, uint64_t first_index, uint64_t n_samples,
 /*   phi(n) = ((n * inc) mod 2^64) >> 32, a fraction of a turn in units of 2^-32  */
 /*   inc    = round(translate_hz / fs_in * 2^64) mod 2^64   (IEEE double, ties to even) */
 /*                                                                            */
-/* into the output ring (GC_IQ_F32), which acquisition, tracking batches and     */
+/* into the output ring (GC_IQ_F32; or quantised into a GC_IQ_I16 / GC_IQ_I8    */
+/* ring, "Integer output rings" below), which acquisition, tracking batches and  */
 /* closed-loop engines read like any other ring, addressing it by absolute sample */
 /* number AT THE OUTPUT RATE fs_in / D.  Mix-then-filter, the same mathematics as  */
 /* GNU Radio's rotated-taps form.  The phase is a closed form of the sample number: */
@@ -230,7 +231,9 @@ typedef struct
 size_t gc_conditioner_conf_size(void);
 
 typedef struct gc_conditioner gc_conditioner;
-/* taps: n_taps real float32 (copied).  out_ring: an empty GC_IQ_F32 ring of the same context; the conditioner keeps a reference on
+/* taps: n_taps real float32 (copied).  out_ring: an empty GC_IQ_F32 ring of the same context, or an empty GC_IQ_I16 / GC_IQ_I8 ring opened with
+ * gc_stream_accept_quantised_output ("Integer output rings" below; any other integer ring is refused with GC_ERR_INVALID, as before
+ * integer output existed); the conditioner keeps a reference on
  * it (the ring handle may be destroyed first) and is its only producer from here on: gc_stream_push / gc_stream_push_pinned on the
  * ring return GC_ERR_STATE.  The configuration and the taps are checked before anything touches a device. */
 gc_status gc_conditioner_create(gc_ctx* ctx, const gc_conditioner_conf* conf, const float* taps, gc_stream* out_ring,
@@ -254,6 +257,44 @@ gc_status gc_conditioner_info(gc_conditioner* c, uint64_t* in_head, uint64_t* ou
  * scaled so that sum(h) = gain (the response at DC); computed in double, returned as float32.  *n_taps receives T; taps may be
  * NULL to ask for T alone; GC_ERR_INVALID when T > capacity. */
 gc_status gc_fir_low_pass(double gain, double fs, double cutoff_hz, double transition_hz, float* taps, int capacity, int* n_taps);
+
+/* Integer output rings: the reference's Freq_Xlating_Fir_Filter takes output_item_type cshort or cbyte next to gr_complex
+ * (float_to_short on each component; complex_float_to_complex_byte, i.e. volk_gnsssdr_32fc_convert_8ic: scale by 127, clamp, rintf),
+ * and Fir_Filter has cshort -> cshort and cbyte -> cbyte.  Here the format is the output ring's: the conditioner and the ring
+ * decimator (below) write a ring of any gc_iq_format, and the tracking batch, the closed-loop engine and acquisition read a
+ * GC_IQ_I16 / GC_IQ_I8 ring at 4 / 2 bytes per sample instead of 8.
+ *
+ * y[m] is the float32 output defined above: the same accumulation, the same bits.  Into a GC_IQ_I16 ring (MIN = -32768,
+ * MAX = 32767) or a GC_IQ_I8 ring (MIN = -128, MAX = 127) each component c of y[m] is stored as
+ *
+ *   v = c * scale                      one float32 product
+ *   v = MAX if v > MAX;  MIN if v < MIN;  unchanged otherwise
+ *   q = (intN) rintf(v)                round to nearest, ties to even
+ *   a NaN component stores 0
+ *
+ * -- clamp first, then round: the order of volk_gnsssdr_32fc_convert_8ic_generic and of VOLK's 32f_s32f_convert_16i.  scale = 1
+ * gives the reference's cshort output and Fir_Filter's cbyte output, scale = 127 Freq_Xlating_Fir_Filter's cbyte output.  scale
+ * is a finite float32 > 0 and defaults to 1.  A component counts as CLIPPED when v > MAX or v < MIN: strict comparisons, made before
+ * the rounding; a NaN is not clipped.  The library keeps a running count of clipped components per conditioner and per decimator;
+ * every output sample is counted once, the copy the kernel writes behind the ring (for windows that would wrap) is not counted
+ * again.  first_out, n_out, gc_conditioner_info, blanking and the real and 2-bit input formats behave as with a GC_IQ_F32 ring: all of
+ * them count samples.  gc_stream_read on the ring returns int16 / int8 (re, im) pairs, as for a pushed ring.  A GC_IQ_F32 ring has
+ * no scale: it holds y[m] itself, bit for bit what the library stored before integer rings existed.
+ *
+ * Quantising is lossy, so a ring takes it only when asked to: an integer ring is by default a ring for host pushes, and
+ * gc_conditioner_create / gc_ring_decimator_create go on refusing it (GC_ERR_INVALID) exactly as they did before integer output existed
+ * -- a float pipeline pointed at a cshort ring by mistake does not silently lose its precision.  gc_stream_accept_quantised_output
+ * opens an integer ring for such a producer. */
+/* Declares that the empty GC_IQ_I16 / GC_IQ_I8 ring `s` may become the output ring of a gc_conditioner or gc_ring_decimator.
+ * GC_ERR_INVALID for a GC_IQ_F32 ring (nothing is quantised into it); GC_ERR_STATE once samples have been pushed or a producer
+ * exists.  Touches no device.  The ring still takes host pushes until a producer is created on it. */
+gc_status gc_stream_accept_quantised_output(gc_stream* s);
+/* Only before the first push (GC_ERR_STATE afterwards).  GC_ERR_INVALID for a scale that is not finite and positive, and for a
+ * conditioner whose output ring is GC_IQ_F32.  The arguments are checked before anything touches a device. */
+gc_status gc_conditioner_set_output_scale(gc_conditioner* c, float scale);
+/* The output ring's gc_iq_format, the scale in use and the clipped components so far (any pointer may be NULL).  Synchronous: waits
+ * for the pushes so far and copies the counter back from the device.  A GC_IQ_F32 ring reports scale 1 and 0 clipped. */
+gc_status gc_conditioner_output_info(gc_conditioner* c, int32_t* out_format, float* scale, uint64_t* clipped_components);
 
 /* Real raw samples: one real channel sampled at an intermediate frequency, the other half of what the reference's
  * Freq_Xlating_Fir_Filter takes (freq_xlating_fir_filter.cc: input_item_type "float", "short", "byte" next to the complex types), and
@@ -739,14 +780,16 @@ gc_status gc_acq_peek(gc_acq* a, int what, int index, float* host_out);
 /*   y[m] = sum_{k=0}^{T-1} h[k] * x[mD - k]      x[n] = 0 for n < 0            */
 /*                                                                            */
 /* (plain cast, float32 products and sums in tap order: the conditioner's        */
-/* definition with translate_hz = 0, and its bits) is appended to a GC_IQ_F32   */
-/* ring.  Output m is source sample mD, delayed by the filter's (T - 1) / 2      */
+/* definition with translate_hz = 0, and its bits) is appended to a ring of any  */
+/* gc_iq_format: a GC_IQ_I16 / GC_IQ_I8 ring receives y[m] quantised as the       */
+/* conditioner's "Integer output rings" section states, by the same code.         */
+/* Output m is source sample mD, delayed by the filter's (T - 1) / 2              */
 /* source samples.  An output's bits are a function of the source samples alone: */
 /* never of the update, the tile or how the source was pushed.                  */
 /* ------------------------------------------------------------------------ */
 typedef struct gc_ring_decimator gc_ring_decimator;
 /* src_ring: a ring of the context in any format, empty or still holding sample 0 (GC_ERR_STATE otherwise).  out_ring: an empty
- * GC_IQ_F32 ring of the same context; the decimator is its only producer from here on (gc_stream_push* on it return GC_ERR_STATE).
+ * GC_IQ_F32 ring of the same context, or an empty integer ring opened with gc_stream_accept_quantised_output; the decimator is its only producer from here on (gc_stream_push* on it return GC_ERR_STATE).
  * decimation 1..64; taps: n_taps = 1..1024 real float32 (copied).  The decimator keeps a reference on both rings.  The arguments
  * are checked before anything touches a device (GC_ERR_INVALID). */
 gc_status gc_ring_decimator_create(gc_ctx* ctx, gc_stream* src_ring, uint32_t decimation, const float* taps, uint32_t n_taps,
@@ -761,6 +804,11 @@ gc_status gc_ring_decimator_destroy(gc_ring_decimator* d);
 gc_status gc_ring_decimator_update(gc_ring_decimator* d, uint64_t* first_out, uint64_t* n_out);
 /* The source head the newest successful update saw, and the output ring's head (any pointer may be NULL). */
 gc_status gc_ring_decimator_info(gc_ring_decimator* d, uint64_t* src_consumed, uint64_t* out_head);
+/* gc_conditioner_set_output_scale for the decimator: only before the first gc_ring_decimator_update (GC_ERR_STATE afterwards);
+ * GC_ERR_INVALID for a scale that is not finite and positive and for a GC_IQ_F32 output ring. */
+gc_status gc_ring_decimator_set_output_scale(gc_ring_decimator* d, float scale);
+/* gc_conditioner_output_info for the decimator (any pointer may be NULL; synchronous). */
+gc_status gc_ring_decimator_output_info(gc_ring_decimator* d, int32_t* out_format, float* scale, uint64_t* clipped_components);
 /* The reference's rule for the acquisition resampler of a signal whose optimal search rate is opt_acq_fs_hz
  * (GPS_L1_CA_OPT_ACQ_FS_HZ = 1 000 000 ...), restated on the host:
  *   decimation   = floor(fs_in / opt), stepped down while fs_in % decimation != 0
