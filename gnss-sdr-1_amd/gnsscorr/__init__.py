@@ -22,6 +22,7 @@ GC_MAX_TAPS = 8
 GC_IQ_F32, GC_IQ_I16, GC_IQ_I8 = range(3)
 # gc_raw_real_format: real raw samples, for Conditioner only (float32 / int16 / int8 one per sample; 2 bits, four samples per byte)
 GC_RAW_REAL_F32, GC_RAW_REAL_I16, GC_RAW_REAL_I8, GC_RAW_REAL_2BIT = range(16, 20)
+GC_RESAMP_DIRECT, GC_RESAMP_POLYPHASE = range(2)
 
 
 class GnsscorrError(RuntimeError):
@@ -171,6 +172,17 @@ class BlankingConf(C.Structure):
 assert C.sizeof(BlankingConf) == 24
 
 
+class ResamplerConf(C.Structure):
+    """gc_resampler_conf: the ring resampler's rates, mode and (polyphase mode) tap bank."""
+    _fields_ = [
+        ("fs_in", C.c_double), ("fs_out", C.c_double), ("mode", C.c_int32), ("phases", C.c_uint32), ("taps_per_phase", C.c_uint32),
+        ("reserved", C.c_uint32), ("bank", C.POINTER(C.c_float)),
+    ]
+
+
+assert C.sizeof(ResamplerConf) == 40
+
+
 # every symbol include/gnsscorr.h declares: name -> (restype, argtypes)
 _vp = C.c_void_p
 _fp = C.POINTER(C.c_float)
@@ -295,6 +307,12 @@ API = {
     "gc_ring_decimator_output_info": (C.c_int, [_vp, C.POINTER(C.c_int32), _fp, C.POINTER(C.c_uint64)]),
     "gc_acq_resampler_plan": (C.c_int, [C.c_int64, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_int64), _fp, C.c_int, C.POINTER(C.c_int),
         C.POINTER(C.c_uint32)]),
+    "gc_resampler_conf_size": (C.c_size_t, []),
+    "gc_ring_resampler_create": (C.c_int, [_vp, _vp, C.POINTER(ResamplerConf), _vp, C.POINTER(_vp)]),
+    "gc_ring_resampler_destroy": (C.c_int, [_vp]),
+    "gc_ring_resampler_update": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "gc_ring_resampler_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "gc_resampler_design": (C.c_int, [C.c_double, C.c_double, C.c_uint32, _fp, C.c_int, C.POINTER(C.c_int)]),
 }
 
 _lib = None
@@ -331,6 +349,9 @@ def load_library():
         if lib.gc_blanking_conf_size() != C.sizeof(BlankingConf):
             raise GnsscorrError(GC_ERR_INVALID, "gc_blanking_conf is %d bytes in the library, %d here -- rebuild with __graft_entry__.build()"
                 % (lib.gc_blanking_conf_size(), C.sizeof(BlankingConf)))
+        if lib.gc_resampler_conf_size() != C.sizeof(ResamplerConf):
+            raise GnsscorrError(GC_ERR_INVALID, "gc_resampler_conf is %d bytes in the library, %d here -- rebuild with __graft_entry__.build()"
+                % (lib.gc_resampler_conf_size(), C.sizeof(ResamplerConf)))
         _lib = lib
     return _lib
 
@@ -781,6 +802,67 @@ def acq_resampler_plan(fs_in, opt_acq_fs_hz):
     if n.value:
         _check(lib.gc_acq_resampler_plan(int(fs_in), int(opt_acq_fs_hz), C.byref(d), C.byref(rfs), _f32p(taps), n.value, C.byref(n), C.byref(lat)))
     return int(d.value), int(rfs.value), taps, int(lat.value)
+
+
+def resampler_design(fs_in, fs_out, phases):
+    """gc_resampler_design: the [phases, T] float32 bank of RingResampler's polyphase mode from the library's low-pass design --
+    prototype gc_fir_low_pass(phases, phases * fs_in, min(fs_in, fs_out) / 2.1, min(fs_in, fs_out) / 10), bank[p, k] = g[k * phases + p]."""
+    lib = load_library()
+    t = C.c_int(0)
+    _check(lib.gc_resampler_design(float(fs_in), float(fs_out), int(phases), None, 0, C.byref(t)))
+    bank = np.zeros((int(phases), t.value), np.float32)
+    _check(lib.gc_resampler_design(float(fs_in), float(fs_out), int(phases), _f32p(bank), bank.size, C.byref(t)))
+    return bank
+
+
+class RingResampler:
+    """gc_ring_resampler: the ring `out` derived on the device from the ring `src` (any format; pushed, or fed by a Conditioner or a
+    RingDecimator) at the rate ratio fs_in / fs_out.  mode "direct": the reference's Direct_Resampler, nearest earlier sample, bits
+    as they are; `out` is an empty IqStream of src's format.  mode "polyphase": y[m] = sum_k bank[p_m, k] x[n_m - k] with `bank` a
+    [P, T] float32 array (resampler_design makes one); `out` is an empty GC_IQ_F32 IqStream.  update() appends what the source's
+    samples so far complete."""
+    _MODES = {"direct": GC_RESAMP_DIRECT, "polyphase": GC_RESAMP_POLYPHASE, GC_RESAMP_DIRECT: GC_RESAMP_DIRECT, GC_RESAMP_POLYPHASE: GC_RESAMP_POLYPHASE}
+
+    def __init__(self, ctx, src, fs_in, fs_out, out, mode="direct", bank=None):
+        if mode not in self._MODES:
+            raise ValueError("mode is 'direct' or 'polyphase'")
+        self._ctx = ctx
+        self._src = src
+        self._ring = out
+        self.mode = self._MODES[mode]
+        self.bank = None
+        phases = taps = 0
+        if bank is not None:
+            self.bank = np.ascontiguousarray(bank, np.float32)
+            if self.bank.ndim != 2:
+                raise ValueError("bank is a [phases, taps per phase] array")
+            phases, taps = self.bank.shape
+        self.conf = ResamplerConf(float(fs_in), float(fs_out), self.mode, phases, taps, 0, None if self.bank is None else _f32p(self.bank))
+        self._h = _vp()
+        _check(load_library().gc_ring_resampler_create(ctx._h, src._h, C.byref(self.conf), out._h, C.byref(self._h)))
+
+    def update(self):
+        """Returns (number of the first new output, new outputs).  Asynchronous on the output ring's copy stream."""
+        first, n_out = C.c_uint64(0), C.c_uint64(0)
+        _check(load_library().gc_ring_resampler_update(self._h, C.byref(first), C.byref(n_out)))
+        return int(first.value), int(n_out.value)
+
+    def info(self):
+        """(source head the newest update saw, output ring head)."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        _check(load_library().gc_ring_resampler_info(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def close(self):
+        if self._h:
+            load_library().gc_ring_resampler_destroy(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class HipMulticorrelatorRealCodes:

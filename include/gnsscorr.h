@@ -823,6 +823,87 @@ gc_status gc_ring_decimator_output_info(gc_ring_decimator* d, int32_t* out_forma
 gc_status gc_acq_resampler_plan(int64_t fs_in, uint32_t opt_acq_fs_hz, uint32_t* decimation, int64_t* resampled_fs, float* taps,
     int capacity, int* n_taps, uint32_t* latency_samples);
 
+/* ------------------------------------------------------------------------ */
+/* Ring resampler: a ring derived ON THE DEVICE from another ring at an        */
+/* ARBITRARY rate ratio -- the third stage of the reference's signal           */
+/* conditioner (data_type_adapter -> input_filter -> resampler,                */
+/* Resampler.implementation=Direct_Resampler with sample_freq_in /             */
+/* sample_freq_out).  The source is a gc_stream ring in any format -- pushed   */
+/* from the host, or written by a gc_conditioner or gc_ring_decimator.  Which   */
+/* source sample an output is, is a closed form of the output's ABSOLUTE number:*/
+/* an output's bits never depend on the update, the tile or how the source was */
+/* pushed.  With M = 2^32:                                                     */
+/*                                                                            */
+/* GC_RESAMP_DIRECT: the reference's Direct_Resampler, nearest earlier sample,  */
+/* no filter (direct_resampler_conditioner_{cc,cs,cb}.cc); out[m] = x[n_m],     */
+/* bits as they are:                                                           */
+/*   fs_in > fs_out   step = floor(M fs_out / fs_in) (IEEE double, to uint32)   */
+/*                    n_m = ceil(m M / step)                                   */
+/*                    outputs for a source head H >= 1: floor((H-1) step / M)+1 */
+/*   fs_in < fs_out   step = floor(M fs_in / fs_out)                           */
+/*                    n_m = floor((m + 1) step / M)                            */
+/*                    outputs for a source head H: ceil(H M / step) - 1        */
+/*   fs_in == fs_out  the identity, n_m = m (the reference's cast of 2^32 to    */
+/*                    uint32 is undefined; on x86 it copies every sample)      */
+/* These are the picks of the reference's running 32-bit phase.  As there, step */
+/* is a floor and the realised rate is slightly below fs_out.  The output ring  */
+/* must have the source ring's gc_iq_format (nothing is converted or           */
+/* quantised: an integer ring needs no gc_stream_accept_quantised_output).     */
+/* 1/64 <= fs_in / fs_out <= 64.                                               */
+/*                                                                            */
+/* GC_RESAMP_POLYPHASE: band-limited, for the role of the reference's           */
+/* Mmse_Resampler (whose taps live in GNU Radio): NOT bit compatible with it.   */
+/*   INC   = round(fs_in / fs_out * M)   quotient in IEEE double, ties to even  */
+/*   pos_m = m INC      n_m = pos_m >> 32                                      */
+/*   p_m   = (pos_m & (M - 1)) >> (32 - log2 P)                                */
+/*   y[m]  = sum_{k=0}^{T-1} H[p_m][k] x[n_m - k]     x[n] = 0 for n < 0        */
+/*   outputs for a source head H: ceil(H M / INC)                              */
+/* (plain cast of integer sources, float32: H[p][0] x first, then one fmaf per  */
+/* tap in k order).  H: a bank of P phases x T real float32 taps, row p first;  */
+/* P a power of two in 1..256, T in 1..1024, P T <= 8192.                      */
+/* 1/8 <= fs_in / fs_out <= 64.  The output ring must be GC_IQ_F32: integer     */
+/* output through the conditioner's store epilogue is not implemented          */
+/* (GC_ERR_INVALID).  The filter's group delay stays in the observables, as     */
+/* with every other filter of the library.                                     */
+/* ------------------------------------------------------------------------ */
+enum { GC_RESAMP_DIRECT = 0, GC_RESAMP_POLYPHASE = 1 };
+typedef struct gc_resampler_conf
+{
+    double fs_in;            /* rate of the source ring */
+    double fs_out;           /* rate of the output ring */
+    int32_t mode;            /* GC_RESAMP_DIRECT or GC_RESAMP_POLYPHASE */
+    uint32_t phases;         /* GC_RESAMP_POLYPHASE: P */
+    uint32_t taps_per_phase; /* GC_RESAMP_POLYPHASE: T */
+    uint32_t reserved;       /* 0 */
+    const float* bank;       /* GC_RESAMP_POLYPHASE: P * T floats, bank[p * T + k] = H[p][k] (copied); ignored in direct mode */
+} gc_resampler_conf;
+size_t gc_resampler_conf_size(void);
+typedef struct gc_ring_resampler gc_ring_resampler;
+/* src_ring: a ring of the context in any format, empty or still holding sample 0 (GC_ERR_STATE otherwise).  out_ring: an empty ring
+ * of the same context -- of the source's format in direct mode, GC_IQ_F32 in polyphase mode; the resampler is its only producer from
+ * here on (gc_stream_push* on it return GC_ERR_STATE) until gc_ring_resampler_destroy.  The resampler keeps a reference on both
+ * rings.  The configuration is checked before anything touches a device (GC_ERR_INVALID). */
+gc_status gc_ring_resampler_create(gc_ctx* ctx, gc_stream* src_ring, const gc_resampler_conf* conf, gc_stream* out_ring, gc_ring_resampler** out);
+gc_status gc_ring_resampler_destroy(gc_ring_resampler* r);
+/* Appends every output the source's samples so far complete: afterwards the output ring's head is the count stated above for the
+ * source's head.  first_out / n_out (optional): the absolute number of the first new output and their count (0 when none is
+ * complete).  Asynchronous on the output ring's copy stream (gc_stream_synchronize waits for it); the launch waits for the newest
+ * source push, and no source push evicts what it reads.  GC_ERR_STATE, with nothing changed, when source sample n_{m0} (direct) or
+ * max(0, n_{m0} - (T - 1)) (polyphase), m0 = the output head, is no longer resident: the source ran more than its capacity ahead.
+ * More outputs than the output ring holds are appended in order, in several pieces.  One update runs at a time; the call may come
+ * from another thread than the source's pushes. */
+gc_status gc_ring_resampler_update(gc_ring_resampler* r, uint64_t* first_out, uint64_t* n_out);
+/* The source head the newest successful update saw, and the output ring's head (any pointer may be NULL). */
+gc_status gc_ring_resampler_info(gc_ring_resampler* r, uint64_t* src_consumed, uint64_t* out_head);
+/* A bank for GC_RESAMP_POLYPHASE from the library's own low-pass design:
+ *   g          = gc_fir_low_pass(gain = P, fs = P fs_in, cutoff = min(fs_in, fs_out) / 2.1, transition = min(fs_in, fs_out) / 10)
+ *   T          = ceil(len(g) / P), g padded with zeros to P T
+ *   bank[p][k] = g[k P + p]         written as bank[p * T + k]
+ * (the two constants are those of gc_acq_resampler_plan).  Every row sums to about 1.  The group delay is that of the prototype at
+ * P times the source rate, (len(g) - 1) / (2 P) source samples -- at most (P T - 1) / (2 P); it stays in the observables.  phases: a
+ * power of two in 1..256.  bank may be NULL to ask for T alone.  GC_ERR_INVALID when T > 1024 or P T > 8192, and when P T > capacity. */
+gc_status gc_resampler_design(double fs_in, double fs_out, uint32_t phases, float* bank, int capacity, int* taps_per_phase);
+
 #define GC_ABI_CHECK() \
     gc_abi_check(sizeof(gc_epoch_params), sizeof(gc_loop_conf), sizeof(gc_loop_record), sizeof(gc_loop_sync_conf), sizeof(gc_acq_conf), sizeof(gc_acq_result))
 
