@@ -49,6 +49,44 @@ TABLE = [
 ]
 
 
+# ---- the closed-loop matrix's engines (tests/closed_loop_matrix_cases.py, run by tests/test_closed_loop_matrix_gpu.py) at 256 CUs: one
+# started channel, workgroup size forced (1024 / 512 / 256) or the high-dynamics 256; headers 1024 / 512 / 256 bytes ----
+MIX4 = "1023/0/1,2046/0/1,1023/1/1,2046/1/1"  # the mixed engines' slots: 3 / 5 taps (1023 / 2046 code samples) x data / pilot, all started
+TABLE += [
+    # resident, 1023 samples, data: image 2110 floats = 8440 bytes
+    ("1,256,0,1024,0,1023,0", "1024 2110 1 9464"), ("1,256,0,512,0,1023,0", "512 2110 1 8952"), ("1,256,0,256,0,1023,0", "256 2110 1 8696"),
+    ("1,256,1,0,0,1023,0", "256 2110 1 8696"),
+    # resident, 1023 samples, pilot: (2046 + 64) * 2 = 4220 floats = 16880 bytes
+    ("1,256,0,1024,0,1023,1", "1024 4220 1 17904"), ("1,256,0,512,0,1023,1", "512 4220 1 17392"), ("1,256,0,256,0,1023,1", "256 4220 1 17136"),
+    ("1,256,1,0,0,1023,1", "256 4220 1 17136"),
+    # resident, 2046 samples, data: 4092 + 64 = 4156 floats = 16624 bytes
+    ("1,256,0,1024,0,2046,0", "1024 4156 1 17648"), ("1,256,0,512,0,2046,0", "512 4156 1 17136"), ("1,256,0,256,0,2046,0", "256 4156 1 16880"),
+    ("1,256,1,0,0,2046,0", "256 4156 1 16880"),
+    # resident, 2046 samples, pilot: 4156 * 2 = 8312 floats = 33248 bytes
+    ("1,256,0,1024,0,2046,1", "1024 8312 1 34272"), ("1,256,0,512,0,2046,1", "512 8312 1 33760"), ("1,256,0,256,0,2046,1", "256 8312 1 33504"),
+    ("1,256,1,0,0,2046,1", "256 8312 1 33504"),
+    # the large resident image, 8000 samples, pilot: (16000 + 64) * 2 = 32128 floats = 128512 bytes; 1024 + 128512 = 129536 <= 153600
+    ("1,256,0,1024,0,8000,1", "1024 32128 1 129536"), ("1,256,0,512,0,8000,1", "512 32128 1 129024"), ("1,256,0,256,0,8000,1", "256 32128 1 128768"),
+    ("1,256,1,0,0,8000,1", "256 32128 1 128768"),
+    # window, pilot: a plain engine sized for 12000 samples (whatever its replicas' length): (24000 + 64) * 2 = 48128 floats,
+    # 1024 + 192512 > 153600: window (12000 + 64) * 2 = 24128 floats = 96512 bytes
+    ("1,256,0,1024,0,12000,1", "1024 24128 0 97536"), ("1,256,0,512,0,12000,1", "512 24128 0 97024"), ("1,256,0,256,0,12000,1", "256 24128 0 96768"),
+    ("1,256,1,0,0,12000,1", "256 24128 0 96768"),
+    # window, data: 257 slots on 256 CUs, sized for 8100 samples: 16264 floats, 1024 + 65056 = 66080 > 65536: window 8164 floats = 32656 bytes
+    ("257,256,0,1024,0,8100,0", "1024 8164 0 33680"), ("257,256,0,512,0,8100,0", "512 8164 0 33168"), ("257,256,0,256,0,8100,0", "256 8164 0 32912"),
+    ("257,256,1,0,0,8100,0", "256 8164 0 32912"),
+    # mixed, resident: the largest need among the four started slots is the 2046-sample pilot's 8312 floats
+    ("4,256,0,1024,1,2046,0," + MIX4, "1024 8312 1 34272"), ("4,256,0,512,1,2046,0," + MIX4, "512 8312 1 33760"),
+    ("4,256,0,256,1,2046,0," + MIX4, "256 8312 1 33504"), ("4,256,1,0,1,2046,0," + MIX4, "256 8312 1 33504"),
+    # mixed, window: max_code_len 12000 does not count; the started 8000-sample pilot slot needs 32128 floats resident, 129536 > 65536 with
+    # 257 slots on 256 CUs: window (8000 + 64) * 2 = 16128 floats = 64512 bytes
+    ("257,256,0,1024,1,12000,0," + MIX4 + ",8000/1/1", "1024 16128 0 65536"), ("257,256,0,512,1,12000,0," + MIX4 + ",8000/1/1", "512 16128 0 65024"),
+    ("257,256,0,256,1,12000,0," + MIX4 + ",8000/1/1", "256 16128 0 64768"), ("257,256,1,0,1,12000,0," + MIX4 + ",8000/1/1", "256 16128 0 64768"),
+    # ... and without that slot the same engine stays on the resident image, whatever its max_code_len
+    ("257,256,0,1024,1,12000,0," + MIX4, "1024 8312 1 34272"),
+]
+
+
 @pytest.fixture(scope="module")
 def selftest(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("loop_plan") / "loop_plan_selftest")
@@ -64,3 +102,14 @@ def test_plan_equals_the_hand_worked_table(selftest):
     assert len(got) == len(TABLE)
     for (engine, want), line in zip(TABLE, got):
         assert line == want, "engine %s: plan %s, expected %s" % (engine, line, want)
+
+
+def test_the_closed_loop_matrix_runs_engines_of_the_table():
+    """Every engine shape tests/test_closed_loop_matrix_gpu.py launches (on a 256-CU GPU) has its hand-worked row above, and the
+    matrix intends that row's workgroup size and image mode."""
+    import closed_loop_matrix_cases as M
+    table = dict(TABLE)
+    for engine, (threads, resident) in M.all_plan_tuples(256).items():
+        assert engine in table, engine
+        got = table[engine].split()
+        assert (int(got[0]), int(got[2])) == (threads, resident), (engine, table[engine])
