@@ -174,4 +174,19 @@ public:
 };
 
 #endif  // GNSSCORR_WITH_GNSS_SDR
+
+#include "gnsscorr.h"
+#include <string>
+
+//! The item types of complex samples as the reference's adapters spell them, "gr_complex" | "cshort" | "cbyte", to gc_iq_format;
+//! false (and *format untouched) for anything else
+inline bool gnsscorr_iq_format(const std::string& item_type, int* format)
+{
+    if (item_type == "gr_complex") *format = GC_IQ_F32;
+    else if (item_type == "cshort") *format = GC_IQ_I16;
+    else if (item_type == "cbyte") *format = GC_IQ_I8;
+    else return false;
+    return true;
+}
+
 #endif  // GNSSCORR_GNSS_SDR_TYPES_H_

@@ -42,10 +42,7 @@ public:
         const std::string mode = configuration->property(role + ".resampler_mode", std::string("direct"));
         const int32_t phases = configuration->property(role + ".phases", static_cast<int32_t>(32));
         int format = GC_IQ_F32;
-        if (d_item_type == "gr_complex") format = GC_IQ_F32;
-        else if (d_item_type == "cshort") format = GC_IQ_I16;
-        else if (d_item_type == "cbyte") format = GC_IQ_I8;
-        else
+        if (!gnsscorr_iq_format(d_item_type, &format))
             {
                 d_status = GC_ERR_INVALID;
                 return;

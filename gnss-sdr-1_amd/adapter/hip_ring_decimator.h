@@ -41,10 +41,7 @@ public:
         : hip_ring_decimator(ctx, source, fs_in, opt_acq_fs_hz)
     {
         const std::string type = configuration->property(role + ".output_item_type", std::string("gr_complex"));
-        if (type == "gr_complex") d_out_format = GC_IQ_F32;
-        else if (type == "cshort") d_out_format = GC_IQ_I16;
-        else if (type == "cbyte") d_out_format = GC_IQ_I8;
-        else
+        if (!gnsscorr_iq_format(type, &d_out_format))
             {
                 d_status = GC_ERR_INVALID;
                 return;

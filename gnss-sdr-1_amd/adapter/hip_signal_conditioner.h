@@ -63,14 +63,11 @@ public:
         d_item_type = configuration->property(role + ".input_item_type", std::string("gr_complex"));
         const std::string filter_type = configuration->property(role + ".filter_type", std::string("bandpass"));
         int format = GC_IQ_F32;
-        if (d_item_type == "gr_complex") format = GC_IQ_F32;
-        else if (d_item_type == "cshort") format = GC_IQ_I16;
-        else if (d_item_type == "cbyte") format = GC_IQ_I8;
-        else if (d_item_type == "float") format = GC_RAW_REAL_F32;
+        if (d_item_type == "float") format = GC_RAW_REAL_F32;
         else if (d_item_type == "short") format = GC_RAW_REAL_I16;
         else if (d_item_type == "byte") format = GC_RAW_REAL_I8;
         else if (d_item_type == "2bit") format = GC_RAW_REAL_2BIT;
-        else
+        else if (!gnsscorr_iq_format(d_item_type, &format))
             {
                 d_status = GC_ERR_INVALID;
                 return;
@@ -81,10 +78,7 @@ public:
                 return;
             }
         d_out_item_type = configuration->property(role + ".output_item_type", std::string("gr_complex"));
-        if (d_out_item_type == "gr_complex") d_out_format = GC_IQ_F32;
-        else if (d_out_item_type == "cshort") d_out_format = GC_IQ_I16;
-        else if (d_out_item_type == "cbyte") d_out_format = GC_IQ_I8;
-        else
+        if (!gnsscorr_iq_format(d_out_item_type, &d_out_format))
             {
                 d_status = GC_ERR_INVALID;
                 return;

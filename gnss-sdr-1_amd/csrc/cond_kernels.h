@@ -2,8 +2,7 @@
 // from a ring of raw samples into a piece of an RF stream ring (gc_stream) and its mirror.
 #ifndef COND_KERNELS_H
 #define COND_KERNELS_H
-#include "gnsscorr.h"
-#include <hip/hip_runtime.h>
+#include "cond_store_epilogue.h"
 
 #define GC_COND_MAX_DECIMATION 64
 #define GC_COND_MAX_TAPS 1024
@@ -23,12 +22,8 @@ struct CondJob
     unsigned long long phase_inc;  // turns per input sample in units of 2^-64; 0 = no mixer
     unsigned long long first_out;  // absolute number m of the first output of the piece
     unsigned n_out;                // outputs in the piece
-    void* dst;                     // where output first_out goes (ring position first_out % capacity), in the ring's format: the
-                                   // host computes it with the ring's bytes per sample (8 / 4 / 2)
-    void* mirror_dst;              // the same position behind the ring
-    unsigned n_mirror;             // the first n_mirror outputs of the piece are stored to mirror_dst as well
-    float out_scale;               // GC_IQ_I16 / GC_IQ_I8 output rings: the factor in front of the clamp (cond_store_epilogue.h)
-    unsigned long long* clipped;   // GC_IQ_I16 / GC_IQ_I8 output rings: the conditioner's count of clipped components (HBM)
+    CondStoreDst out;              // where the piece goes: ring position first_out % capacity, its mirror, the scale and the
+                                   // conditioner's count of clipped components (gc_ring_stage_piece)
 };
 
 // Outputs per workgroup for a launch (a multiple of 64, at most 1024): as many as fit in GC_COND_LDS_SAMPLES, fewer when the

@@ -20,32 +20,7 @@
 #include "cond_kernels.h"
 #include "cond_fir_accum.h"
 #include "cond_store_epilogue.h"
-
-typedef float cond_f32x4 __attribute__((ext_vector_type(4)));
-typedef short cond_i16x8 __attribute__((ext_vector_type(8)));
-typedef signed char cond_i8x16 __attribute__((ext_vector_type(16)));
-
-// 16 bytes of raw samples
-template <int FMT>
-struct CondRaw;
-template <>
-struct CondRaw<GC_IQ_F32>
-{
-    typedef cond_f32x4 vec;
-    static constexpr int N = 2, ELEM = 8;
-};
-template <>
-struct CondRaw<GC_IQ_I16>
-{
-    typedef cond_i16x8 vec;
-    static constexpr int N = 4, ELEM = 4;
-};
-template <>
-struct CondRaw<GC_IQ_I8>
-{
-    typedef cond_i8x16 vec;
-    static constexpr int N = 8, ELEM = 2;
-};
+#include "ring_window.h"
 
 // real formats: BITS per sample, N = 128 / BITS samples in a vector of four dwords
 typedef unsigned cond_u32x4 __attribute__((ext_vector_type(4)));
@@ -104,8 +79,8 @@ template <int FMT, bool MIX>
 static __device__ __forceinline__ void cond_front_complex(const CondJob& job, float2* cond_lds, const long long a0, const int count, const int D,
     const int rowlen)
 {
-    typedef typename CondRaw<FMT>::vec vec;
-    constexpr int S = CondRaw<FMT>::N;
+    typedef typename RingRaw<FMT>::vec vec;
+    constexpr int S = RingRaw<FMT>::N;
     const int tid = threadIdx.x;
     // whole 16-byte vectors from the boundary below a0; those below sample 0 read as zeros
     const long long av = a0 & ~(long long)(S - 1);
@@ -120,7 +95,7 @@ static __device__ __forceinline__ void cond_front_complex(const CondJob& job, fl
                 {
                     unsigned pos = base + (unsigned)(nv - (long long)avp);  // count + S < raw_cap: at most one wrap
                     if (pos >= job.raw_cap) pos -= job.raw_cap;
-                    raw = *reinterpret_cast<const vec*>(static_cast<const char*>(job.raw) + (size_t)pos * CondRaw<FMT>::ELEM);
+                    raw = *reinterpret_cast<const vec*>(static_cast<const char*>(job.raw) + (size_t)pos * RingRaw<FMT>::ELEM);
                 }
 #pragma unroll
             for (int e = 0; e < S; e++)
@@ -243,8 +218,7 @@ __global__ __launch_bounds__(GC_COND_THREADS) void cond_fir_decim_kernel(const C
     for (int r = 0; r < R; r++) j[r] = min(tid + r * GC_COND_THREADS, tn - 1);
     float2 acc[R];
     cond_fir_accumulate<R>(cond_lds, rowlen, D, T, job.taps, j, acc);
-    const CondStoreDst out = {job.dst, job.mirror_dst, job.n_mirror, job.out_scale, job.clipped};
-    cond_store_tile<OUT, R, GC_COND_THREADS>(cond_lds, acc, tn, o0, out);
+    cond_store_tile<OUT, R, GC_COND_THREADS>(cond_lds, acc, tn, o0, job.out);
 }
 
 static int cond_rowlen(int decimation, int n_taps, int tile) { return cond_fir_rowlen(decimation, n_taps, tile); }
@@ -327,7 +301,7 @@ hipError_t cond_launch(int iq_format, int out_format, hipStream_t st, const Cond
     if (job.decimation < 1 || job.decimation > GC_COND_MAX_DECIMATION || job.n_taps < 1 || job.n_taps > GC_COND_MAX_TAPS || tile < 64 ||
         tile > 4 * GC_COND_THREADS || align == 0 || job.raw_cap % align != 0)
         return hipErrorInvalidValue;
-    if (out_format != GC_IQ_F32 && (job.clipped == nullptr || !(job.out_scale > 0.0f))) return hipErrorInvalidValue;
+    if (out_format != GC_IQ_F32 && (job.out.clipped == nullptr || !(job.out.scale > 0.0f))) return hipErrorInvalidValue;
     const int rowlen = cond_rowlen(job.decimation, job.n_taps, tile);
     const size_t lds_samples = (size_t)job.decimation * rowlen;
     // a tile's inputs (plus one vector of slack on each side) must fit in the raw ring without lapping it

@@ -1,4 +1,5 @@
-// cond_store_epilogue.h -- the store epilogue every FIR decimator of the library shares (cond_kernels.hip, ring_decim_kernels.hip):
+// cond_store_epilogue.h -- the store epilogue every FIR decimator of the library shares (cond_kernels.hip, ring_decim_kernels.hip),
+// and the description of a piece of the output ring that every stage's job carries (the ring resampler's too):
 // a tile's accumulated outputs go to a piece of the output ring and, for the first n_mirror outputs of the piece, to the same
 // place behind the ring.  OUT is the ring's gc_iq_format.
 //
@@ -25,7 +26,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// where a tile's outputs go
+// where a piece of outputs that is contiguous in the output ring goes: embedded in every stage's job, filled by the host's
+// gc_ring_stage_piece (gc_ring_stage.h)
 struct CondStoreDst
 {
     void* dst;                    // where output 0 of the piece goes, in the ring's format

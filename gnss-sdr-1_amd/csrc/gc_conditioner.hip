@@ -14,10 +14,12 @@
 // ring for the next push, in front of the T - 1 samples of history.
 //
 // The output ring may have any gc_iq_format.  The kernel's store epilogue (cond_store_epilogue.h) scales, clamps and rounds into a
-// GC_IQ_I16 / GC_IQ_I8 ring and counts the clipped components in d_clipped; a GC_IQ_F32 ring has neither a scale nor a counter.
+// GC_IQ_I16 / GC_IQ_I8 ring and counts the clipped components; a GC_IQ_F32 ring has neither a scale nor a counter.  The claim on
+// the output ring, the geometry of a piece and that output state are shared with the derived rings (gc_ring_stage.h); the
+// filter design and the blanker's quantile are host numerics (gc_numerics.cpp).
 #include "cond_blank_kernels.h"
 #include "cond_kernels.h"
-#include "gc_stream.h"
+#include "gc_ring_stage.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -45,8 +47,7 @@ struct gc_conditioner
     unsigned char* d_blank_flags = nullptr;
     uint64_t blank_max_seg = 0;             // segments one chunk can complete
     // GC_IQ_I16 / GC_IQ_I8 output rings (gc_conditioner_set_output_scale, gc_conditioner_output_info)
-    float out_scale = 1.0f;
-    unsigned long long* d_clipped = nullptr;  // clipped components so far; nullptr for a GC_IQ_F32 ring
+    gc_quantised_output quant;
     // pinned staging for pageable caller buffers (as in gc_stream)
     static const int kSlots = 2;
     char* h_slot[kSlots] = {nullptr, nullptr};
@@ -79,11 +80,7 @@ struct cond_writer : gc_ring_writer
         job.phase_inc = c->phase_inc;
         job.first_out = idx;
         job.n_out = (unsigned)*len;
-        job.dst = s->d_ring + pos * s->elem;
-        job.mirror_dst = s->d_ring + (s->capacity + pos) * s->elem;
-        job.n_mirror = pos < s->mirror ? (unsigned)std::min<uint64_t>(*len, s->mirror - pos) : 0u;
-        job.out_scale = c->out_scale;
-        job.clipped = c->d_clipped;
+        job.out = gc_ring_stage_piece(s, pos, *len, c->quant.scale, c->quant.d_clipped);
         const int tile = cond_tile_outputs(job.decimation, job.n_taps, job.n_out, 2 * std::max(1, c->ctx->n_cus));
         GC_HIP(cond_launch(c->conf.in_format, s->iq_format, s->copy_stream, job, tile));
         return GC_OK;
@@ -143,24 +140,16 @@ gc_status cond_check_blanking(const gc_blanking_conf* b)
 
 void cond_release(gc_conditioner* c)
 {
-    if (c->out)
-        {
-            (void)hipStreamSynchronize(c->out->copy_stream);
-            {
-                std::lock_guard<std::mutex> lk(c->out->mtx);
-                c->out->kernel_fed = false;
-            }
-        }
+    if (c->out) gc_ring_stage_release(c->out);  // waits for the kernels that read what is freed below
     (void)hipFree(c->d_raw);
     (void)hipFree(c->d_taps);
-    (void)hipFree(c->d_clipped);
+    gc_quantised_output_free(&c->quant);
     cond_blank_free(c);
     for (int i = 0; i < gc_conditioner::kSlots; i++)
         {
             if (c->h_slot[i]) (void)hipHostFree(c->h_slot[i]);
             if (c->slot_done[i]) (void)hipEventDestroy(c->slot_done[i]);
         }
-    if (c->out) gc_stream_drop(c->out);
 }
 
 gc_status cond_push(gc_conditioner* c, const void* host_raw, uint64_t n_in, uint64_t* first_out, uint64_t* n_out, bool pinned)
@@ -254,13 +243,9 @@ gc_status gc_conditioner_create(gc_ctx* ctx, const gc_conditioner_conf* conf, co
     GC_REQUIRE(out_ring->iq_format == GC_IQ_F32 || out_ring->quantised_output,
         "gc_conditioner_create: the output ring must be GC_IQ_F32, or an integer ring opened with gc_stream_accept_quantised_output");
     gc_device_guard g(ctx->device);
-    {
-        std::lock_guard<std::mutex> no_push(out_ring->push_mtx);
-        std::lock_guard<std::mutex> lk(out_ring->mtx);
-        if (out_ring->kernel_fed) return gc_fail(GC_ERR_STATE, "gc_conditioner_create: the ring already has a conditioner");
-        if (out_ring->head != 0) return gc_fail(GC_ERR_STATE, "gc_conditioner_create: samples have been pushed into the ring already");
-        out_ring->kernel_fed = true;
-    }
+    const unsigned why = gc_ring_stage_claim(out_ring);
+    if (why & GC_RING_HAS_PRODUCER) return gc_fail(GC_ERR_STATE, "gc_conditioner_create: the ring already has a conditioner");
+    if (why) return gc_fail(GC_ERR_STATE, "gc_conditioner_create: samples have been pushed into the ring already");
     gc_conditioner* c = new gc_conditioner();
     c->ctx = ctx;
     c->ctx_ref.bind(ctx);
@@ -282,8 +267,7 @@ gc_status gc_conditioner_create(gc_ctx* ctx, const gc_conditioner_conf* conf, co
     if (e == hipSuccess) e = hipMemset(c->d_raw, 0, raw_bytes(c, c->raw_cap));
     if (e == hipSuccess) e = hipMalloc(&c->d_taps, sizeof(float) * conf->n_taps);
     if (e == hipSuccess) e = hipMemcpy(c->d_taps, taps, sizeof(float) * conf->n_taps, hipMemcpyHostToDevice);
-    if (e == hipSuccess && out_ring->iq_format != GC_IQ_F32) e = hipMalloc(&c->d_clipped, sizeof(unsigned long long));
-    if (e == hipSuccess && c->d_clipped) e = hipMemset(c->d_clipped, 0, sizeof(unsigned long long));
+    if (e == hipSuccess) e = gc_quantised_output_alloc(&c->quant, out_ring);
     for (int i = 0; i < gc_conditioner::kSlots && e == hipSuccess; i++)
         {
             e = hipHostMalloc(reinterpret_cast<void**>(&c->h_slot[i]), slot_bytes, hipHostMallocDefault);
@@ -330,13 +314,11 @@ gc_status gc_conditioner_info(gc_conditioner* c, uint64_t* in_head, uint64_t* ou
 
 gc_status gc_conditioner_set_output_scale(gc_conditioner* c, float scale)
 {
-    // the arguments first, before anything that needs a device
-    GC_REQUIRE(std::isfinite(scale) && scale > 0.0f, "gc_conditioner_set_output_scale: scale %g is not finite and positive", (double)scale);
-    GC_REQUIRE(c, "gc_conditioner_set_output_scale: NULL handle");
-    GC_REQUIRE(c->out->iq_format != GC_IQ_F32, "gc_conditioner_set_output_scale: a GC_IQ_F32 output ring has no scale");
+    const gc_status st = gc_quantised_output_check_scale("gc_conditioner_set_output_scale", scale, c ? c->out : nullptr);
+    if (st != GC_OK) return st;
     std::lock_guard<std::mutex> one_push(c->mtx);
     if (c->in_head != 0) return gc_fail(GC_ERR_STATE, "gc_conditioner_set_output_scale: samples have been pushed already");
-    c->out_scale = scale;
+    c->quant.scale = scale;
     return GC_OK;
 }
 
@@ -344,17 +326,7 @@ gc_status gc_conditioner_output_info(gc_conditioner* c, int32_t* out_format, flo
 {
     GC_REQUIRE(c, "gc_conditioner_output_info: NULL handle");
     std::lock_guard<std::mutex> one_push(c->mtx);
-    unsigned long long n = 0;
-    if (c->d_clipped && clipped_components)
-        {
-            gc_device_guard g(c->ctx->device);
-            GC_HIP(hipStreamSynchronize(c->out->copy_stream));
-            GC_HIP(hipMemcpy(&n, c->d_clipped, sizeof n, hipMemcpyDeviceToHost));
-        }
-    if (out_format) *out_format = c->out->iq_format;
-    if (scale) *scale = c->d_clipped ? c->out_scale : 1.0f;
-    if (clipped_components) *clipped_components = n;
-    return GC_OK;
+    return gc_quantised_output_info(&c->quant, c->ctx, c->out, out_format, scale, clipped_components);
 }
 
 size_t gc_blanking_conf_size(void) { return sizeof(gc_blanking_conf); }
@@ -415,101 +387,6 @@ gc_status gc_conditioner_blanking_info(gc_conditioner* c, uint64_t* segments_dec
     if (noise_power) *noise_power = st.noise;
     if (n_segments) *n_segments = st.n;
     if (threshold) *threshold = c->blank_params.threshold;
-    return GC_OK;
-}
-
-namespace
-{
-// log of the gamma function's regularised incomplete pair: P by its series (x < a + 1), Q by Lentz's continued fraction otherwise
-double chi2_gamma_q(double a, double x)
-{
-    if (x <= 0.0) return 1.0;
-    const double lead = std::exp(a * std::log(x) - x - std::lgamma(a));
-    if (x < a + 1.0)
-        {
-            double term = 1.0 / a, sum = term;
-            for (int k = 1; k < 1000000; k++)
-                {
-                    term *= x / (a + k);
-                    sum += term;
-                    if (term < sum * 1e-17) break;
-                }
-            return 1.0 - lead * sum;
-        }
-    const double tiny = 1e-300;
-    double b = x + 1.0 - a, cc = 1.0 / tiny, d = 1.0 / b, h = d;
-    for (int k = 1; k < 1000000; k++)
-        {
-            const double an = -(double)k * ((double)k - a);
-            b += 2.0;
-            d = an * d + b;
-            if (std::fabs(d) < tiny) d = tiny;
-            cc = b + an / cc;
-            if (std::fabs(cc) < tiny) cc = tiny;
-            d = 1.0 / d;
-            const double del = d * cc;
-            h *= del;
-            if (std::fabs(del - 1.0) < 1e-16) break;
-        }
-    return lead * h;
-}
-}  // namespace
-
-gc_status gc_chi2_upper_quantile(double dof, double pfa, double* out)
-{
-    if (out) *out = 0.0;
-    GC_REQUIRE(out, "gc_chi2_upper_quantile: NULL result");
-    GC_REQUIRE(dof > 0.0 && std::isfinite(dof), "gc_chi2_upper_quantile: dof %g is not positive", dof);
-    GC_REQUIRE(pfa > 0.0 && pfa < 1.0, "gc_chi2_upper_quantile: pfa %g is outside (0, 1)", pfa);
-    // Q(a, x) = pfa for x = q / 2, a = dof / 2: Newton steps on Q (dQ/dx = -x^(a-1) e^-x / Gamma(a)) kept inside a bracket that
-    // every evaluation tightens, bisection whenever a step leaves it
-    const double a = 0.5 * dof;
-    double lo = 0.0, hi = a + 1.0;
-    while (chi2_gamma_q(a, hi) > pfa) hi *= 2.0;
-    double x = 0.5 * (lo + hi);
-    for (int it = 0; it < 300; it++)
-        {
-            const double f = chi2_gamma_q(a, x) - pfa;
-            if (f > 0.0)
-                lo = x;
-            else
-                hi = x;
-            const double pdf = std::exp((a - 1.0) * std::log(x) - x - std::lgamma(a));
-            double xn = x + f / pdf;
-            if (!(xn > lo && xn < hi)) xn = 0.5 * (lo + hi);
-            const bool done = std::fabs(xn - x) <= 2e-16 * x || hi - lo <= 2e-16 * hi;
-            x = xn;
-            if (done) break;
-        }
-    *out = 2.0 * x;
-    return GC_OK;
-}
-
-gc_status gc_fir_low_pass(double gain, double fs, double cutoff_hz, double transition_hz, float* taps, int capacity, int* n_taps)
-{
-    if (n_taps) *n_taps = 0;
-    GC_REQUIRE(fs > 0.0 && cutoff_hz > 0.0 && cutoff_hz <= 0.5 * fs && transition_hz > 0.0 && std::isfinite(gain) && std::isfinite(fs),
-        "gc_fir_low_pass: need fs > 0, 0 < cutoff_hz <= fs / 2 and transition_hz > 0");
-    // Hamming window: 53 dB of stop-band attenuation, length 53 fs / (22 transition), made odd
-    const double want = 53.0 * fs / (22.0 * transition_hz);
-    GC_REQUIRE(want < 1.0e6, "gc_fir_low_pass: the transition width asks for %.0f taps", want);
-    int n = (int)want;
-    if ((n & 1) == 0) n++;
-    if (n_taps) *n_taps = n;
-    if (!taps) return GC_OK;  // length query
-    GC_REQUIRE(n <= capacity, "gc_fir_low_pass: %d taps do not fit in %d", n, capacity);
-    const int M = (n - 1) / 2;
-    const double pi = 3.14159265358979323846, w0 = 2.0 * pi * cutoff_hz / fs;
-    std::vector<double> h((size_t)n);
-    double sum = 0.0;
-    for (int i = 0; i < n; i++)
-        {
-            const int k = i - M;
-            const double win = n > 1 ? 0.54 - 0.46 * std::cos(2.0 * pi * i / (n - 1)) : 1.0;
-            h[i] = (k == 0 ? w0 / pi : std::sin(k * w0) / (k * pi)) * win;
-            sum += h[i];
-        }
-    for (int i = 0; i < n; i++) taps[i] = (float)(gain * h[i] / sum);
     return GC_OK;
 }
 

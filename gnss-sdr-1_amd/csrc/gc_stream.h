@@ -43,7 +43,8 @@ struct gc_stream
     std::mutex push_mtx;  // one push at a time (a push may release mtx while it waits for readers)
     std::atomic<int> refs{1};  // the creator's reference + one per batch channel that reads the ring
     bool quantised_output = false;  // gc_stream_accept_quantised_output: a conditioner / ring decimator may quantise into this integer ring
-    bool kernel_fed = false;   // a kernel writes the ring (gc_conditioner.hip, gc_ring_decimator.hip): gc_stream_push is refused
+    bool kernel_fed = false;   // a stage on the device -- conditioner, ring decimator or ring resampler -- writes the ring: gc_stream_push is
+                               // refused.  Set by gc_ring_stage_claim alone, cleared by gc_ring_stage_release (gc_ring_stage.h)
 };
 
 // Who writes the samples of a push.  gc_stream_produce does the ring's bookkeeping -- one push at a time, the wait for launches that

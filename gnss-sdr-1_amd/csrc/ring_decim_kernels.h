@@ -18,11 +18,8 @@ struct RingDecimJob
     int decimation;
     unsigned long long first_out;  // absolute number m of the first output of the piece
     unsigned n_out;                // outputs in the piece
-    void* dst;                     // where output first_out goes (ring position first_out % capacity), in the ring's format
-    void* mirror_dst;              // the same position behind the ring
-    unsigned n_mirror;             // the first n_mirror outputs of the piece are stored to mirror_dst as well
-    float out_scale;               // GC_IQ_I16 / GC_IQ_I8 output rings: the factor in front of the clamp (cond_store_epilogue.h)
-    unsigned long long* clipped;   // GC_IQ_I16 / GC_IQ_I8 output rings: the decimator's count of clipped components (HBM)
+    CondStoreDst out;              // where the piece goes: ring position first_out % capacity, its mirror, the scale and the
+                                   // decimator's count of clipped components (gc_ring_stage_piece)
 };
 
 // Outputs per workgroup (64, 128 or 256): the largest that fits in GC_COND_LDS_SAMPLES and still gives `want_groups` workgroups.

@@ -5,83 +5,27 @@
 //   y[m] = sum_{k=0}^{T-1} h[k] * x[mD - k]        x[n] = 0 for n < 0, plain cast, float32 products and sums, k ascending
 //
 // One workgroup produces a tile of outputs.  Its input window [m0 D - (T - 1), (m0 + tile - 1) D] is, apart from the zeros in front
-// of sample 0, at most two contiguous pieces of the source ring: the split is found once per tile (one modulo, uniform), and each
-// piece is loaded with 16-byte loads from its first 16-byte boundary on, with single-sample loads for the < 16 bytes at either
-// ragged end -- the ring's capacity need not be a multiple of anything, and nothing past the ring's end (its mirror) is read.
+// of sample 0, at most two contiguous pieces of the source ring: ring_window.h's loader finds the split once per tile and reads
+// nothing past the ring's end (its mirror), whatever the ring's capacity.
 // Samples go to LDS in the conditioner's polyphase order, are accumulated by the conditioner's code (cond_fir_accum.h) and stored by
 // its epilogue (cond_store_epilogue.h; OUT is the output ring's format), so an output's bits are a function of the source samples alone.
 #include "ring_decim_kernels.h"
 #include "cond_fir_accum.h"
 #include "cond_store_epilogue.h"
+#include "ring_window.h"
 #include <algorithm>
 
-typedef float rdec_f32x4 __attribute__((ext_vector_type(4)));
-typedef short rdec_i16x8 __attribute__((ext_vector_type(8)));
-typedef signed char rdec_i8x16 __attribute__((ext_vector_type(16)));
-typedef float rdec_f32x2 __attribute__((ext_vector_type(2)));
-typedef short rdec_i16x2 __attribute__((ext_vector_type(2)));
-typedef signed char rdec_i8x2 __attribute__((ext_vector_type(2)));
-
-// 16 bytes of source samples, and one sample
-template <int FMT>
-struct RdecRaw;
-template <>
-struct RdecRaw<GC_IQ_F32>
-{
-    typedef rdec_f32x4 vec;
-    typedef rdec_f32x2 one;
-    static constexpr int N = 2, ELEM = 8;
-};
-template <>
-struct RdecRaw<GC_IQ_I16>
-{
-    typedef rdec_i16x8 vec;
-    typedef rdec_i16x2 one;
-    static constexpr int N = 4, ELEM = 4;
-};
-template <>
-struct RdecRaw<GC_IQ_I8>
-{
-    typedef rdec_i8x16 vec;
-    typedef rdec_i8x2 one;
-    static constexpr int N = 8, ELEM = 2;
-};
-
 // input i of the tile to its polyphase place
-static __device__ __forceinline__ void rdec_put(float2* lds, int rowlen, unsigned D, int i, float2 x)
+struct RdecPolyphasePut
 {
-    const unsigned row = (unsigned)i % D, col = (unsigned)i / D;
-    lds[row * (unsigned)rowlen + col] = x;
-}
-
-// n samples that are contiguous in the ring from position pos become inputs i0 .. i0 + n - 1 of the tile
-template <int FMT>
-static __device__ __forceinline__ void rdec_load_piece(float2* lds, int rowlen, unsigned D, const char* ring, unsigned pos, int i0, int n)
-{
-    typedef typename RdecRaw<FMT>::vec vec;
-    typedef typename RdecRaw<FMT>::one one;
-    constexpr int S = RdecRaw<FMT>::N, ELEM = RdecRaw<FMT>::ELEM;
-    const int tid = threadIdx.x;
-    if (n <= 0) return;
-    const int head = min((int)((0u - pos) & (unsigned)(S - 1)), n);  // samples in front of the first 16-byte boundary
-    const int n_vec = (n - head) / S;
-    const int tail0 = head + n_vec * S;
-    const vec* vp = reinterpret_cast<const vec*>(ring + (size_t)(pos + (unsigned)head) * ELEM);
-    for (int v = tid; v < n_vec; v += GC_RDEC_THREADS)
-        {
-            const vec raw = vp[v];
-            const int i = i0 + head + v * S;
-#pragma unroll
-            for (int e = 0; e < S; e++) rdec_put(lds, rowlen, D, i + e, float2{(float)raw[2 * e], (float)raw[2 * e + 1]});
-        }
-    const int n_ragged = head + (n - tail0);  // < 2 S <= 16
-    if (tid < n_ragged)
-        {
-            const int k = tid < head ? tid : tail0 + (tid - head);
-            const one raw = *reinterpret_cast<const one*>(ring + (size_t)(pos + (unsigned)k) * ELEM);
-            rdec_put(lds, rowlen, D, i0 + k, float2{(float)raw[0], (float)raw[1]});
-        }
-}
+    float2* lds;
+    unsigned rowlen, D;
+    __device__ __forceinline__ void operator()(int i, float2 x) const
+    {
+        const unsigned row = (unsigned)i % D, col = (unsigned)i / D;
+        lds[row * rowlen + col] = x;
+    }
+};
 
 template <int FMT, int OUT>
 __global__ __launch_bounds__(GC_RDEC_THREADS) void ring_decim_kernel(const RingDecimJob job, const int tile, const int rowlen)
@@ -93,16 +37,7 @@ __global__ __launch_bounds__(GC_RDEC_THREADS) void ring_decim_kernel(const RingD
     const int tn = (int)min((unsigned)tile, job.n_out - o0);
     const long long a0 = (long long)(job.first_out + o0) * D - (T - 1);  // absolute number of the tile's first input (< 0: zeros)
     const int count = (tn - 1) * D + T;
-    const int n_zero = a0 < 0 ? (int)min((long long)count, -a0) : 0;
-    for (int i = tid; i < n_zero; i += GC_RDEC_THREADS) rdec_put(rdec_lds, rowlen, (unsigned)D, i, float2{0.0f, 0.0f});
-    // the split: [lo, lo + n) is resident (n <= src_cap), so it wraps at most once
-    const unsigned long long lo = a0 < 0 ? 0ull : (unsigned long long)a0;
-    const int n = count - n_zero;
-    const unsigned pos = (unsigned)(lo % job.src_cap);
-    const int n1 = (int)min((unsigned)n, job.src_cap - pos);
-    const char* ring = static_cast<const char*>(job.src);
-    rdec_load_piece<FMT>(rdec_lds, rowlen, (unsigned)D, ring, pos, n_zero, n1);
-    rdec_load_piece<FMT>(rdec_lds, rowlen, (unsigned)D, ring, 0u, n_zero + n1, n - n1);
+    ring_window_load<FMT, GC_RDEC_THREADS>(job.src, job.src_cap, a0, count, RdecPolyphasePut{rdec_lds, (unsigned)rowlen, (unsigned)D});
     __syncthreads();
     // the integer epilogues hold barriers: there the lanes past the end of a short tile stay, read the last output's samples and
     // store nothing
@@ -112,8 +47,7 @@ __global__ __launch_bounds__(GC_RDEC_THREADS) void ring_decim_kernel(const RingD
     int j[1] = {min(tid, tn - 1)};
     float2 acc[1];
     cond_fir_accumulate<1>(rdec_lds, rowlen, D, T, job.taps, j, acc);
-    const CondStoreDst out = {job.dst, job.mirror_dst, job.n_mirror, job.out_scale, job.clipped};
-    cond_store_tile<OUT, 1, GC_RDEC_THREADS>(rdec_lds, acc, tn, o0, out);
+    cond_store_tile<OUT, 1, GC_RDEC_THREADS>(rdec_lds, acc, tn, o0, job.out);
 }
 
 int ring_decim_tile_outputs(int decimation, int n_taps, unsigned n_out, int want_groups)
@@ -143,7 +77,7 @@ hipError_t ring_decim_launch(int iq_format, int out_format, hipStream_t st, cons
     if (job.decimation < 1 || job.decimation > GC_COND_MAX_DECIMATION || job.n_taps < 1 || job.n_taps > GC_COND_MAX_TAPS ||
         (tile != 64 && tile != 128 && tile != 256) || job.src_cap == 0 || job.src == nullptr || job.taps == nullptr)
         return hipErrorInvalidValue;
-    if (out_format != GC_IQ_F32 && (job.clipped == nullptr || !(job.out_scale > 0.0f))) return hipErrorInvalidValue;
+    if (out_format != GC_IQ_F32 && (job.out.clipped == nullptr || !(job.out.scale > 0.0f))) return hipErrorInvalidValue;
     const int rowlen = cond_fir_rowlen(job.decimation, job.n_taps, tile);
     const size_t lds_samples = (size_t)job.decimation * rowlen;
     // the longest window of the launch, clipped at sample 0, must not lap the source ring

@@ -3,15 +3,16 @@
 // Direct_Resampler); polyphase mode filters with one of P tap rows per output.  The index arithmetic is resamp_index.h's.
 #ifndef RING_RESAMP_KERNELS_H
 #define RING_RESAMP_KERNELS_H
-#include "gnsscorr.h"
+#include "cond_store_epilogue.h"
 #include "resamp_index.h"
-#include <hip/hip_runtime.h>
 
 #define GC_RRES_THREADS 256
 #define GC_RRES_MAX_PHASES 256
 #define GC_RRES_MAX_TAPS 1024
 #define GC_RRES_MAX_BANK 8192        // phases * taps per phase: 32 KiB of LDS
 #define GC_RRES_LDS_BYTES 65536      // source window + tap bank of one workgroup
+
+static inline bool ring_resamp_power_of_two(uint32_t v) { return v != 0 && (v & (v - 1)) == 0; }
 
 // One piece of outputs that is contiguous in the output ring.
 struct RingResampJob
@@ -22,9 +23,8 @@ struct RingResampJob
     unsigned long long step;   // step of the direct kinds, INC of RESAMP_POLY
     unsigned long long q0, r0; // resamp_base() of the piece's first output
     unsigned n_out;            // outputs in the piece
-    void* dst;                 // where the piece's first output goes, in the output ring's format
-    void* mirror_dst;          // the same position behind the ring
-    unsigned n_mirror;         // the first n_mirror outputs of the piece are stored to mirror_dst as well
+    CondStoreDst out;          // where the piece goes, in the output ring's format, and its mirror (gc_ring_stage_piece); neither
+                               // kernel scales or counts
     // RESAMP_POLY
     const float* bank;         // phases rows of ring_resamp_bank_pitch(taps) floats (HBM): row p holds H[p][0 .. taps - 1]
     int log2_phases;

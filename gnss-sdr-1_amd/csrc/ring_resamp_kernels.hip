@@ -7,53 +7,18 @@
 //              64-bit modulo, uniform, and each lane adds its distance from it and folds once.
 //   polyphase  y[m] = sum_{k=0}^{T-1} H[p_m][k] x[n_m - k],  x[n] = 0 for n < 0, plain cast, H[p][0] x first and then one fmaf per
 //              tap in k order.  The tile's source window [n_first - (T - 1), n_last] is, apart from the zeros in front of sample
-//              0, at most two contiguous pieces of the ring: each is loaded with 16-byte loads from its first 16-byte boundary
-//              on and single-sample loads at either ragged end, as the ring decimator does, so nothing behind the ring's end is
-//              read and any capacity works.  Window (float2) and bank (odd row pitch) lie in LDS; after one barrier lane j
+//              0, at most two contiguous pieces of the ring: ring_window.h's loader, which the ring decimator shares, reads
+//              nothing behind the ring's end, so any capacity works.  Window (float2) and bank (odd row pitch) lie in LDS; after one barrier lane j
 //              accumulates output j with its own phase row.  An output's bits are a function of its T source samples and its tap
 //              row alone.
 #include "ring_resamp_kernels.h"
+#include "ring_window.h"
 #include <algorithm>
-
-typedef float rres_f32x4 __attribute__((ext_vector_type(4)));
-typedef short rres_i16x8 __attribute__((ext_vector_type(8)));
-typedef signed char rres_i8x16 __attribute__((ext_vector_type(16)));
-typedef float rres_f32x2 __attribute__((ext_vector_type(2)));
-typedef short rres_i16x2 __attribute__((ext_vector_type(2)));
-typedef signed char rres_i8x2 __attribute__((ext_vector_type(2)));
-
-// 16 bytes of source samples, one sample, and one sample as bits
-template <int FMT>
-struct RresRaw;
-template <>
-struct RresRaw<GC_IQ_F32>
-{
-    typedef rres_f32x4 vec;
-    typedef rres_f32x2 one;
-    typedef uint2 bits;
-    static constexpr int N = 2, ELEM = 8;
-};
-template <>
-struct RresRaw<GC_IQ_I16>
-{
-    typedef rres_i16x8 vec;
-    typedef rres_i16x2 one;
-    typedef unsigned bits;
-    static constexpr int N = 4, ELEM = 4;
-};
-template <>
-struct RresRaw<GC_IQ_I8>
-{
-    typedef rres_i8x16 vec;
-    typedef rres_i8x2 one;
-    typedef unsigned short bits;
-    static constexpr int N = 8, ELEM = 2;
-};
 
 template <int FMT>
 __global__ __launch_bounds__(GC_RRES_THREADS) void ring_resamp_direct_kernel(const RingResampJob job)
 {
-    typedef typename RresRaw<FMT>::bits bits;
+    typedef typename RingRaw<FMT>::bits bits;
     const unsigned o0 = blockIdx.x * (unsigned)GC_RRES_THREADS;  // first output of the tile, counted in the piece
     const unsigned j = o0 + threadIdx.x;
     // the wrap split: once per tile
@@ -65,38 +30,16 @@ __global__ __launch_bounds__(GC_RRES_THREADS) void ring_resamp_direct_kernel(con
     unsigned pos = pos_tile + (unsigned)(n - n_tile);
     if (pos >= job.src_cap) pos -= job.src_cap;
     const bits v = static_cast<const bits*>(job.src)[pos];
-    static_cast<bits*>(job.dst)[j] = v;
-    if (j < job.n_mirror) static_cast<bits*>(job.mirror_dst)[j] = v;
+    static_cast<bits*>(job.out.dst)[j] = v;
+    if (j < job.out.n_mirror) static_cast<bits*>(job.out.mirror_dst)[j] = v;
 }
 
-// n samples that are contiguous in the ring from position pos become entries i0 .. i0 + n - 1 of the window
-template <int FMT>
-static __device__ __forceinline__ void rres_load_piece(float2* win, const char* ring, unsigned pos, int i0, int n)
+// entry i of the window to its place: the window is flat
+struct RresLinearPut
 {
-    typedef typename RresRaw<FMT>::vec vec;
-    typedef typename RresRaw<FMT>::one one;
-    constexpr int S = RresRaw<FMT>::N, ELEM = RresRaw<FMT>::ELEM;
-    const int tid = threadIdx.x;
-    if (n <= 0) return;
-    const int head = min((int)((0u - pos) & (unsigned)(S - 1)), n);  // samples in front of the first 16-byte boundary
-    const int n_vec = (n - head) / S;
-    const int tail0 = head + n_vec * S;
-    const vec* vp = reinterpret_cast<const vec*>(ring + (size_t)(pos + (unsigned)head) * ELEM);
-    for (int v = tid; v < n_vec; v += GC_RRES_THREADS)
-        {
-            const vec raw = vp[v];
-            float2* w = win + i0 + head + v * S;
-#pragma unroll
-            for (int e = 0; e < S; e++) w[e] = float2{(float)raw[2 * e], (float)raw[2 * e + 1]};
-        }
-    const int n_ragged = head + (n - tail0);  // < 2 S <= 16
-    if (tid < n_ragged)
-        {
-            const int k = tid < head ? tid : tail0 + (tid - head);
-            const one raw = *reinterpret_cast<const one*>(ring + (size_t)(pos + (unsigned)k) * ELEM);
-            win[i0 + k] = float2{(float)raw[0], (float)raw[1]};
-        }
-}
+    float2* win;
+    __device__ __forceinline__ void operator()(int i, float2 x) const { win[i] = x; }
+};
 
 // the accumulation of cond_fir_accum.h with a tap row per lane: h[0] x first, then one fmaf per tap in the order k = 1 .. T-1.
 // x points at the window entry of source sample n_m; tap k reads the entry k in front of it.
@@ -130,16 +73,7 @@ __global__ __launch_bounds__(GC_RRES_THREADS) void ring_resamp_poly_kernel(const
     const unsigned long long n_last = resamp_offset_index(RESAMP_POLY, job.step, job.q0, job.r0, o0 + (unsigned)(tn - 1));
     const long long a0 = (long long)n_first - (T - 1);  // absolute number of the window's first entry (< 0: zeros)
     const int count = (int)(n_last - n_first) + T;       // <= win_cap (ring_resamp_window)
-    const int n_zero = a0 < 0 ? (int)min((long long)count, -a0) : 0;
-    for (int i = tid; i < n_zero; i += GC_RRES_THREADS) win[i] = float2{0.0f, 0.0f};
-    // the split: [lo, lo + n) is resident (n <= src_cap), so it wraps at most once
-    const unsigned long long lo = a0 < 0 ? 0ull : (unsigned long long)a0;
-    const int n = count - n_zero;
-    const unsigned pos = (unsigned)(lo % job.src_cap);
-    const int n1 = (int)min((unsigned)n, job.src_cap - pos);
-    const char* ring = static_cast<const char*>(job.src);
-    rres_load_piece<FMT>(win, ring, pos, n_zero, n1);
-    rres_load_piece<FMT>(win, ring, 0u, n_zero + n1, n - n1);
+    ring_window_load<FMT, GC_RRES_THREADS>(job.src, job.src_cap, a0, count, RresLinearPut{win});
     const int n_bank = pitch << job.log2_phases;
     for (int i = tid; i < n_bank; i += GC_RRES_THREADS) bank[i] = job.bank[i];
     __syncthreads();
@@ -149,8 +83,8 @@ __global__ __launch_bounds__(GC_RRES_THREADS) void ring_resamp_poly_kernel(const
     const unsigned long long nm = resamp_offset_index(RESAMP_POLY, job.step, job.q0, job.r0, j);
     const unsigned p = resamp_offset_phase(job.step, job.log2_phases, job.r0, j);
     const float2 y = rres_accumulate(win + (int)(nm - n_first) + (T - 1), bank + p * (unsigned)pitch, T);
-    static_cast<float2*>(job.dst)[j] = y;
-    if (j < job.n_mirror) static_cast<float2*>(job.mirror_dst)[j] = y;
+    static_cast<float2*>(job.out.dst)[j] = y;
+    if (j < job.out.n_mirror) static_cast<float2*>(job.out.mirror_dst)[j] = y;
 }
 
 static size_t rres_lds_bytes(unsigned long long inc, int taps, int phases, int tile)
@@ -181,8 +115,8 @@ static bool rres_span(const RingResampJob& job, unsigned long long* span)
 hipError_t ring_resamp_direct_launch(int iq_format, hipStream_t st, const RingResampJob& job)
 {
     if (job.n_out == 0) return hipSuccess;
-    if (job.kind < RESAMP_IDENTITY || job.kind > RESAMP_UP || job.src_cap == 0 || job.src == nullptr || job.dst == nullptr ||
-        (job.n_mirror > 0 && job.mirror_dst == nullptr) || job.n_mirror > job.n_out)
+    if (job.kind < RESAMP_IDENTITY || job.kind > RESAMP_UP || job.src_cap == 0 || job.src == nullptr || job.out.dst == nullptr ||
+        (job.out.n_mirror > 0 && job.out.mirror_dst == nullptr) || job.out.n_mirror > job.n_out)
         return hipErrorInvalidValue;
     // what the piece reads, [n_first, n_last], must not lap the source ring
     unsigned long long span = 0;
@@ -204,7 +138,7 @@ hipError_t ring_resamp_poly_launch(int iq_format, hipStream_t st, const RingResa
     const int phases = 1 << job.log2_phases;
     if (job.kind != RESAMP_POLY || job.log2_phases < 0 || phases > GC_RRES_MAX_PHASES || job.taps < 1 || job.taps > GC_RRES_MAX_TAPS ||
         phases * job.taps > GC_RRES_MAX_BANK || tile < 16 || tile > GC_RRES_THREADS || (tile & (tile - 1)) != 0 || job.src_cap == 0 || job.src == nullptr ||
-        job.bank == nullptr || job.dst == nullptr || (job.n_mirror > 0 && job.mirror_dst == nullptr) || job.n_mirror > job.n_out)
+        job.bank == nullptr || job.out.dst == nullptr || (job.out.n_mirror > 0 && job.out.mirror_dst == nullptr) || job.out.n_mirror > job.n_out)
         return hipErrorInvalidValue;
     const size_t lds_bytes = rres_lds_bytes(job.step, job.taps, phases, tile);
     if (lds_bytes > GC_RRES_LDS_BYTES) return hipErrorInvalidValue;

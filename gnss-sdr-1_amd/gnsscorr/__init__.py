@@ -648,11 +648,54 @@ def chi2_upper_quantile(dof, pfa):
     return float(out.value)
 
 
-class Conditioner:
+class _RingStage:
+    """Handle of a stage that writes a ring on the device (Conditioner, RingDecimator, RingResampler): the calls that differ between
+    the stages in the C prefix alone.  A subclass names its prefix in _C and sets self._h."""
+    _C = None
+
+    def _call(self, name, *args):
+        _check(getattr(load_library(), "%s_%s" % (self._C, name))(self._h, *args))
+
+    def _pair(self, name):
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        self._call(name, C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
+    def info(self):
+        """(source head the newest update saw, output ring head)."""
+        return self._pair("info")
+
+    def _output_info(self):
+        fmt, scale, n = C.c_int32(0), C.c_float(0.0), C.c_uint64(0)
+        self._call("output_info", C.byref(fmt), C.byref(scale), C.byref(n))
+        return int(fmt.value), float(scale.value), int(n.value)
+
+    def close(self):
+        if self._h:
+            getattr(load_library(), self._C + "_destroy")(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _DerivedRing(_RingStage):
+    """A stage whose input is another ring: update() appends what the source's samples so far complete."""
+
+    def update(self):
+        """Returns (number of the first new output, new outputs).  Asynchronous on the output ring's copy stream."""
+        return self._pair("update")
+
+
+class Conditioner(_RingStage):
     """gc_conditioner: raw samples of any gc_iq_format or gc_raw_real_format at fs_in are mixed down by translate_hz, filtered with
     `taps` and decimated on the device into `out_ring` (an empty GC_IQ_F32 IqStream, or an integer one after accept_quantised_output()), which consumers then read at
     fs_in / decimation.  A GC_IQ_I16 / GC_IQ_I8 ring receives each component scaled, clamped and rounded (set_output_scale,
     output_info).  The filter's group delay, (len(taps) - 1) / 2 input samples, is the caller's to account for."""
+    _C = "gc_conditioner"
     _REAL_DTYPES = {GC_RAW_REAL_F32: np.float32, GC_RAW_REAL_I16: np.int16, GC_RAW_REAL_I8: np.int8}
 
     def __init__(self, ctx, out_ring, fs_in, translate_hz, decimation, taps, in_format=GC_IQ_F32):
@@ -698,9 +741,7 @@ class Conditioner:
 
     def info(self):
         """(raw samples pushed, output ring head)."""
-        a, b = C.c_uint64(0), C.c_uint64(0)
-        _check(load_library().gc_conditioner_info(self._h, C.byref(a), C.byref(b)))
-        return int(a.value), int(b.value)
+        return self._pair("info")
 
     def set_output_scale(self, scale):
         """gc_conditioner_set_output_scale: the factor in front of the clamp of a GC_IQ_I16 / GC_IQ_I8 output ring (default 1; 127
@@ -709,9 +750,7 @@ class Conditioner:
 
     def output_info(self):
         """gc_conditioner_output_info (synchronous): (output ring's format, scale, clipped components so far)."""
-        fmt, scale, n = C.c_int32(0), C.c_float(0.0), C.c_uint64(0)
-        _check(load_library().gc_conditioner_output_info(self._h, C.byref(fmt), C.byref(scale), C.byref(n)))
-        return int(fmt.value), float(scale.value), int(n.value)
+        return self._output_info()
 
     def set_pulse_blanking(self, pfa=0.04, length=32, segments_est=12500, segments_reset=5000000, threshold=None):
         """gc_conditioner_set_pulse_blanking (defaults: the reference adapter's): segments of `length` raw samples whose energy
@@ -730,23 +769,13 @@ class Conditioner:
         return dict(segments_decided=int(d.value), segments_blanked=int(b.value), noise_power=float(noise.value), n_segments=int(n.value),
             threshold=float(thr.value))
 
-    def close(self):
-        if self._h:
-            load_library().gc_conditioner_destroy(self._h)
-            self._h = _vp()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class RingDecimator:
+class RingDecimator(_DerivedRing):
     """gc_ring_decimator: y[m] = sum_k taps[k] x[m decimation - k] from the ring `src` (any format; pushed, or fed by a Conditioner)
     into `out_ring` (an empty GC_IQ_F32 IqStream, or an integer one after accept_quantised_output(), which receives the
     conditioner's quantisation), on the device.
     update() appends what the source's samples so far complete."""
+    _C = "gc_ring_decimator"
 
     def __init__(self, ctx, src, decimation, taps, out_ring):
         self._ctx = ctx
@@ -758,38 +787,13 @@ class RingDecimator:
         _check(load_library().gc_ring_decimator_create(ctx._h, src._h, self.decimation, _f32p(self.taps), int(self.taps.size), out_ring._h,
             C.byref(self._h)))
 
-    def update(self):
-        """Returns (number of the first new output, new outputs).  Asynchronous on the output ring's copy stream."""
-        first, n_out = C.c_uint64(0), C.c_uint64(0)
-        _check(load_library().gc_ring_decimator_update(self._h, C.byref(first), C.byref(n_out)))
-        return int(first.value), int(n_out.value)
-
     def set_output_scale(self, scale):
         """gc_ring_decimator_set_output_scale: as Conditioner.set_output_scale; only before the first update."""
         _check(load_library().gc_ring_decimator_set_output_scale(self._h, float(scale)))
 
     def output_info(self):
         """gc_ring_decimator_output_info (synchronous): (output ring's format, scale, clipped components so far)."""
-        fmt, scale, n = C.c_int32(0), C.c_float(0.0), C.c_uint64(0)
-        _check(load_library().gc_ring_decimator_output_info(self._h, C.byref(fmt), C.byref(scale), C.byref(n)))
-        return int(fmt.value), float(scale.value), int(n.value)
-
-    def info(self):
-        """(source head the newest update saw, output ring head)."""
-        a, b = C.c_uint64(0), C.c_uint64(0)
-        _check(load_library().gc_ring_decimator_info(self._h, C.byref(a), C.byref(b)))
-        return int(a.value), int(b.value)
-
-    def close(self):
-        if self._h:
-            load_library().gc_ring_decimator_destroy(self._h)
-            self._h = _vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._output_info()
 
 
 def acq_resampler_plan(fs_in, opt_acq_fs_hz):
@@ -815,12 +819,13 @@ def resampler_design(fs_in, fs_out, phases):
     return bank
 
 
-class RingResampler:
+class RingResampler(_DerivedRing):
     """gc_ring_resampler: the ring `out` derived on the device from the ring `src` (any format; pushed, or fed by a Conditioner or a
     RingDecimator) at the rate ratio fs_in / fs_out.  mode "direct": the reference's Direct_Resampler, nearest earlier sample, bits
     as they are; `out` is an empty IqStream of src's format.  mode "polyphase": y[m] = sum_k bank[p_m, k] x[n_m - k] with `bank` a
     [P, T] float32 array (resampler_design makes one); `out` is an empty GC_IQ_F32 IqStream.  update() appends what the source's
     samples so far complete."""
+    _C = "gc_ring_resampler"
     _MODES = {"direct": GC_RESAMP_DIRECT, "polyphase": GC_RESAMP_POLYPHASE, GC_RESAMP_DIRECT: GC_RESAMP_DIRECT, GC_RESAMP_POLYPHASE: GC_RESAMP_POLYPHASE}
 
     def __init__(self, ctx, src, fs_in, fs_out, out, mode="direct", bank=None):
@@ -840,29 +845,6 @@ class RingResampler:
         self.conf = ResamplerConf(float(fs_in), float(fs_out), self.mode, phases, taps, 0, None if self.bank is None else _f32p(self.bank))
         self._h = _vp()
         _check(load_library().gc_ring_resampler_create(ctx._h, src._h, C.byref(self.conf), out._h, C.byref(self._h)))
-
-    def update(self):
-        """Returns (number of the first new output, new outputs).  Asynchronous on the output ring's copy stream."""
-        first, n_out = C.c_uint64(0), C.c_uint64(0)
-        _check(load_library().gc_ring_resampler_update(self._h, C.byref(first), C.byref(n_out)))
-        return int(first.value), int(n_out.value)
-
-    def info(self):
-        """(source head the newest update saw, output ring head)."""
-        a, b = C.c_uint64(0), C.c_uint64(0)
-        _check(load_library().gc_ring_resampler_info(self._h, C.byref(a), C.byref(b)))
-        return int(a.value), int(b.value)
-
-    def close(self):
-        if self._h:
-            load_library().gc_ring_resampler_destroy(self._h)
-            self._h = _vp()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class HipMulticorrelatorRealCodes:
