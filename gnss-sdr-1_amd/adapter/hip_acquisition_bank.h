@@ -16,6 +16,10 @@
  * engine and replicas at that rate, and scales delay and sample stamp back to the ring's rate as pcps_acquisition.cc:756-762 does.
  * Everything the caller sees stays at the ring's rate; tracking stays on `ring`.  When the plan's decimation is 1 the flag does
  * nothing.  Deviation: the reference switches the resampler off for item types other than gr_complex; here every ring format works.
+ *
+ * cccwsr (Galileo E1 "1B" only): every satellite is searched on BOTH components the way pcps_cccwsr_acquisition_cc does (:316-370,
+ * data and pilot correlations combined as d + jp and d - jp, the larger wins) -- a paired MAX engine (gc_acq_create_paired) whose slots
+ * hold gc_cccwsr_replicas(E1-B, E1-C); statistic, threshold and result mapping stay those of the one-replica search.
  */
 #ifndef GNSSCORR_HIP_ACQUISITION_BANK_H_
 #define GNSSCORR_HIP_ACQUISITION_BANK_H_
@@ -35,7 +39,8 @@ public:
     /*! system / signal: 'G' "1C" | "L5", 'E' "1B" | "5X", 'C' "B1" | "B3"; prns: the satellites searched; fs_in: the ring's sampling rate;
      *  doppler_max / doppler_step [Hz]; threshold on the block's statistic (pcps_acquisition.cc:565-665); max_dwells non-coherent dwells */
     hip_acquisition_bank(gc_ctx* ctx, gc_stream* ring, char system, const std::string& signal, const std::vector<uint32_t>& prns, int64_t fs_in, uint32_t doppler_max,
-        uint32_t doppler_step, float threshold, uint32_t max_dwells = 1, bool use_cfar = true, int iq_format = GC_IQ_F32, bool use_acquisition_resampler = false)
+        uint32_t doppler_step, float threshold, uint32_t max_dwells = 1, bool use_cfar = true, int iq_format = GC_IQ_F32, bool use_acquisition_resampler = false,
+        bool cccwsr = false)
         : d_ring(ring), d_acq_ring(ring), d_system(system), d_signal(signal), d_prns(prns), d_threshold(threshold), d_max_dwells(std::max(1u, max_dwells))
     {
         double code_rate = 1.023e6, code_len = 1023.0;
@@ -88,7 +93,8 @@ public:
         c.doppler_step = doppler_step;
         c.max_dwells = d_max_dwells;
         c.use_CFAR_algorithm_flag = use_cfar ? 1 : 0;
-        d_status = gc_acq_create(ctx, &c, static_cast<int>(prns.size()), &d_acq);
+        cccwsr = cccwsr && system == 'E' && signal == "1B";
+        d_status = cccwsr ? gc_acq_create_paired(ctx, &c, static_cast<int>(prns.size()), GC_ACQ_COMBINE_MAX, &d_acq) : gc_acq_create(ctx, &c, static_cast<int>(prns.size()), &d_acq);
         if (d_status == GC_OK && iq_format != GC_IQ_F32) d_status = gc_acq_set_input_format(d_acq, iq_format);
         if (d_status != GC_OK) return;
         uint32_t fft = 0, consumed = 0, bins = 0;
@@ -103,6 +109,8 @@ public:
         d_samples_per_code = static_cast<uint32_t>(std::floor(static_cast<double>(fs_in) / (code_rate / code_len)));
         // replicas: one code period at fs, tiled over the coherent time (the adapters' set_local_code)
         std::vector<float> one(2 * (d_samples_per_code + 16)), tiled(2 * static_cast<size_t>(consumed));
+        std::vector<float> pilot, rep_a, rep_b;
+        if (cccwsr) pilot.resize(tiled.size()), rep_a.resize(tiled.size()), rep_b.resize(tiled.size());
         for (size_t s = 0; s < prns.size() && d_status == GC_OK; s++)
             {
                 const int32_t fs = static_cast<int32_t>(fs_in);
@@ -118,7 +126,20 @@ public:
                         tiled[2 * i] = one[2 * (i % d_samples_per_code)];
                         tiled[2 * i + 1] = one[2 * (i % d_samples_per_code) + 1];
                     }
-                d_status = gc_acq_set_local_code(d_acq, static_cast<int>(s), tiled.data());
+                if (!cccwsr)
+                    {
+                        d_status = gc_acq_set_local_code(d_acq, static_cast<int>(s), tiled.data());
+                        continue;
+                    }
+                d_status = gc_galileo_e1_code_gen_complex_sampled(one.data(), "1C", 0, prns[s], fs, 0, nullptr);
+                if (d_status != GC_OK) return;
+                for (size_t i = 0; i < consumed; i++)
+                    {
+                        pilot[2 * i] = one[2 * (i % d_samples_per_code)];
+                        pilot[2 * i + 1] = one[2 * (i % d_samples_per_code) + 1];
+                    }
+                d_status = gc_cccwsr_replicas(tiled.data(), pilot.data(), consumed, rep_a.data(), rep_b.data());
+                if (d_status == GC_OK) d_status = gc_acq_set_local_code_pair(d_acq, static_cast<int>(s), rep_a.data(), rep_b.data());
             }
         d_results.resize(prns.size());
         d_ready = (d_status == GC_OK);

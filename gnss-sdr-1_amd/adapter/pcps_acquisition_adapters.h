@@ -9,6 +9,8 @@
  *   BeidouB1iPcpsAcquisition          src/algorithms/acquisition/adapters/beidou_b1i_pcps_acquisition.cc:45-330
  *   GlonassL1CaPcpsAcquisition        src/algorithms/acquisition/adapters/glonass_l1_ca_pcps_acquisition.cc:44-330
  *   GpsL2MPcpsAcquisition, GpsL5iPcpsAcquisition, GalileoE5aPcpsAcquisition, BeidouB3iPcpsAcquisition (same directory)
+ *   GalileoE1PcpsCccwsrAmbiguousAcquisition, GalileoE1Pcps8msAmbiguousAcquisition (same directory): both E1 components, or both sign
+ *   hypotheses of an 8 ms replica, in one search -- backed by hip_pcps_paired_acquisition (at the end of this file)
  * (item_type gr_complex only; `dump` / `dump_filename` / `dump_channel` write the reference's .mat
  * variables, see hip_pcps_acquisition::dump_results; the acquisition resampler and the GNU Radio
  * connect()/get_left_block() plumbing are outside this path).  Registration in a GNSS-SDR tree is one
@@ -19,6 +21,7 @@
 #define GNSSCORR_PCPS_ACQUISITION_ADAPTERS_H_
 
 #include "hip_pcps_acquisition.h"
+#include "hip_pcps_paired_acquisition.h"
 #include <cmath>
 #include <memory>
 #include <string>
@@ -343,5 +346,152 @@ using GalileoE5aPcpsAcquisitionHip = PcpsAcquisitionHip<gnsscorr::AcqSignal::GAL
 using BeidouB3iPcpsAcquisitionHip = PcpsAcquisitionHip<gnsscorr::AcqSignal::BEIDOU_B3I>;
 //! the block applies the FDMA offset in set_local_code() once hip_pcps_acquisition::set_glonass_channel_map() holds the almanac
 using GlonassL1CaPcpsAcquisitionHip = PcpsAcquisitionHip<gnsscorr::AcqSignal::GLONASS_L1_CA>;
+
+
+/*! GalileoE1PcpsCccwsrAmbiguousAcquisition (galileo_e1_pcps_cccwsr_ambiguous_acquisition.cc:42-243) and
+ *  GalileoE1Pcps8msAmbiguousAcquisition (galileo_e1_pcps_8ms_ambiguous_acquisition.cc:41-263) over hip_pcps_paired_acquisition.
+ *  Keys of both: doppler_max, coherent_integration_time_ms (default 4; rounded down to a multiple of 4, :65-73 / :66-74),
+ *  max_dwells, Acquisition<ch>.cboc, dump, dump_filename; code_length = round(fs / (1.023e6 / 4092)), samples_per_ms = code_length / 4,
+ *  vector_length = code_length * (coherent_integration_time_ms / 4).  Threshold: the CCCWSR adapter installs the value it is given
+ *  (its Pfa rule is "not implemented", :237-243); the 8 ms adapter looks up <role><ch>.pfa, then <role>.pfa, and applies the
+ *  exponential-quantile rule (:136-160, :245-263).  The E1-B and E1-C replicas come from gc_galileo_e1_code_gen_complex_sampled;
+ *  the CCCWSR adapter of the reference generates ONE code period whatever the coherent time and hands the block a buffer it reads
+ *  vector_length samples of (:199-220) -- here the period is tiled over the coherent time, as its 8 ms sibling does (:224-228). */
+template <hip_pcps_paired_acquisition::Kind KIND>
+class GalileoE1PairedAcquisitionHip : public AcquisitionInterface
+{
+public:
+    GalileoE1PairedAcquisitionHip(ConfigurationInterface* configuration, const std::string& role, unsigned int in_streams, unsigned int out_streams)
+        : configuration_(configuration), role_(role), in_streams_(in_streams), out_streams_(out_streams)
+    {
+        item_type_ = configuration_->property(role + ".item_type", std::string("gr_complex"));
+        int64_t fs_in_deprecated = configuration_->property("GNSS-SDR.internal_fs_hz", static_cast<int64_t>(4000000));
+        fs_in_ = configuration_->property("GNSS-SDR.internal_fs_sps", fs_in_deprecated);
+        dump_ = configuration_->property(role + ".dump", false);
+        doppler_max_ = configuration_->property(role + ".doppler_max", 5000);
+        sampled_ms_ = configuration_->property(role + ".coherent_integration_time_ms", 4);
+        if (sampled_ms_ % 4 != 0) sampled_ms_ = static_cast<int>(sampled_ms_ / 4) * 4;
+        max_dwells_ = configuration_->property(role + ".max_dwells", 1);
+        dump_filename_ = configuration_->property(role + ".dump_filename", std::string("../data/acquisition.dat"));
+        code_length_ = static_cast<unsigned int>(std::round(static_cast<double>(fs_in_) / (1.023e6 / 4092.0)));
+        vector_length_ = code_length_ * static_cast<int>(sampled_ms_ / 4);
+        const int samples_per_ms = code_length_ / 4;
+        acquisition_ = std::make_shared<hip_pcps_paired_acquisition>(KIND, sampled_ms_, max_dwells_, doppler_max_, fs_in_, samples_per_ms, code_length_, dump_, dump_filename_);
+    }
+
+    std::string role() override { return role_; }
+    std::string implementation() override
+    {
+        return KIND == hip_pcps_paired_acquisition::CCCWSR ? "Galileo_E1_PCPS_CCCWSR_Ambiguous_Acquisition_HIP" : "Galileo_E1_PCPS_8ms_Ambiguous_Acquisition_HIP";
+    }
+    size_t item_size() override { return sizeof(gr_complex); }
+
+    void set_gnss_synchro(Gnss_Synchro* p_gnss_synchro) override
+    {
+        gnss_synchro_ = p_gnss_synchro;
+        acquisition_->set_gnss_synchro(gnss_synchro_);
+    }
+
+    void set_channel(unsigned int channel) override
+    {
+        channel_ = channel;
+        acquisition_->set_channel(channel_);
+    }
+
+    void set_channel_fsm(std::shared_ptr<ChannelFsm> channel_fsm) override { channel_fsm_ = channel_fsm; }
+
+    void set_threshold(float threshold) override
+    {
+        threshold_ = threshold;
+        if (KIND == hip_pcps_paired_acquisition::E1_8MS)
+            {
+                float pfa = configuration_->property(role_ + std::to_string(channel_) + ".pfa", 0.0f);
+                if (pfa == 0.0f) pfa = configuration_->property(role_ + ".pfa", 0.0f);
+                if (pfa != 0.0f) threshold_ = calculate_threshold(pfa);
+            }
+        acquisition_->set_threshold(threshold_);
+    }
+
+    void set_doppler_max(unsigned int doppler_max) override
+    {
+        doppler_max_ = doppler_max;
+        acquisition_->set_doppler_max(doppler_max_);
+    }
+
+    void set_doppler_step(unsigned int doppler_step) override
+    {
+        doppler_step_ = doppler_step;
+        acquisition_->set_doppler_step(doppler_step_);
+    }
+
+    void init() override { acquisition_->init(); }
+
+    void set_local_code() override
+    {
+        const bool cboc = configuration_->property("Acquisition" + std::to_string(channel_) + ".cboc", false);
+        const unsigned int reps = sampled_ms_ / 4;
+        std::vector<gr_complex> one(code_length_ + 8), data(vector_length_), pilot(vector_length_);
+        // without a synchro signal the data component is searched, as "1B" selects it in the reference's generator
+        const char* sig_8ms = (gnss_synchro_->Signal[0] == '1' && gnss_synchro_->Signal[1] == 'C') ? "1C" : "1B";
+        gc_galileo_e1_code_gen_complex_sampled(reinterpret_cast<float*>(one.data()), KIND == hip_pcps_paired_acquisition::CCCWSR ? "1B" : sig_8ms, cboc ? 1 : 0,
+            gnss_synchro_->PRN, static_cast<int32_t>(fs_in_), 0, nullptr);
+        for (unsigned int i = 0; i < reps; i++) std::memcpy(&data[i * code_length_], one.data(), sizeof(gr_complex) * code_length_);
+        if (KIND == hip_pcps_paired_acquisition::CCCWSR)
+            {
+                gc_galileo_e1_code_gen_complex_sampled(reinterpret_cast<float*>(one.data()), "1C", cboc ? 1 : 0, gnss_synchro_->PRN, static_cast<int32_t>(fs_in_), 0, nullptr);
+                for (unsigned int i = 0; i < reps; i++) std::memcpy(&pilot[i * code_length_], one.data(), sizeof(gr_complex) * code_length_);
+                acquisition_->set_local_code(data.data(), pilot.data());
+            }
+        else
+            acquisition_->set_local_code(data.data());
+    }
+
+    void set_state(int state) override { acquisition_->set_state(state); }
+    signed int mag() override { return acquisition_->mag(); }
+    void reset() override { acquisition_->set_active(true); }
+    void stop_acquisition() override {}
+    void set_resampler_latency(uint32_t) override {}
+
+    //! the block (get_left_block() is a stream_to_vector of vector_length() samples in front of it in the reference)
+    std::shared_ptr<hip_pcps_paired_acquisition> block() { return acquisition_; }
+    unsigned int vector_length() const { return vector_length_; }
+    float threshold() const { return threshold_; }
+
+private:
+    //! galileo_e1_pcps_8ms_ambiguous_acquisition.cc:245-263
+    float calculate_threshold(float pfa)
+    {
+        unsigned int frequency_bins = 0;
+        for (int doppler = static_cast<int>(-doppler_max_); doppler <= static_cast<int>(doppler_max_); doppler += doppler_step_) frequency_bins++;
+        unsigned int ncells = vector_length_ * frequency_bins;
+        double exponent = 1 / static_cast<double>(ncells);
+        double val = std::pow(1.0 - pfa, exponent);
+        auto lambda = double(vector_length_);
+        return static_cast<float>(-std::log(1.0 - val) / lambda);
+    }
+
+    ConfigurationInterface* configuration_;
+    std::shared_ptr<hip_pcps_paired_acquisition> acquisition_;
+    std::string item_type_;
+    std::string role_;
+    std::string dump_filename_;
+    unsigned int in_streams_;
+    unsigned int out_streams_;
+    unsigned int vector_length_ = 0;
+    unsigned int code_length_ = 0;
+    unsigned int channel_ = 0;
+    unsigned int doppler_max_ = 0;
+    unsigned int doppler_step_ = 0;
+    unsigned int sampled_ms_ = 4;
+    unsigned int max_dwells_ = 1;
+    bool dump_ = false;
+    float threshold_ = 0.0f;
+    int64_t fs_in_ = 0;
+    std::shared_ptr<ChannelFsm> channel_fsm_;
+    Gnss_Synchro* gnss_synchro_ = nullptr;
+};
+
+using GalileoE1PcpsCccwsrAmbiguousAcquisitionHip = GalileoE1PairedAcquisitionHip<hip_pcps_paired_acquisition::CCCWSR>;
+using GalileoE1Pcps8msAmbiguousAcquisitionHip = GalileoE1PairedAcquisitionHip<hip_pcps_paired_acquisition::E1_8MS>;
 
 #endif  // GNSSCORR_PCPS_ACQUISITION_ADAPTERS_H_

@@ -21,7 +21,14 @@ enum
     ACQ_EPI_MAG2 = 4,     // two dwells at once: Q holds [sat][2 * n_bins][N], the second n_bins being the next dwell; the grid gets
                           // |.|^2 of the first + |.|^2 of the second, written once
     ACQ_EPI_MAG2_ACC = 5, // the same on top of earlier dwells: (grid + first) + second
-    ACQ_EPI_MAG_ACC = 6   // grid += |.|^2: later dwells
+    ACQ_EPI_MAG_ACC = 6,  // grid += |.|^2: later dwells
+    // paired engine (gc_acq_create_paired): Q holds [sat][2][n_bins][N], the second n_bins being the SAME spectra against the satellite's
+    // second replica; with a = |.|^2 of the first and b = |.|^2 of the second the grid cell gets c = max(a, b) (PMAX) or c = a + b (PSUM,
+    // float32, a first) where a one-replica dwell stores its |.|^2: first dwell
+    ACQ_EPI_PMAX = 7,
+    ACQ_EPI_PMAX_ACC = 8, // grid += c: later dwells (the scratch image of the last bin holds c, as it holds |.|^2 under MAG_ACC)
+    ACQ_EPI_PSUM = 9,
+    ACQ_EPI_PSUM_ACC = 10
 };
 
 struct AcqMagArgs

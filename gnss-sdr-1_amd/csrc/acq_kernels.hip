@@ -1287,7 +1287,12 @@ static __device__ __forceinline__ MaxPair max_pair(MaxPair a, MaxPair b)
 #ifndef ACQ_COLS_PAIR_WAVES
 #define ACQ_COLS_PAIR_WAVES 3  // the two-dwell epilogue is held to the registers of the one-dwell kernel (168: three waves per SIMD)
 #endif
-// one 256-column block `xblk` (of n_xblk) of cell `cell`.  p1s: N1 x ACQ_THREADS floats of LDS (two-dwell epilogues only), svs: 2 x
+// epilogues of a paired engine: two replicas per satellite, one combined |.|^2 per cell (acq_kernels.h)
+static constexpr bool acq_epi_comb_max(int epi) { return epi == ACQ_EPI_PMAX || epi == ACQ_EPI_PMAX_ACC; }
+static constexpr bool acq_epi_comb(int epi) { return acq_epi_comb_max(epi) || epi == ACQ_EPI_PSUM || epi == ACQ_EPI_PSUM_ACC; }
+// epilogues that transform two columns per grid cell: the first |.|^2 waits in the LDS plane p1s
+static constexpr bool acq_epi_two(int epi) { return epi == ACQ_EPI_MAG2 || epi == ACQ_EPI_MAG2_ACC || acq_epi_comb(epi); }
+// one 256-column block `xblk` (of n_xblk) of cell `cell`.  p1s: N1 x ACQ_THREADS floats of LDS (two-column epilogues only), svs: 2 x
 // ACQ_THREADS / 64 words of LDS; a caller that loops over blocks puts a __syncthreads() between them
 template <int N1, bool INV, int EPI>
 static __device__ __forceinline__ void acq_cols_body(const AcqFftPlan& plan, const float2* __restrict__ Q, float2* __restrict__ out, const AcqMagArgs& mag,
@@ -1313,7 +1318,10 @@ static __device__ __forceinline__ void acq_cols_body(const AcqFftPlan& plan, con
     float2 v0[N1], v1[N1];
     // ACQ_EPI_MAG2: the rows pass ran over 2 * n_bins "bins" per satellite, the second half being the next dwell's spectra
     constexpr bool PAIR = (EPI == ACQ_EPI_MAG2 || EPI == ACQ_EPI_MAG2_ACC);
-    const size_t qcell = PAIR ? (size_t)(cell / mag.n_bins) * (2 * mag.n_bins) + cell % mag.n_bins : (size_t)cell;
+    // ACQ_EPI_PMAX / _PSUM: the same layout, [sat][2][n_bins][N], the second half being the same spectra against the satellite's second replica
+    constexpr bool COMB = acq_epi_comb(EPI);
+    constexpr bool TWO = acq_epi_two(EPI);
+    const size_t qcell = TWO ? (size_t)(cell / mag.n_bins) * (2 * mag.n_bins) + cell % mag.n_bins : (size_t)cell;
     const float2* q = Q + qcell * N;
     // the inter-pass buffer is read exactly once (here): streaming loads when ACQ_COLS_NT & 1; the magnitude grid is written once per
     // search: streaming stores when ACQ_COLS_NT & 2
@@ -1334,7 +1342,7 @@ static __device__ __forceinline__ void acq_cols_body(const AcqFftPlan& plan, con
     float2* res = RegFft<N1, 1, N1, INV>::result_in_first ? v0 : v1;
     // first dwell's magnitudes wait in LDS (N1 x 256 floats: 25 KB of the 160) while the second column is transformed: in
     // registers they cost the third wave per SIMD (208 instead of 168), and so do the second column's loads hoisted above the first transform
-    if (PAIR)
+    if (TWO)
         {
 #pragma unroll
             for (int k = 0; k < N1; k++) p1s[k * ACQ_THREADS + threadIdx.x] = res[k].x * res[k].x + res[k].y * res[k].y;
@@ -1376,14 +1384,16 @@ static __device__ __forceinline__ void acq_cols_body(const AcqFftPlan& plan, con
             float* g = mag.grid + (size_t)cell * N;
             const int sat = cell / mag.n_bins, bin = cell % mag.n_bins;
             // the scratch image holds the LAST dwell's own magnitudes of one bin whenever that dwell accumulated (the second of a fused pair always does)
-            float* tmp = (mag.tmp && (EPI == ACQ_EPI_MAG_ACC || PAIR) && bin == mag.tmp_bin) ? mag.tmp + (size_t)sat * N : nullptr;
+            // (a paired engine's accumulating dwell leaves its combined magnitudes there, its first dwell nothing: the rules of MAG_ACC and MAG)
+            constexpr bool COMB_ACC = (EPI == ACQ_EPI_PMAX_ACC || EPI == ACQ_EPI_PSUM_ACC);
+            float* tmp = (mag.tmp && (EPI == ACQ_EPI_MAG_ACC || PAIR || COMB_ACC) && bin == mag.tmp_bin) ? mag.tmp + (size_t)sat * N : nullptr;
             MaxPair best = {-1.0f, 0xffffffffu};
             if (active)
                 {
                     // non-coherent accumulation: all previous grid values are fetched before the first store (the compiler
                     // cannot prove that g[idx(k)] and g[idx(k')] differ, so a load after a store would wait for it: N1 serial
                     // round trips made the accumulating launches 2.5x slower than the first dwell's)
-                    constexpr bool HAS_PREV = (EPI == ACQ_EPI_MAG_ACC || EPI == ACQ_EPI_MAG2_ACC);  // whether the grid holds earlier dwells is part of the instantiation:
+                    constexpr bool HAS_PREV = (EPI == ACQ_EPI_MAG_ACC || EPI == ACQ_EPI_MAG2_ACC || COMB_ACC);  // whether the grid holds earlier dwells is part of the instantiation:
                     // the previous values are fetched up front (25 registers, the third instead of the fourth wave per SIMD) only where they exist
                     float prev[HAS_PREV ? N1 : 1];
 #pragma unroll
@@ -1407,6 +1417,19 @@ static __device__ __forceinline__ void acq_cols_body(const AcqFftPlan& plan, con
                                             const float first = p1s[k * ACQ_THREADS + threadIdx.x];
                                             val = (EPI == ACQ_EPI_MAG2_ACC ? prev[HAS_PREV ? k : 0] + first : first) + p;
                                             if (tmp) tmp[idx] = p;
+                                        }
+                                    else if (COMB)
+                                        {
+                                            // replica A's |.|^2 waited in LDS, p is replica B's: c = max(a, b) or a + b takes the place of
+                                            // a single-replica dwell's |.|^2
+                                            const float first = p1s[k * ACQ_THREADS + threadIdx.x];
+                                            const float c = acq_epi_comb_max(EPI) ? fmaxf(first, p) : first + p;
+                                            val = c;
+                                            if (COMB_ACC)
+                                                {
+                                                    if (tmp) tmp[idx] = c;
+                                                    val = prev[HAS_PREV ? k : 0] + c;
+                                                }
                                         }
                                     else if (EPI == ACQ_EPI_MAG_ACC)
                                         {
@@ -1456,12 +1479,11 @@ static __device__ __forceinline__ void acq_cols_body(const AcqFftPlan& plan, con
 
 
 template <int N1, bool INV, int EPI>
-__global__ __launch_bounds__(ACQ_THREADS, (N1 <= 25 ? ((EPI == ACQ_EPI_MAG2 || EPI == ACQ_EPI_MAG2_ACC) ? ACQ_COLS_PAIR_WAVES : ACQ_COLS_WAVES) : 1)) void acq_cols_kernel(AcqFftPlan plan, const float2* __restrict__ Q,
+__global__ __launch_bounds__(ACQ_THREADS, (N1 <= 25 ? (acq_epi_two(EPI) ? ACQ_COLS_PAIR_WAVES : ACQ_COLS_WAVES) : 1)) void acq_cols_kernel(AcqFftPlan plan, const float2* __restrict__ Q,
     float2* __restrict__ out, AcqMagArgs mag)
 {
-    constexpr bool PAIR = (EPI == ACQ_EPI_MAG2 || EPI == ACQ_EPI_MAG2_ACC);
-    // first dwell's magnitudes wait in LDS (N1 x 256 floats: 25 KB of the 160) while the second column is transformed
-    __shared__ float p1[PAIR ? N1 * ACQ_THREADS : 1];
+    // the first column's magnitudes wait in LDS (N1 x 256 floats: 25 KB of the 160) while the second column is transformed
+    __shared__ float p1[acq_epi_two(EPI) ? N1 * ACQ_THREADS : 1];
     __shared__ float sv[2 * (ACQ_THREADS / 64)];
     acq_cols_body<N1, INV, EPI>(plan, Q, out, mag, blockIdx.x, gridDim.x, blockIdx.y, p1, sv);
 }
@@ -2557,6 +2579,10 @@ static hipError_t launch_cols_n1(hipStream_t st, bool inverse, int epilogue, con
                 case ACQ_EPI_MAG_ACC: LAUNCH(true, ACQ_EPI_MAG_ACC); break;
                 case ACQ_EPI_MAG2: LAUNCH(true, ACQ_EPI_MAG2); break;
                 case ACQ_EPI_MAG2_ACC: LAUNCH(true, ACQ_EPI_MAG2_ACC); break;
+                case ACQ_EPI_PMAX: LAUNCH(true, ACQ_EPI_PMAX); break;
+                case ACQ_EPI_PMAX_ACC: LAUNCH(true, ACQ_EPI_PMAX_ACC); break;
+                case ACQ_EPI_PSUM: LAUNCH(true, ACQ_EPI_PSUM); break;
+                case ACQ_EPI_PSUM_ACC: LAUNCH(true, ACQ_EPI_PSUM_ACC); break;
                 default: return hipErrorInvalidValue;
                 }
         }

@@ -97,6 +97,12 @@ struct gc_acq
     hipStream_t side = nullptr;
     hipEvent_t ev_rows[2] = {nullptr, nullptr}, ev_cols[2] = {nullptr, nullptr};
     size_t q_stride = 0;      // float2 elements between the two halves of d_Q (0: single buffer)
+    // Paired engine (gc_acq_create_paired): 0, or GC_ACQ_COMBINE_MAX / _SUM.  Every satellite slot holds TWO replicas (d_codes is
+    // [sat][2][N]); the inverse row pass runs over 2 * n_bins cells per satellite -- the dwell's n_bins spectra against replica A, then
+    // the same spectra against replica B -- and the column pass combines the two |.|^2 of a grid cell before it writes it once
+    // (ACQ_EPI_PMAX / _PSUM).  The inter-pass buffer is the one a held-back dwell pair would need, so dwells are never held back.
+    int combine = 0;
+    int replicas() const { return combine ? 2 : 1; }
 };
 
 static hipError_t acq_flush_inverse(gc_acq* a, hipStream_t st);
@@ -216,12 +222,9 @@ static hipError_t acq_build_main_wipeoffs(gc_acq* a, hipStream_t st)
         }                                                                                              \
     while (0)
 
-extern "C" {
-
-gc_status gc_acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, gc_acq** out)
+// gc_acq_create (combine = 0) and gc_acq_create_paired
+static gc_status acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, int combine, gc_acq** out)
 {
-    GC_REQUIRE(ctx && conf && out, "gc_acq_create: NULL argument");
-    *out = nullptr;
     GC_REQUIRE(n_sats > 0, "gc_acq_create: n_sats must be > 0");
     GC_REQUIRE(conf->sampled_ms > 0 && conf->samples_per_ms > 0.0f, "gc_acq_create: bad sizes");
     GC_REQUIRE(conf->doppler_step > 0, "gc_acq_create: doppler_step must be > 0");
@@ -231,6 +234,7 @@ gc_status gc_acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, gc_acq
     a->ctx_ref.bind(ctx);
     a->conf = *conf;
     a->n_sats = n_sats;
+    a->combine = combine;
     // pcps_acquisition.cc:77-85, :113-117
     const bool bt = conf->bit_transition_flag != 0;
     a->consumed = (uint32_t)(conf->sampled_ms * conf->samples_per_ms * (bt ? 2 : 1));
@@ -267,7 +271,8 @@ gc_status gc_acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, gc_acq
     // batches are equal: a launch's workgroups run in rounds of (CUs x workgroups per CU), so the time of a pass steps with the
     // round count -- 11 + 11 + 10 satellites x 41 bins cost 3 + 3 + 2 rounds of the row pass, 16 + 16 cost 4 + 4 with fewer, larger
     // launches (measured 0.53 -> 0.50 ms per search)
-    size_t per_sat = (size_t)a->n_bins_alloc * N * sizeof(float2);
+    // (a paired engine's row pass writes 2 * n_bins_alloc cells per satellite; one satellite's pair always fits, whatever the budget says)
+    size_t per_sat = (size_t)a->replicas() * a->n_bins_alloc * N * sizeof(float2);
     size_t q_budget = (size_t)140 << 20;
     if (const char* e = std::getenv("GNSSCORR_ACQ_Q_MB")) q_budget = (size_t)std::max(1, std::atoi(e)) << 20;
     a->sats_per_batch = (int)(q_budget / per_sat);
@@ -277,7 +282,7 @@ gc_status gc_acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, gc_acq
         const int n_batches = (n_sats + a->sats_per_batch - 1) / a->sats_per_batch;
         a->sats_per_batch = (n_sats + n_batches - 1) / n_batches;
     }
-    size_t q_cells = (size_t)a->sats_per_batch * a->n_bins_alloc;
+    size_t q_cells = (size_t)a->sats_per_batch * a->replicas() * a->n_bins_alloc;
 
     ACQ_TRY(hipMalloc(&a->d_wN, N * sizeof(float2)));
     ACQ_TRY(hipMalloc(&a->d_wN2, (size_t)2 * a->plan.N2 * sizeof(float2)));
@@ -285,7 +290,7 @@ gc_status gc_acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, gc_acq
     a->d_wipe = a->d_wipe_main;
     if (conf->make_2_steps && conf->num_doppler_bins_step2 > 0)
         ACQ_TRY(hipMalloc(&a->d_wipe2, (size_t)conf->num_doppler_bins_step2 * N * sizeof(float2)));
-    ACQ_TRY(hipMalloc(&a->d_codes, (size_t)n_sats * N * sizeof(float2)));
+    ACQ_TRY(hipMalloc(&a->d_codes, (size_t)a->replicas() * n_sats * N * sizeof(float2)));
     ACQ_TRY(hipMalloc(&a->d_xw, (size_t)a->n_bins_alloc * N * sizeof(float2)));
     ACQ_TRY(hipMalloc(&a->d_X, (size_t)2 * a->n_bins_alloc * N * sizeof(float2)));  // two dwells' spectra (see inv_pending)
     if (const char* e = gc_exp_env("GNSSCORR_ACQ_FUSE")) a->fuse_dwells = std::atoi(e) != 0;
@@ -297,6 +302,7 @@ gc_status gc_acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, gc_acq
 #else
     a->roles = a->overlap = a->onchip = false;
 #endif
+    if (a->combine) a->roles = a->overlap = a->onchip = false;  // the experiment launches know one replica per satellite only
     if (a->roles && n_sats > 1) a->q_stride = q_cells * N;  // second inter-pass buffer
     if (a->overlap && a->sats_per_batch < n_sats)
         {
@@ -352,11 +358,54 @@ gc_status gc_acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, gc_acq
     }
     ACQ_TRY(hipMemsetAsync(a->d_grid, 0, (size_t)n_sats * a->n_bins_alloc * N * sizeof(float), st));
     ACQ_TRY(hipMemsetAsync(a->d_tmp, 0, (size_t)n_sats * N * sizeof(float), st));
-    ACQ_TRY(hipMemsetAsync(a->d_codes, 0, (size_t)n_sats * N * sizeof(float2), st));
+    ACQ_TRY(hipMemsetAsync(a->d_codes, 0, (size_t)a->replicas() * n_sats * N * sizeof(float2), st));
     ACQ_TRY(hipMemsetAsync(a->d_power, 0, sizeof(float), st));
     ACQ_TRY(hipStreamSynchronize(st));
     *out = a;
     return GC_OK;
+}
+
+// set_local_code (:252-273) of one replica: zero padded, FFT, conjugate, kept in d_codes[slot]; the caller holds the context mutex
+static gc_status acq_load_code(gc_acq* a, hipStream_t st, const float* code, size_t slot)
+{
+    const size_t N = a->fft_size;
+    // [0 .. 0 c_0 .. c_L] layouts of set_local_code (:252-269)
+    std::vector<float2> buf(N, make_float2(0.f, 0.f));
+    const float2* c = reinterpret_cast<const float2*>(code);
+    if (a->conf.bit_transition_flag)
+        {
+            size_t off = N / 2;
+            std::memcpy(buf.data() + off, c, sizeof(float2) * off);
+        }
+    else if (a->fft_size == a->consumed)
+        std::memcpy(buf.data(), c, sizeof(float2) * a->consumed);
+    else
+        std::memcpy(buf.data() + (N - a->consumed), c, sizeof(float2) * a->consumed);
+    GC_HIP(hipMemcpyAsync(a->d_in, buf.data(), N * sizeof(float2), hipMemcpyHostToDevice, st));
+    // FFT, conjugate (:272-273), kept in the row-permuted layout the inverse rows pass reads
+    hipError_t e = acq_launch_permute(st, a->d_in, nullptr, a->d_xw, a->plan, (int)N, 1, 0, 0, 0);
+    if (e == hipSuccess) e = acq_launch_rows(st, false, a->plan, 1, a->d_xw, AcqCellMap{1, 1}, nullptr, AcqCellMap{1, 1}, a->d_Q, a->d_wN2, a->d_wN);
+    if (e == hipSuccess) e = acq_launch_cols(st, false, ACQ_EPI_COMPLEX_CONJ_PERM, a->plan, 1, a->d_Q, a->d_codes + slot * N, nullptr);
+    if (e != hipSuccess) return gc_fail(GC_ERR_HIP, "gc_acq_set_local_code: %s", hipGetErrorString(e));
+    GC_HIP(hipStreamSynchronize(st));  // buf goes out of scope
+    return GC_OK;
+}
+
+extern "C" {
+
+gc_status gc_acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, gc_acq** out)
+{
+    GC_REQUIRE(ctx && conf && out, "gc_acq_create: NULL argument");
+    *out = nullptr;
+    return acq_create(ctx, conf, n_sats, 0, out);
+}
+
+gc_status gc_acq_create_paired(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, int combine, gc_acq** out)
+{
+    GC_REQUIRE(ctx && conf && out, "gc_acq_create_paired: NULL argument");
+    *out = nullptr;
+    GC_REQUIRE(combine == GC_ACQ_COMBINE_MAX || combine == GC_ACQ_COMBINE_SUM, "gc_acq_create_paired: unknown combiner %d", combine);
+    return acq_create(ctx, conf, n_sats, combine, out);
 }
 
 gc_status gc_acq_destroy(gc_acq* a)
@@ -382,31 +431,30 @@ gc_status gc_acq_fft_size(const gc_acq* a, uint32_t* fft_size, uint32_t* consume
 gc_status gc_acq_set_local_code(gc_acq* a, int sat, const float* code)
 {
     GC_REQUIRE(a && code, "gc_acq_set_local_code: NULL argument");
+    GC_REQUIRE(!a->combine, "gc_acq_set_local_code: a paired engine takes two replicas per slot (gc_acq_set_local_code_pair)");
     GC_REQUIRE(sat >= 0 && sat < a->n_sats, "gc_acq_set_local_code: satellite slot %d out of range", sat);
     gc_device_guard g(a->ctx->device);
     std::lock_guard<std::mutex> lk(a->ctx->mtx);
     hipStream_t st = a->ctx->stream;
-    const size_t N = a->fft_size;
     GC_HIP(acq_flush_inverse(a, st));  // a held-back dwell was searched with the codes of its time (and d_Q is the staging buffer below)
-    // [0 .. 0 c_0 .. c_L] layouts of set_local_code (:252-269)
-    std::vector<float2> buf(N, make_float2(0.f, 0.f));
-    const float2* c = reinterpret_cast<const float2*>(code);
-    if (a->conf.bit_transition_flag)
-        {
-            size_t off = N / 2;
-            std::memcpy(buf.data() + off, c, sizeof(float2) * off);
-        }
-    else if (a->fft_size == a->consumed)
-        std::memcpy(buf.data(), c, sizeof(float2) * a->consumed);
-    else
-        std::memcpy(buf.data() + (N - a->consumed), c, sizeof(float2) * a->consumed);
-    GC_HIP(hipMemcpyAsync(a->d_in, buf.data(), N * sizeof(float2), hipMemcpyHostToDevice, st));
-    // FFT, conjugate (:272-273), kept in the row-permuted layout the inverse rows pass reads
-    hipError_t e = acq_launch_permute(st, a->d_in, nullptr, a->d_xw, a->plan, (int)N, 1, 0, 0, 0);
-    if (e == hipSuccess) e = acq_launch_rows(st, false, a->plan, 1, a->d_xw, AcqCellMap{1, 1}, nullptr, AcqCellMap{1, 1}, a->d_Q, a->d_wN2, a->d_wN);
-    if (e == hipSuccess) e = acq_launch_cols(st, false, ACQ_EPI_COMPLEX_CONJ_PERM, a->plan, 1, a->d_Q, a->d_codes + (size_t)sat * N, nullptr);
-    if (e != hipSuccess) return gc_fail(GC_ERR_HIP, "gc_acq_set_local_code: %s", hipGetErrorString(e));
-    GC_HIP(hipStreamSynchronize(st));  // buf goes out of scope
+    const gc_status s = acq_load_code(a, st, code, (size_t)sat);
+    if (s != GC_OK) return s;
+    a->code_set[sat] = 1;
+    return GC_OK;
+}
+
+gc_status gc_acq_set_local_code_pair(gc_acq* a, int sat, const float* code_a, const float* code_b)
+{
+    GC_REQUIRE(a && code_a && code_b, "gc_acq_set_local_code_pair: NULL argument");
+    GC_REQUIRE(a->combine, "gc_acq_set_local_code_pair: not a paired engine (gc_acq_create_paired)");
+    GC_REQUIRE(sat >= 0 && sat < a->n_sats, "gc_acq_set_local_code_pair: satellite slot %d out of range", sat);
+    gc_device_guard g(a->ctx->device);
+    std::lock_guard<std::mutex> lk(a->ctx->mtx);
+    hipStream_t st = a->ctx->stream;
+    GC_HIP(acq_flush_inverse(a, st));  // as gc_acq_set_local_code (a paired engine holds no dwell back: nothing to run)
+    gc_status s = acq_load_code(a, st, code_a, (size_t)2 * sat);
+    if (s == GC_OK) s = acq_load_code(a, st, code_b, (size_t)2 * sat + 1);
+    if (s != GC_OK) return s;
     a->code_set[sat] = 1;
     return GC_OK;
 }
@@ -485,8 +533,10 @@ static hipError_t acq_inverse(gc_acq* a, hipStream_t st, bool pair, bool accumul
     const size_t N = a->fft_size;
     const int n_bins = (int)a->n_bins;
     const bool bt = a->conf.bit_transition_flag != 0;
-    const int spectra = pair ? 2 * n_bins : n_bins;  // per satellite
-    const int q_cells = a->sats_per_batch * (int)a->n_bins_alloc;
+    // a paired engine (never `pair`: it holds no dwell back) runs the dwell's n_bins spectra against replica A, then against replica B
+    const int reps = a->replicas();
+    const int spectra = (pair ? 2 : reps) * n_bins;  // row-pass cells per satellite
+    const int q_cells = a->sats_per_batch * reps * (int)a->n_bins_alloc;
     int per_batch = q_cells / spectra;
     {
         const int n_batches = (a->n_sats + per_batch - 1) / per_batch;
@@ -549,14 +599,19 @@ static hipError_t acq_inverse(gc_acq* a, hipStream_t st, bool pair, bool accumul
             float2* Q = a->d_Q + (two_streams ? (size_t)(b & 1) * a->q_stride : 0);
             hipStream_t cst = two_streams ? a->side : st;
             if (two_streams && b >= 2) e = hipStreamWaitEvent(st, a->ev_cols[b & 1], 0);  // the columns of batch b - 2 have read this half
+            // cell -> (spectrum, replica): [sat][dwell][bin] x d_codes[sat] for a dwell pair, [sat][replica][bin] x d_codes[sat][replica] paired
+            const int x_spectra = spectra / reps, code_cells = spectra / reps;
             if (e == hipSuccess)
-                e = acq_launch_rows(st, true, a->plan, ns * spectra, a->d_X, AcqCellMap{1, spectra}, a->d_codes + (size_t)s0 * N,
-                    AcqCellMap{spectra, 1 << 30}, Q, a->d_wN2, a->d_wN);
+                e = acq_launch_rows(st, true, a->plan, ns * spectra, a->d_X, AcqCellMap{1, x_spectra}, a->d_codes + (size_t)s0 * reps * N,
+                    AcqCellMap{code_cells, 1 << 30}, Q, a->d_wN2, a->d_wN);
             if (e == hipSuccess && two_streams) e = hipEventRecord(a->ev_rows[b & 1], st);
             if (e == hipSuccess && two_streams) e = hipStreamWaitEvent(cst, a->ev_rows[b & 1], 0);
             if (e != hipSuccess) break;
             const AcqMagArgs m = mag_args(s0);
-            e = acq_launch_cols(cst, true, pair ? (accumulate ? ACQ_EPI_MAG2_ACC : ACQ_EPI_MAG2) : (accumulate ? ACQ_EPI_MAG_ACC : ACQ_EPI_MAG), a->plan, ns * n_bins, Q, nullptr, &m);
+            int epi = pair ? (accumulate ? ACQ_EPI_MAG2_ACC : ACQ_EPI_MAG2) : (accumulate ? ACQ_EPI_MAG_ACC : ACQ_EPI_MAG);
+            if (a->combine == GC_ACQ_COMBINE_MAX) epi = accumulate ? ACQ_EPI_PMAX_ACC : ACQ_EPI_PMAX;
+            if (a->combine == GC_ACQ_COMBINE_SUM) epi = accumulate ? ACQ_EPI_PSUM_ACC : ACQ_EPI_PSUM;
+            e = acq_launch_cols(cst, true, epi, a->plan, ns * n_bins, Q, nullptr, &m);
             if (e == hipSuccess && two_streams) e = hipEventRecord(a->ev_cols[b & 1], cst);
         }
     // everything behind this call on `st` sees the finished grid (the side stream runs its column passes in order: the last one's event covers all)
@@ -688,7 +743,7 @@ static gc_status acq_enqueue(gc_acq* a, const void* dev_iq_in, int iq_format, hi
                     e = acq_forward(a, st, 2);
                     if (e == hipSuccess) e = acq_inverse(a, st, true, a->inv_accumulate);
                 }
-            else if (a->fuse_dwells && plain && a->dwell_counter < a->max_dwells && q_cells >= 2 * n_bins && a->n_bins_alloc >= 2)
+            else if (a->fuse_dwells && !a->combine && plain && a->dwell_counter < a->max_dwells && q_cells >= 2 * n_bins && a->n_bins_alloc >= 2)
                 {
                     // more dwells of this search are expected: hold everything behind the input permutation back (see gc_acq::inv_pending)
                     a->inv_pending = true;
@@ -877,7 +932,8 @@ gc_status gc_acq_peek(gc_acq* a, int what, int index, float* host_out)
         }
     else if (what == GC_ACQ_PEEK_CODE)
         {
-            GC_REQUIRE(index >= 0 && index < a->n_sats, "gc_acq_peek: satellite slot %d out of range", index);
+            // paired engine: index = 2 * sat + replica
+            GC_REQUIRE(index >= 0 && index < a->replicas() * a->n_sats, "gc_acq_peek: code slot %d out of range", index);
             src = a->d_codes + (size_t)index * N;
         }
     else

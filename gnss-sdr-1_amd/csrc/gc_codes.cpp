@@ -782,4 +782,28 @@ gc_status gc_loop_sync_for_signal(char system, const char* signal, uint32_t prn,
     return GC_OK;
 }
 
+gc_status gc_cccwsr_replicas(const float* code_data, const float* code_pilot, uint32_t n, float* replica_a, float* replica_b)
+{
+    GC_REQUIRE(code_data && code_pilot && replica_a && replica_b, "gc_cccwsr_replicas: NULL argument");
+    for (uint32_t i = 0; i < n; i++)
+        {
+            const float dr = code_data[2 * i], di = code_data[2 * i + 1], pr = code_pilot[2 * i], pi = code_pilot[2 * i + 1];
+            // j * cp = (-pi, pr)
+            replica_a[2 * i] = dr + pi;
+            replica_a[2 * i + 1] = di - pr;
+            replica_b[2 * i] = dr - pi;
+            replica_b[2 * i + 1] = di + pr;
+        }
+    return GC_OK;
+}
+
+gc_status gc_e1_8ms_replicas(const float* code, uint32_t n, uint32_t samples_per_code, float* replica_a, float* replica_b)
+{
+    GC_REQUIRE(code && replica_a && replica_b, "gc_e1_8ms_replicas: NULL argument");
+    GC_REQUIRE(samples_per_code > 0 && (uint64_t)2 * samples_per_code <= n, "gc_e1_8ms_replicas: %u samples do not hold two code periods of %u", n, samples_per_code);
+    for (uint32_t i = 0; i < 2 * n; i++) replica_a[i] = replica_b[i] = code[i];
+    for (uint32_t i = 2 * samples_per_code; i < 4 * samples_per_code; i++) replica_b[i] = -code[i];
+    return GC_OK;
+}
+
 }  // extern "C"

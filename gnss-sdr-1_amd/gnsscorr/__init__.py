@@ -299,6 +299,10 @@ API = {
     "gc_acq_flush": (C.c_int, [_vp, _vp]),
     "gc_acq_get_grid": (C.c_int, [_vp, C.c_int, _fp]),
     "gc_acq_peek": (C.c_int, [_vp, C.c_int, C.c_int, _fp]),
+    "gc_acq_create_paired": (C.c_int, [_vp, C.POINTER(AcqConf), C.c_int, C.c_int, C.POINTER(_vp)]),
+    "gc_acq_set_local_code_pair": (C.c_int, [_vp, C.c_int, _fp, _fp]),
+    "gc_cccwsr_replicas": (C.c_int, [_fp, _fp, C.c_uint32, _fp, _fp]),
+    "gc_e1_8ms_replicas": (C.c_int, [_fp, C.c_uint32, C.c_uint32, _fp, _fp]),
     "gc_ring_decimator_create": (C.c_int, [_vp, _vp, C.c_uint32, _fp, C.c_uint32, _vp, C.POINTER(_vp)]),
     "gc_ring_decimator_destroy": (C.c_int, [_vp]),
     "gc_ring_decimator_update": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
@@ -515,6 +519,30 @@ def galileo_e1_code_gen_complex_sampled(signal, cboc, prn, fs, chip_shift=0):
     _check(load_library().gc_galileo_e1_code_gen_complex_sampled(d.view(np.float32).ctypes.data_as(_fp), signal.encode(), int(cboc), prn, fs,
         chip_shift, C.byref(n)))
     return d[:n.value].copy()
+
+
+def _c64p(a):
+    return a.view(np.float32).ctypes.data_as(_fp)
+
+
+def cccwsr_replicas(code_data, code_pilot):
+    """gc_cccwsr_replicas: (cd - j cp, cd + j cp), the two complex replicas whose correlations are the d + jp and d - jp of
+    pcps_cccwsr_acquisition_cc.cc:342-351."""
+    cd = np.ascontiguousarray(code_data, np.complex64)
+    cp = np.ascontiguousarray(code_pilot, np.complex64)
+    assert cd.shape == cp.shape and cd.ndim == 1, (cd.shape, cp.shape)
+    a, b = np.zeros_like(cd), np.zeros_like(cd)
+    _check(load_library().gc_cccwsr_replicas(_c64p(cd), _c64p(cp), cd.size, _c64p(a), _c64p(b)))
+    return a, b
+
+
+def e1_8ms_replicas(code, samples_per_code):
+    """gc_e1_8ms_replicas: the block's code A and code B, the second code period negated (galileo_pcps_8ms_acquisition_cc.cc:150-165)."""
+    code = np.ascontiguousarray(code, np.complex64)
+    assert code.ndim == 1, code.shape
+    a, b = np.zeros_like(code), np.zeros_like(code)
+    _check(load_library().gc_e1_8ms_replicas(_c64p(code), code.size, int(samples_per_code), _c64p(a), _c64p(b)))
+    return a, b
 
 
 class Context:
@@ -1136,19 +1164,27 @@ class TrackingLoop:
 
 class PcpsAcquisition:
     """gc_acq: pcps_acquisition (pcps_acquisition.cc) for n_sats satellites that
-    search the same input block."""
+    search the same input block.  combine = "max" / "sum": a paired engine (gc_acq_create_paired) whose slots hold two
+    replicas each (set_local_code_pair) and whose grid cells hold max(a, b) / a + b of the two |.|^2."""
+
+    COMBINE = {"max": 1, "sum": 2}
 
     def __init__(self, ctx, n_sats, fs_in, sampled_ms, ms_per_code, samples_per_ms, samples_per_code, samples_per_chip,
             doppler_max, doppler_step, max_dwells=1, bit_transition_flag=False, use_cfar=True, num_doppler_bins_override=0,
-            make_2_steps=False, num_doppler_bins_step2=4, doppler_step2=125.0):
+            make_2_steps=False, num_doppler_bins_step2=4, doppler_step2=125.0, combine=None):
         self._ctx = ctx
         self.n_sats = n_sats
+        self.combine = combine
         conf = AcqConf(int(fs_in), sampled_ms, ms_per_code, samples_per_ms, samples_per_code, samples_per_chip,
             doppler_max, doppler_step, max_dwells, int(bit_transition_flag), int(use_cfar), num_doppler_bins_override,
             int(make_2_steps), num_doppler_bins_step2, doppler_step2)
         self.conf = conf
         self._h = _vp()
-        _check(load_library().gc_acq_create(ctx._h, C.byref(conf), n_sats, C.byref(self._h)))
+        if combine is None:
+            _check(load_library().gc_acq_create(ctx._h, C.byref(conf), n_sats, C.byref(self._h)))
+        else:
+            # an unknown name reaches the library as an unknown combiner: GC_ERR_INVALID
+            _check(load_library().gc_acq_create_paired(ctx._h, C.byref(conf), n_sats, self.COMBINE.get(combine, 0), C.byref(self._h)))
         a, b, c = C.c_uint32(), C.c_uint32(), C.c_uint32()
         _check(load_library().gc_acq_fft_size(self._h, C.byref(a), C.byref(b), C.byref(c)))
         self.fft_size, self.consumed_samples, self.num_doppler_bins = a.value, b.value, c.value
@@ -1158,6 +1194,13 @@ class PcpsAcquisition:
         need = self.fft_size // 2 if self.conf.bit_transition_flag else self.consumed_samples
         assert code.size >= need, (code.size, need)
         _check(load_library().gc_acq_set_local_code(self._h, sat, code.view(np.float32).ctypes.data_as(_fp)))
+
+    def set_local_code_pair(self, sat, code_a, code_b):
+        code_a = np.ascontiguousarray(code_a, np.complex64)
+        code_b = np.ascontiguousarray(code_b, np.complex64)
+        need = self.fft_size // 2 if self.conf.bit_transition_flag else self.consumed_samples
+        assert code_a.size >= need and code_b.size >= need, (code_a.size, code_b.size, need)
+        _check(load_library().gc_acq_set_local_code_pair(self._h, sat, _c64p(code_a), _c64p(code_b)))
 
     def reset(self):
         _check(load_library().gc_acq_reset(self._h))
@@ -1212,7 +1255,7 @@ class PcpsAcquisition:
 
     def peek(self, what, index):
         """gc_acq_peek: a device-resident intermediate in natural order (complex64[fft_size], or float32[num_doppler_bins, 2]
-        = (row maximum, its index) for PEEK_ROW_MAX)."""
+        = (row maximum, its index) for PEEK_ROW_MAX).  PEEK_CODE on a paired engine: index = 2 * sat + replica."""
         if what == self.PEEK_ROW_MAX:
             out = np.zeros((self.num_doppler_bins, 2), np.float32)
         else:

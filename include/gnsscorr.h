@@ -754,13 +754,42 @@ gc_status gc_acq_flush(gc_acq* a, void* stream);
 gc_status gc_acq_dwell_stream(gc_acq* a, gc_stream* s, uint64_t first_index, gc_acq_result* host_results);
 /* Copies satellite `sat`'s magnitude grid (num_doppler_bins * fft_size floats) to host. */
 gc_status gc_acq_get_grid(gc_acq* a, int sat, float* host_grid);
+
+/* Paired engine: every satellite slot holds TWO replicas, A and B, and each dwell searches both against the same spectra -- the
+ * operation the reference ships three times:
+ *   pcps_cccwsr_acquisition_cc.cc:316-370          data and pilot correlations combined as d + jp and d - jp, the larger wins
+ *   galileo_pcps_8ms_acquisition_cc.cc:303-345     two sign hypotheses of an 8 ms replica, the larger wins
+ *   galileo_e5a_noncoherent_iq_acquisition_caf_cc  |corr_I|^2 + |corr_Q|^2
+ * For every dwell, Doppler bin and sample, with a = |IFFT(X_bin conj(FFT(A)))|^2 and b the same for B:
+ *   GC_ACQ_COMBINE_MAX   c = max(a, b)
+ *   GC_ACQ_COMBINE_SUM   c = a + b   (float32, a first)
+ * The grid gets c on the first dwell and prev + c on later dwells: c stands wherever a one-replica dwell puts its |.|^2 (grid, row
+ * maxima, the scratch image of the second-peak search, gc_acq_result, gc_acq_get_grid, GC_ACQ_PEEK_ROW_MAX), and the two |.|^2 are
+ * combined on the device before the cell is written once.  CCCWSR is two complex replicas by linearity: d + jp belongs to
+ * A = cd - j cp and d - jp to B = cd + j cp (gc_cccwsr_replicas).  Any other `combine` returns GC_ERR_INVALID.  Everything else --
+ * conf, bit transition, step two, frequency offset, input formats, the enqueue / flush / fetch calls -- is gc_acq_create's; dwells
+ * enqueued back to back are never held back for one another and give the results of one gc_acq_dwell per block, bit for bit. */
+enum { GC_ACQ_COMBINE_MAX = 1, GC_ACQ_COMBINE_SUM = 2 };
+gc_status gc_acq_create_paired(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, int combine, gc_acq** out);
+/* set_local_code of both replicas of slot `sat` (pcps_cccwsr_acquisition_cc.cc:161-179, galileo_pcps_8ms_acquisition_cc.cc:147-166):
+ * two host pointers with the length rules of gc_acq_set_local_code; an all-zero replica is legal (its |.|^2 is 0).  Paired engines
+ * only: GC_ERR_INVALID on a gc_acq_create engine, as gc_acq_set_local_code is on a paired one. */
+gc_status gc_acq_set_local_code_pair(gc_acq* a, int sat, const float* code_a, const float* code_b);
+/* The replica pairs of the reference's two-hypothesis blocks, n complex samples each (interleaved floats; outputs may not alias inputs):
+ *   gc_cccwsr_replicas   A = cd - j cp, B = cd + j cp: |d + jp|^2 and |d - jp|^2 of pcps_cccwsr_acquisition_cc.cc:342-351 are the
+ *                        |.|^2 of the correlations with A and B
+ *   gc_e1_8ms_replicas   A = code, B = code with its second code period [samples_per_code, 2 * samples_per_code) negated
+ *                        (galileo_pcps_8ms_acquisition_cc.cc:150-165); n >= 2 * samples_per_code */
+gc_status gc_cccwsr_replicas(const float* code_data, const float* code_pilot, uint32_t n, float* replica_a, float* replica_b);
+gc_status gc_e1_8ms_replicas(const float* code, uint32_t n, uint32_t samples_per_code, float* replica_a, float* replica_b);
 /* Inspection of the engine's device-resident intermediates (tests, failure dumps; synchronises the context stream; natural element
  * order whatever the layout in HBM).  `what`:
  *   GC_ACQ_PEEK_WIPEOFF   index = Doppler bin: the wipe-off row exp(-j phase) of the ACTIVE grid, d_grid_doppler_wipeoffs[bin]
  *                         (pcps_acquisition.cc:296-310), fft_size complex values = 2 * fft_size floats
  *   GC_ACQ_PEEK_SPECTRUM  index = Doppler bin: FFT(x * wipeoff[bin]) of the last dwell's block (of the first block of a dwell
  *                         pair processed together) (:721), 2 * fft_size floats
- *   GC_ACQ_PEEK_CODE      index = satellite slot: conj(FFT(code)) (d_fft_codes, :272-273), 2 * fft_size floats
+ *   GC_ACQ_PEEK_CODE      index = satellite slot: conj(FFT(code)) (d_fft_codes, :272-273), 2 * fft_size floats; on a paired engine
+ *                         index = 2 * satellite slot + replica (0: A, 1: B)
  *   GC_ACQ_PEEK_ROW_MAX   index = satellite slot: per Doppler bin the maximum of the grid row and its position as the statistics
  *                         kernel sees them (the column pass's block maxima, combined): 2 * num_doppler_bins floats (value, index) */
 enum { GC_ACQ_PEEK_WIPEOFF = 0, GC_ACQ_PEEK_SPECTRUM = 1, GC_ACQ_PEEK_CODE = 2, GC_ACQ_PEEK_ROW_MAX = 3 };
