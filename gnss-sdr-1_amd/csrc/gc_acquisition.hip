@@ -4,6 +4,7 @@
 // acquisition_core (:668-770) -- batched over n_sats satellites that search the
 // same input block.
 #include "acq_kernels.h"
+#include "acq_quicksync_kernels.h"
 #include "gc_internal.h"
 #include "gc_stream.h"
 #include <algorithm>
@@ -103,6 +104,19 @@ struct gc_acq
     // (ACQ_EPI_PMAX / _PSUM).  The inter-pass buffer is the one a held-back dwell pair would need, so dwells are never held back.
     int combine = 0;
     int replicas() const { return combine ? 2 : 1; }
+    // QuickSync engine (gc_acq_create_quicksync, pcps_quicksync_acquisition_cc.cc): 0, or the folding factor f.  fft_size is M = N / f
+    // (N = samples_per_code), consumed is L = f N.  The wipe-off table holds L samples per bin in NATURAL order (the fold kernel and
+    // the candidate check read it; no transform does), a dwell folds x * wipeoff into n_bins rows of M samples (acq_qs_fold_kernel,
+    // row-permuted into d_xw), runs the transforms and the CFAR statistic of the plain engine at size M -- the grid is overwritten
+    // by every dwell, nothing accumulates -- and resolves the f aliased delays on the device (acq_qs_verify_kernel).  Dwells are
+    // never held back and the statistics kernel runs with its dwell: the candidate check reads its winner.
+    int fold = 0;
+    uint32_t qs_code_len = 0;          // N
+    AcqFftPlan wipe_plan{};            // N1 = 1, N2 = L: the table builder writes natural order
+    float2* d_code_time = nullptr;     // [sat][N]: the codes as handed in (d_code, :182)
+    float* d_cand_val = nullptr;       // [sat][f]: d_corr_output_f of the last dwell
+    uint32_t* d_cand_delay = nullptr;  // [sat][f]: d_possible_delay
+    size_t input_len() const { return fold ? consumed : fft_size; }  // samples of d_in / d_cvt and of a wipe-off row
 };
 
 static hipError_t acq_flush_inverse(gc_acq* a, hipStream_t st);
@@ -147,6 +161,9 @@ static void acq_release(gc_acq* a)
     (void)hipFree(a->d_results);
     (void)hipFree(a->d_part_val);
     (void)hipFree(a->d_part_cnt);
+    (void)hipFree(a->d_code_time);
+    (void)hipFree(a->d_cand_val);
+    (void)hipFree(a->d_cand_delay);
     if (a->h_results) (void)hipHostFree(a->h_results);
     for (int i = 0; i < 2; i++)
         {
@@ -170,7 +187,7 @@ static hipError_t acq_build_wipeoffs(gc_acq* a, const std::vector<float>& inc, f
     std::vector<int> off(n + 1, 0);
     for (int d = 0; d < n; d++)
         {
-            acq_phase_segments(inc[d], (int)a->fft_size, segs);
+            acq_phase_segments(inc[d], (int)a->input_len(), segs);
             off[d + 1] = (int)segs.size();
         }
     hipError_t e = hipSuccess;
@@ -186,7 +203,7 @@ static hipError_t acq_build_wipeoffs(gc_acq* a, const std::vector<float>& inc, f
         }
     e = hipMemcpyAsync(a->d_segs, segs.data(), sizeof(AcqPhaseSeg) * segs.size(), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = hipMemcpyAsync(a->d_seg_off, off.data(), sizeof(int) * (n + 1), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = acq_launch_wipeoff_segments(st, a->d_segs, a->d_seg_off, table, n, a->plan);
+    if (e == hipSuccess) e = acq_launch_wipeoff_segments(st, a->d_segs, a->d_seg_off, table, n, a->fold ? a->wipe_plan : a->plan);
     if (e == hipSuccess) e = hipStreamSynchronize(st);  // the host vectors go out of scope
     return e;
 }
@@ -222,8 +239,8 @@ static hipError_t acq_build_main_wipeoffs(gc_acq* a, hipStream_t st)
         }                                                                                              \
     while (0)
 
-// gc_acq_create (combine = 0) and gc_acq_create_paired
-static gc_status acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, int combine, gc_acq** out)
+// gc_acq_create (combine = 0), gc_acq_create_paired and gc_acq_create_quicksync (fold = f, conf prepared by the entry point)
+static gc_status acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, int combine, int fold, gc_acq** out)
 {
     GC_REQUIRE(n_sats > 0, "gc_acq_create: n_sats must be > 0");
     GC_REQUIRE(conf->sampled_ms > 0 && conf->samples_per_ms > 0.0f, "gc_acq_create: bad sizes");
@@ -235,6 +252,7 @@ static gc_status acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, in
     a->conf = *conf;
     a->n_sats = n_sats;
     a->combine = combine;
+    a->fold = fold;
     // pcps_acquisition.cc:77-85, :113-117
     const bool bt = conf->bit_transition_flag != 0;
     a->consumed = (uint32_t)(conf->sampled_ms * conf->samples_per_ms * (bt ? 2 : 1));
@@ -250,6 +268,17 @@ static gc_status acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, in
     a->use_cfar = (a->max_dwells == 1) ? (conf->use_CFAR_algorithm_flag != 0) : false;
     // :326
     a->n_bins = (uint32_t)std::ceil((double)((int32_t)conf->doppler_max - (int32_t)(-(int32_t)conf->doppler_max)) / (double)conf->doppler_step);
+    if (fold)
+        {
+            // pcps_quicksync_acquisition_cc.cc:95 (d_fft_size), :226-231 (the grid includes +doppler_max), :362-364 (f code periods per dwell)
+            a->qs_code_len = (uint32_t)conf->samples_per_code;
+            a->fft_size = a->qs_code_len / (uint32_t)fold;
+            a->consumed = a->qs_code_len * (uint32_t)fold;
+            a->eff = a->fft_size;
+            a->n_bins = 2 * conf->doppler_max / conf->doppler_step + 1;
+            a->wipe_plan.N = a->wipe_plan.N2 = (int)a->consumed;
+            a->wipe_plan.N1 = 1;
+        }
     if (conf->num_doppler_bins_override > 0) a->n_bins = conf->num_doppler_bins_override;
     a->n_bins_main = a->n_bins;
     a->n_bins_alloc = a->n_bins;
@@ -286,7 +315,7 @@ static gc_status acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, in
 
     ACQ_TRY(hipMalloc(&a->d_wN, N * sizeof(float2)));
     ACQ_TRY(hipMalloc(&a->d_wN2, (size_t)2 * a->plan.N2 * sizeof(float2)));
-    ACQ_TRY(hipMalloc(&a->d_wipe_main, (size_t)a->n_bins_main * N * sizeof(float2)));
+    ACQ_TRY(hipMalloc(&a->d_wipe_main, (size_t)a->n_bins_main * a->input_len() * sizeof(float2)));
     a->d_wipe = a->d_wipe_main;
     if (conf->make_2_steps && conf->num_doppler_bins_step2 > 0)
         ACQ_TRY(hipMalloc(&a->d_wipe2, (size_t)conf->num_doppler_bins_step2 * N * sizeof(float2)));
@@ -324,9 +353,19 @@ static gc_status acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, in
     ACQ_TRY(hipMalloc(&a->d_blkv, (size_t)n_sats * a->n_bins_alloc * a->n_blocks * sizeof(float)));
     ACQ_TRY(hipMalloc(&a->d_blki, (size_t)n_sats * a->n_bins_alloc * a->n_blocks * sizeof(unsigned)));
     ACQ_TRY(hipMalloc(&a->d_power, sizeof(float)));
-    ACQ_TRY(hipMalloc(&a->d_in, N * sizeof(float2)));
-    ACQ_TRY(hipMalloc(&a->d_cvt, N * sizeof(float2)));
+    ACQ_TRY(hipMalloc(&a->d_in, a->input_len() * sizeof(float2)));
+    ACQ_TRY(hipMalloc(&a->d_cvt, a->input_len() * sizeof(float2)));
+    if (fold)
+        {
+            ACQ_TRY(hipMalloc(&a->d_code_time, (size_t)n_sats * a->qs_code_len * sizeof(float2)));
+            ACQ_TRY(hipMalloc(&a->d_cand_val, (size_t)n_sats * fold * sizeof(float)));
+            ACQ_TRY(hipMalloc(&a->d_cand_delay, (size_t)n_sats * fold * sizeof(uint32_t)));
+            ACQ_TRY(hipMemset(a->d_code_time, 0, (size_t)n_sats * a->qs_code_len * sizeof(float2)));
+            ACQ_TRY(hipMemset(a->d_cand_val, 0, (size_t)n_sats * fold * sizeof(float)));
+            ACQ_TRY(hipMemset(a->d_cand_delay, 0, (size_t)n_sats * fold * sizeof(uint32_t)));
+        }
     ACQ_TRY(hipMalloc(&a->d_results, (size_t)n_sats * sizeof(gc_acq_result)));
+    if (fold) ACQ_TRY(hipMemset(a->d_results, 0, (size_t)n_sats * sizeof(gc_acq_result)));  // the candidate check reads its winner from here
     ACQ_TRY(hipMalloc(&a->d_part_val, (size_t)n_sats * ACQ_FINAL_PIECES * 2 * sizeof(float)));
     ACQ_TRY(hipMalloc(&a->d_part_cnt, (size_t)n_sats * sizeof(unsigned)));
     ACQ_TRY(hipMemset(a->d_part_cnt, 0, (size_t)n_sats * sizeof(unsigned)));
@@ -365,6 +404,8 @@ static gc_status acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, in
     return GC_OK;
 }
 
+static gc_status acq_load_padded(gc_acq* a, hipStream_t st, const std::vector<float2>& buf, size_t slot);
+
 // set_local_code (:252-273) of one replica: zero padded, FFT, conjugate, kept in d_codes[slot]; the caller holds the context mutex
 static gc_status acq_load_code(gc_acq* a, hipStream_t st, const float* code, size_t slot)
 {
@@ -381,6 +422,12 @@ static gc_status acq_load_code(gc_acq* a, hipStream_t st, const float* code, siz
         std::memcpy(buf.data(), c, sizeof(float2) * a->consumed);
     else
         std::memcpy(buf.data() + (N - a->consumed), c, sizeof(float2) * a->consumed);
+    return acq_load_padded(a, st, buf, slot);
+}
+
+static gc_status acq_load_padded(gc_acq* a, hipStream_t st, const std::vector<float2>& buf, size_t slot)
+{
+    const size_t N = a->fft_size;
     GC_HIP(hipMemcpyAsync(a->d_in, buf.data(), N * sizeof(float2), hipMemcpyHostToDevice, st));
     // FFT, conjugate (:272-273), kept in the row-permuted layout the inverse rows pass reads
     hipError_t e = acq_launch_permute(st, a->d_in, nullptr, a->d_xw, a->plan, (int)N, 1, 0, 0, 0);
@@ -397,7 +444,7 @@ gc_status gc_acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, gc_acq
 {
     GC_REQUIRE(ctx && conf && out, "gc_acq_create: NULL argument");
     *out = nullptr;
-    return acq_create(ctx, conf, n_sats, 0, out);
+    return acq_create(ctx, conf, n_sats, 0, 0, out);
 }
 
 gc_status gc_acq_create_paired(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, int combine, gc_acq** out)
@@ -405,7 +452,30 @@ gc_status gc_acq_create_paired(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats,
     GC_REQUIRE(ctx && conf && out, "gc_acq_create_paired: NULL argument");
     *out = nullptr;
     GC_REQUIRE(combine == GC_ACQ_COMBINE_MAX || combine == GC_ACQ_COMBINE_SUM, "gc_acq_create_paired: unknown combiner %d", combine);
-    return acq_create(ctx, conf, n_sats, combine, out);
+    return acq_create(ctx, conf, n_sats, combine, 0, out);
+}
+
+gc_status gc_acq_create_quicksync(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, uint32_t folding_factor, gc_acq** out)
+{
+    GC_REQUIRE(ctx && conf && out, "gc_acq_create_quicksync: NULL argument");
+    *out = nullptr;
+    GC_REQUIRE(folding_factor >= 1 && folding_factor <= 100, "gc_acq_create_quicksync: folding factor %u is not in 1 .. 100", folding_factor);
+    GC_REQUIRE(!conf->make_2_steps, "gc_acq_create_quicksync: the QuickSync search has no second step");
+    GC_REQUIRE(conf->samples_per_code >= 1.0f && conf->samples_per_code < 16777216.0f, "gc_acq_create_quicksync: bad samples_per_code");
+    const uint32_t n_code = (uint32_t)conf->samples_per_code;
+    GC_REQUIRE(n_code / folding_factor >= 1, "gc_acq_create_quicksync: %u samples per code folded %u times leave no transform", n_code, folding_factor);
+    GC_REQUIRE(conf->sampled_ms > 0 && conf->samples_per_ms > 0.0f, "gc_acq_create_quicksync: bad sizes");
+    GC_REQUIRE((uint64_t)(conf->sampled_ms * conf->samples_per_ms) >= (uint64_t)n_code * folding_factor,
+        "gc_acq_create_quicksync: a block of %u ms does not hold %u code periods of %u samples", conf->sampled_ms, folding_factor, n_code);
+    // the engine's view of the configuration: the decision machine (max_dwells, bit_transition_flag, :503-527) belongs to the caller, every
+    // dwell stands alone (:340-342) and is judged by max / M^4 / input_power (:422, :480); a doppler_step of 0 means 250 (:219-222)
+    gc_acq_conf c = *conf;
+    if (c.doppler_step == 0) c.doppler_step = 250;
+    c.max_dwells = 1;
+    c.bit_transition_flag = 0;
+    c.use_CFAR_algorithm_flag = 1;
+    c.num_doppler_bins_step2 = 0;
+    return acq_create(ctx, &c, n_sats, 0, (int)folding_factor, out);
 }
 
 gc_status gc_acq_destroy(gc_acq* a)
@@ -437,6 +507,21 @@ gc_status gc_acq_set_local_code(gc_acq* a, int sat, const float* code)
     std::lock_guard<std::mutex> lk(a->ctx->mtx);
     hipStream_t st = a->ctx->stream;
     GC_HIP(acq_flush_inverse(a, st));  // a held-back dwell was searched with the codes of its time (and d_Q is the staging buffer below)
+    if (a->fold)
+        {
+            // set_local_code (pcps_quicksync_acquisition_cc.cc:178-201): the code itself for the candidate check, and conj(FFT_M) of
+            // its f pieces of M samples added in float32, first piece first, onto a zeroed buffer
+            const size_t M = a->fft_size;
+            const float2* c = reinterpret_cast<const float2*>(code);
+            std::vector<float2> cf(M, make_float2(0.f, 0.f));
+            for (int i = 0; i < a->fold; i++)
+                for (size_t m = 0; m < M; m++) cf[m] = make_float2(cf[m].x + c[i * M + m].x, cf[m].y + c[i * M + m].y);
+            GC_HIP(hipMemcpyAsync(a->d_code_time + (size_t)sat * a->qs_code_len, code, sizeof(float2) * a->qs_code_len, hipMemcpyHostToDevice, st));
+            const gc_status sq = acq_load_padded(a, st, cf, (size_t)sat);  // synchronises: `code` and cf are free afterwards
+            if (sq != GC_OK) return sq;
+            a->code_set[sat] = 1;
+            return GC_OK;
+        }
     const gc_status s = acq_load_code(a, st, code, (size_t)sat);
     if (s != GC_OK) return s;
     a->code_set[sat] = 1;
@@ -447,6 +532,7 @@ gc_status gc_acq_set_local_code_pair(gc_acq* a, int sat, const float* code_a, co
 {
     GC_REQUIRE(a && code_a && code_b, "gc_acq_set_local_code_pair: NULL argument");
     GC_REQUIRE(a->combine, "gc_acq_set_local_code_pair: not a paired engine (gc_acq_create_paired)");
+    GC_REQUIRE(!a->fold, "gc_acq_set_local_code_pair: a QuickSync engine takes one code period per slot (gc_acq_set_local_code)");
     GC_REQUIRE(sat >= 0 && sat < a->n_sats, "gc_acq_set_local_code_pair: satellite slot %d out of range", sat);
     gc_device_guard g(a->ctx->device);
     std::lock_guard<std::mutex> lk(a->ctx->mtx);
@@ -462,6 +548,7 @@ gc_status gc_acq_set_local_code_pair(gc_acq* a, int sat, const float* code_a, co
 gc_status gc_acq_set_frequency_offset(gc_acq* a, int64_t offset_hz)
 {
     GC_REQUIRE(a, "gc_acq_set_frequency_offset: NULL handle");
+    GC_REQUIRE(!a->fold, "gc_acq_set_frequency_offset: the QuickSync search has no frequency offset");
     gc_device_guard g(a->ctx->device);
     std::lock_guard<std::mutex> lk(a->ctx->mtx);
     if (offset_hz == a->freq_offset_hz && a->wipe_valid) return GC_OK;
@@ -491,6 +578,7 @@ gc_status gc_acq_reset(gc_acq* a)
 gc_status gc_acq_set_step_two(gc_acq* a, int enable, float doppler_center_hz)
 {
     GC_REQUIRE(a, "gc_acq_set_step_two: NULL handle");
+    GC_REQUIRE(!a->fold, "gc_acq_set_step_two: the QuickSync search has no second step");
     gc_device_guard g(a->ctx->device);
     std::lock_guard<std::mutex> lk(a->ctx->mtx);
     hipStream_t st = a->ctx->stream;
@@ -690,6 +778,40 @@ static hipError_t acq_flush_inverse(gc_acq* a, hipStream_t st)
     return e;
 }
 
+// one QuickSync dwell (pcps_quicksync_acquisition_cc.cc:340-483) of every satellite slot on `st`, x the float block of L samples
+static hipError_t acq_enqueue_quicksync(gc_acq* a, const float2* x, hipStream_t st)
+{
+    const int n_bins = (int)a->n_bins, L = (int)a->consumed;
+    a->dwell_counter = 1;  // d_mag and d_test_statistics restart with every dwell (:340-342): nothing accumulates
+    // input power over the L samples (:362-364)
+    hipError_t e = acq_launch_input_power(st, x, L, L, a->d_power, nullptr, 0, 0);
+    // x * wipeoff[bin] folded f * f times (:382-396) into the rows the forward transform reads, which then runs with no second operand
+    if (e == hipSuccess) e = acq_qs_launch_fold(st, x, a->d_wipe, a->d_xw, n_bins, L, a->fold * a->fold, a->plan);
+    if (e == hipSuccess) e = acq_launch_rows(st, false, a->plan, n_bins, a->d_xw, AcqCellMap{1, n_bins}, nullptr, AcqCellMap{1, 1}, a->d_Q, a->d_wN2, a->d_wN);
+    if (e == hipSuccess) e = acq_launch_cols(st, false, ACQ_EPI_PERM, a->plan, n_bins, a->d_Q, a->d_X, nullptr);
+    // * conj(FFT_M(folded code)), IFFT_M, |.|^2 stored (:405-414); first maximum and max / M^4 / input_power (:420-422, :480)
+    if (e == hipSuccess) e = acq_inverse(a, st, false, false);
+    if (e == hipSuccess) e = acq_flush_final(a, st);
+    // the f delays the folded index stands for, correlated in the time domain (:440-474); the winner is read on the device
+    if (e == hipSuccess)
+        {
+            AcqQsVerifyArgs v;
+            v.x = x;
+            v.wipe = a->d_wipe;
+            v.codes = a->d_code_time;
+            v.results = a->d_results;
+            v.cand_val = a->d_cand_val;
+            v.cand_delay = a->d_cand_delay;
+            v.N = (int)a->qs_code_len;
+            v.M = (int)a->fft_size;
+            v.L = L;
+            v.f = a->fold;
+            v.n_bins = n_bins;
+            e = acq_qs_launch_verify(st, v, a->n_sats);
+        }
+    return e;
+}
+
 // one dwell of every satellite slot on `st`; the caller holds the context mutex
 static gc_status acq_enqueue(gc_acq* a, const void* dev_iq_in, int iq_format, hipStream_t st)
 {
@@ -704,6 +826,13 @@ static gc_status acq_enqueue(gc_acq* a, const void* dev_iq_in, int iq_format, hi
             hipError_t ec = acq_launch_convert(st, iq_format, dev_iq_in, a->d_cvt, (int)a->consumed);
             if (ec != hipSuccess) return gc_fail(GC_ERR_HIP, "gc_acq_dwell: input conversion failed: %s", hipGetErrorString(ec));
             dev_iq = a->d_cvt;
+        }
+    if (a->fold)
+        {
+            const hipError_t eq = acq_enqueue_quicksync(a, dev_iq, st);
+            if (eq != hipSuccess) return gc_fail(GC_ERR_HIP, "gc_acq_dwell: kernel launch failed: %s", hipGetErrorString(eq));
+            a->grid_logically_zero = false;
+            return GC_OK;
         }
     const size_t N = a->fft_size;
     const int n_bins = (int)a->n_bins;
@@ -938,9 +1067,52 @@ gc_status gc_acq_peek(gc_acq* a, int what, int index, float* host_out)
         }
     else
         return gc_fail(GC_ERR_INVALID, "gc_acq_peek: unknown item %d", what);
+    if (a->fold && what == GC_ACQ_PEEK_WIPEOFF)
+        {
+            // the QuickSync table: L samples per bin, in natural order already
+            GC_HIP(hipMemcpy(host_out, a->d_wipe + (size_t)index * a->consumed, (size_t)a->consumed * sizeof(float2), hipMemcpyDeviceToHost));
+            return GC_OK;
+        }
     std::vector<float2> p(N);
     GC_HIP(hipMemcpy(p.data(), src, N * sizeof(float2), hipMemcpyDeviceToHost));
     acq_unpermute(a->plan, p.data(), host_out);  // all three live in the row-permuted layout
+    return GC_OK;
+}
+
+gc_status gc_acq_quicksync_candidates(gc_acq* a, int sat, uint32_t* possible_delay, float* corr_output_f)
+{
+    GC_REQUIRE(a && possible_delay && corr_output_f, "gc_acq_quicksync_candidates: NULL argument");
+    GC_REQUIRE(a->fold, "gc_acq_quicksync_candidates: not a QuickSync engine (gc_acq_create_quicksync)");
+    GC_REQUIRE(sat >= 0 && sat < a->n_sats, "gc_acq_quicksync_candidates: satellite slot %d out of range", sat);
+    gc_device_guard g(a->ctx->device);
+    std::lock_guard<std::mutex> lk(a->ctx->mtx);
+    GC_HIP(hipStreamSynchronize(a->ctx->stream));
+    GC_HIP(hipMemcpy(possible_delay, a->d_cand_delay + (size_t)sat * a->fold, (size_t)a->fold * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    GC_HIP(hipMemcpy(corr_output_f, a->d_cand_val + (size_t)sat * a->fold, (size_t)a->fold * sizeof(float), hipMemcpyDeviceToHost));
+    return GC_OK;
+}
+
+gc_status gc_quicksync_default_folding_factor(uint32_t code_length, uint32_t* out)
+{
+    GC_REQUIRE(out, "gc_quicksync_default_folding_factor: NULL argument");
+    GC_REQUIRE(code_length >= 1, "gc_quicksync_default_folding_factor: empty code");
+    // gps_l1_ca_pcps_quicksync_acquisition.cc: ceil(sqrt(log2(code_length)))
+    *out = (uint32_t)std::ceil(std::sqrt(std::log2((double)code_length)));
+    return GC_OK;
+}
+
+gc_status gc_quicksync_threshold(float pfa, uint32_t code_length, uint32_t folding_factor, uint32_t doppler_max, uint32_t doppler_step, float* out)
+{
+    GC_REQUIRE(out, "gc_quicksync_threshold: NULL argument");
+    GC_REQUIRE(folding_factor >= 1 && doppler_step >= 1 && code_length >= folding_factor, "gc_quicksync_threshold: bad sizes");
+    // calculate_threshold of the adapters: the bins counted like init() counts them
+    uint32_t bins = 0;
+    for (int32_t d = -(int32_t)doppler_max; d <= (int32_t)doppler_max; d += (int32_t)doppler_step) bins++;
+    const uint32_t ncells = (code_length / folding_factor) * bins;
+    const double exponent = 1.0 / (double)ncells;
+    const double val = std::pow(1.0 - (double)pfa, exponent);
+    const double lambda = (double)code_length / (double)folding_factor;
+    *out = (float)(-std::log(1.0 - val) / lambda);
     return GC_OK;
 }
 

@@ -301,6 +301,10 @@ API = {
     "gc_acq_peek": (C.c_int, [_vp, C.c_int, C.c_int, _fp]),
     "gc_acq_create_paired": (C.c_int, [_vp, C.POINTER(AcqConf), C.c_int, C.c_int, C.POINTER(_vp)]),
     "gc_acq_set_local_code_pair": (C.c_int, [_vp, C.c_int, _fp, _fp]),
+    "gc_acq_create_quicksync": (C.c_int, [_vp, C.POINTER(AcqConf), C.c_int, C.c_uint32, C.POINTER(_vp)]),
+    "gc_acq_quicksync_candidates": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint32), _fp]),
+    "gc_quicksync_default_folding_factor": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32)]),
+    "gc_quicksync_threshold": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
     "gc_cccwsr_replicas": (C.c_int, [_fp, _fp, C.c_uint32, _fp, _fp]),
     "gc_e1_8ms_replicas": (C.c_int, [_fp, C.c_uint32, C.c_uint32, _fp, _fp]),
     "gc_ring_decimator_create": (C.c_int, [_vp, _vp, C.c_uint32, _fp, C.c_uint32, _vp, C.POINTER(_vp)]),
@@ -543,6 +547,20 @@ def e1_8ms_replicas(code, samples_per_code):
     a, b = np.zeros_like(code), np.zeros_like(code)
     _check(load_library().gc_e1_8ms_replicas(_c64p(code), code.size, int(samples_per_code), _c64p(a), _c64p(b)))
     return a, b
+
+
+def quicksync_default_folding_factor(code_length):
+    """gc_quicksync_default_folding_factor: ceil(sqrt(log2(code_length))), the QuickSync adapters' default."""
+    out = C.c_uint32()
+    _check(load_library().gc_quicksync_default_folding_factor(int(code_length), C.byref(out)))
+    return out.value
+
+
+def quicksync_threshold(pfa, code_length, folding_factor, doppler_max, doppler_step):
+    """gc_quicksync_threshold: calculate_threshold of the QuickSync adapters."""
+    out = C.c_float()
+    _check(load_library().gc_quicksync_threshold(float(pfa), int(code_length), int(folding_factor), int(doppler_max), int(doppler_step), C.byref(out)))
+    return out.value
 
 
 class Context:
@@ -1165,22 +1183,32 @@ class TrackingLoop:
 class PcpsAcquisition:
     """gc_acq: pcps_acquisition (pcps_acquisition.cc) for n_sats satellites that
     search the same input block.  combine = "max" / "sum": a paired engine (gc_acq_create_paired) whose slots hold two
-    replicas each (set_local_code_pair) and whose grid cells hold max(a, b) / a + b of the two |.|^2."""
+    replicas each (set_local_code_pair) and whose grid cells hold max(a, b) / a + b of the two |.|^2.
+    folding_factor = f: the QuickSync engine (gc_acq_create_quicksync, pcps_quicksync_acquisition_cc.cc): fft_size is
+    samples_per_code // f, a dwell consumes f * samples_per_code samples, set_local_code takes one code period, candidates(sat)
+    gives the f aliased delays and their time-domain correlations.  It excludes `combine`."""
 
     COMBINE = {"max": 1, "sum": 2}
 
     def __init__(self, ctx, n_sats, fs_in, sampled_ms, ms_per_code, samples_per_ms, samples_per_code, samples_per_chip,
             doppler_max, doppler_step, max_dwells=1, bit_transition_flag=False, use_cfar=True, num_doppler_bins_override=0,
-            make_2_steps=False, num_doppler_bins_step2=4, doppler_step2=125.0, combine=None):
+            make_2_steps=False, num_doppler_bins_step2=4, doppler_step2=125.0, combine=None, folding_factor=None):
+        if folding_factor is not None and combine is not None:
+            raise ValueError("folding_factor (the QuickSync engine) excludes combine (the paired engine)")
         self._ctx = ctx
         self.n_sats = n_sats
         self.combine = combine
+        self.folding_factor = folding_factor
         conf = AcqConf(int(fs_in), sampled_ms, ms_per_code, samples_per_ms, samples_per_code, samples_per_chip,
             doppler_max, doppler_step, max_dwells, int(bit_transition_flag), int(use_cfar), num_doppler_bins_override,
             int(make_2_steps), num_doppler_bins_step2, doppler_step2)
         self.conf = conf
         self._h = _vp()
-        if combine is None:
+        if folding_factor is not None:
+            if not 0 <= int(folding_factor) < 2 ** 32:
+                raise GnsscorrError(GC_ERR_INVALID, "folding factor %r out of range" % (folding_factor,))
+            _check(load_library().gc_acq_create_quicksync(ctx._h, C.byref(conf), n_sats, int(folding_factor), C.byref(self._h)))
+        elif combine is None:
             _check(load_library().gc_acq_create(ctx._h, C.byref(conf), n_sats, C.byref(self._h)))
         else:
             # an unknown name reaches the library as an unknown combiner: GC_ERR_INVALID
@@ -1192,6 +1220,8 @@ class PcpsAcquisition:
     def set_local_code(self, sat, code):
         code = np.ascontiguousarray(code, np.complex64)
         need = self.fft_size // 2 if self.conf.bit_transition_flag else self.consumed_samples
+        if self.folding_factor is not None:
+            need = int(self.conf.samples_per_code)  # one code period, folded by the engine
         assert code.size >= need, (code.size, need)
         _check(load_library().gc_acq_set_local_code(self._h, sat, code.view(np.float32).ctypes.data_as(_fp)))
 
@@ -1251,6 +1281,13 @@ class PcpsAcquisition:
         _check(load_library().gc_acq_get_grid(self._h, sat, _f32p(g)))
         return g
 
+    def candidates(self, sat):
+        """gc_acq_quicksync_candidates: (possible_delay uint32[f], corr_output_f float32[f]) of the last dwell (QuickSync engine)."""
+        f = int(self.folding_factor or 0)
+        delay, val = np.zeros(max(f, 1), np.uint32), np.zeros(max(f, 1), np.float32)
+        _check(load_library().gc_acq_quicksync_candidates(self._h, sat, delay.ctypes.data_as(C.POINTER(C.c_uint32)), _f32p(val)))
+        return delay[:f], val[:f]
+
     PEEK_WIPEOFF, PEEK_SPECTRUM, PEEK_CODE, PEEK_ROW_MAX = 0, 1, 2, 3
 
     def peek(self, what, index):
@@ -1258,6 +1295,8 @@ class PcpsAcquisition:
         = (row maximum, its index) for PEEK_ROW_MAX).  PEEK_CODE on a paired engine: index = 2 * sat + replica."""
         if what == self.PEEK_ROW_MAX:
             out = np.zeros((self.num_doppler_bins, 2), np.float32)
+        elif what == self.PEEK_WIPEOFF and self.folding_factor is not None:
+            out = np.zeros(2 * self.consumed_samples, np.float32)  # the QuickSync table holds f code periods per bin
         else:
             out = np.zeros(2 * self.fft_size, np.float32)
         _check(load_library().gc_acq_peek(self._h, int(what), int(index), _f32p(out)))

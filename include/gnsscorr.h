@@ -782,6 +782,35 @@ gc_status gc_acq_set_local_code_pair(gc_acq* a, int sat, const float* code_a, co
  *                        (galileo_pcps_8ms_acquisition_cc.cc:150-165); n >= 2 * samples_per_code */
 gc_status gc_cccwsr_replicas(const float* code_data, const float* code_pilot, uint32_t n, float* replica_a, float* replica_b);
 gc_status gc_e1_8ms_replicas(const float* code, uint32_t n, uint32_t samples_per_code, float* replica_a, float* replica_b);
+/* QuickSync engine (pcps_quicksync_acquisition_cc.cc): with N = samples_per_code, f = folding_factor, M = N / f (integer division)
+ * and L = f N, a dwell wipes the carrier off L samples, folds the f * f pieces of M samples into one (float32 products and sums,
+ * first piece first), correlates circularly at FFT size M against the code folded the same way, and then resolves the f aliased
+ * delays k* + i M of the winning cell by f time-domain correlations with the unfolded code -- on the device, with no host round trip.
+ *   Doppler bins    -doppler_max + b doppler_step for every value <= +doppler_max (the grid is INCLUSIVE: 21 bins for 5000 / 500,
+ *                   :226-231); a doppler_step of 0 means 250 (:219-222); num_doppler_bins_override as in gc_acq_create
+ *   conf fields     fs_in, sampled_ms, samples_per_ms, samples_per_code, doppler_max, doppler_step, max_dwells,
+ *                   bit_transition_flag, num_doppler_bins_override.  The last two of the block's own parameters only steer its decision
+ *                   state machine (:503-527), which lives with the caller (adapter/hip_pcps_quicksync_acquisition.h): every dwell
+ *                   stands alone, overwrites the grid, and dwells are never held back for one another
+ *   GC_ERR_INVALID  folding_factor outside 1 .. 100, M < 1, sampled_ms * samples_per_ms < L, make_2_steps set
+ * On such a handle gc_acq_fft_size reports M, L and the inclusive bin count; gc_acq_set_local_code takes ONE code period of N
+ * complex samples; a dwell consumes L samples; gc_acq_get_grid gives num_doppler_bins * M floats, |IFFT_M(.)|^2 unnormalised;
+ * gc_acq_peek gives 2 L floats for WIPEOFF and 2 M for SPECTRUM and CODE; input formats, rings, enqueue / flush / fetch work as
+ * documented above.  gc_acq_set_step_two, gc_acq_set_frequency_offset and gc_acq_set_local_code_pair return GC_ERR_INVALID.
+ * gc_acq_result: indext = k* (folded index of the first grid maximum, bins ascending), doppler_index / doppler_hz / acq_doppler_hz
+ * of its bin, mag = the grid maximum, input_power = mean |x|^2 over L samples, test_statistics = mag / M^4 / input_power (:422, :480),
+ * acq_delay_samples = k* + i* M of the first largest candidate (:471-474), both second_peak fields 0.
+ * Two deviations from the block: its candidate accumulators (`complex_acumulator[100]`, :442) are never initialised and are taken
+ * as zero; its candidate correlations read past the end of the wiped-off block when f = 1 (k* + N > L), here they stop at L. */
+gc_status gc_acq_create_quicksync(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, uint32_t folding_factor, gc_acq** out);
+/* d_possible_delay[i] and d_corr_output_f[i], i < folding_factor, of satellite slot `sat` in the last dwell (the values the block logs at
+ * :549-552).  Synchronises the context stream: call it behind the fetch of a dwell enqueued on another stream. */
+gc_status gc_acq_quicksync_candidates(gc_acq* a, int sat, uint32_t* possible_delay, float* corr_output_f);
+/* The adapters' default folding factor, ceil(sqrt(log2(code_length))) (gps_l1_ca_pcps_quicksync_acquisition.cc). */
+gc_status gc_quicksync_default_folding_factor(uint32_t code_length, uint32_t* out);
+/* The adapters' calculate_threshold: ncells = (code_length / folding_factor) * bins (integer division, bins counted inclusively),
+ * lambda = code_length / (double)folding_factor, threshold = -log(1 - pow(1 - pfa, 1 / ncells)) / lambda. */
+gc_status gc_quicksync_threshold(float pfa, uint32_t code_length, uint32_t folding_factor, uint32_t doppler_max, uint32_t doppler_step, float* out);
 /* Inspection of the engine's device-resident intermediates (tests, failure dumps; synchronises the context stream; natural element
  * order whatever the layout in HBM).  `what`:
  *   GC_ACQ_PEEK_WIPEOFF   index = Doppler bin: the wipe-off row exp(-j phase) of the ACTIVE grid, d_grid_doppler_wipeoffs[bin]
