@@ -28,7 +28,11 @@ enum
     ACQ_EPI_PMAX = 7,
     ACQ_EPI_PMAX_ACC = 8, // grid += c: later dwells (the scratch image of the last bin holds c, as it holds |.|^2 under MAG_ACC)
     ACQ_EPI_PSUM = 9,
-    ACQ_EPI_PSUM_ACC = 10
+    ACQ_EPI_PSUM_ACC = 10,
+    // Tong engine (gc_acq_create_tong, acq_launch_cols_tong only): the grid cell gets |.|^2 * s, rounded to float32, with
+    // s = 1 / (N^2 * N^2 * input power) of THIS dwell (pcps_tong_acquisition_cc.cc:352-360): first dwell of a search
+    ACQ_EPI_TONG = 11,
+    ACQ_EPI_TONG_ACC = 12  // grid += |.|^2 * s (product rounded, then added): later dwells
 };
 
 struct AcqMagArgs
@@ -59,6 +63,13 @@ hipError_t acq_launch_rows(hipStream_t st, bool inverse, const AcqFftPlan& plan,
 // columns pass + epilogue
 hipError_t acq_launch_cols(hipStream_t st, bool inverse, int epilogue, const AcqFftPlan& plan, int n_cells,
     const float2* Q, float2* out, const AcqMagArgs* mag);
+
+// inverse columns pass of a Tong dwell (epilogue ACQ_EPI_TONG, or ACQ_EPI_TONG_ACC with `accumulate`) over n_cells grid cells of
+// mag.n_bins per satellite: `frozen` holds one flag per satellite of THIS launch (offset like the pointers of `mag`) -- the
+// workgroups of a flagged satellite return at once, so its grid and row maxima stay those of its deciding dwell; `power` is the
+// dwell's input power on the device
+hipError_t acq_launch_cols_tong(hipStream_t st, bool accumulate, const AcqFftPlan& plan, int n_cells, const float2* Q, const AcqMagArgs& mag,
+    const int* frozen, const float* power);
 
 // The inverse row pass of one batch (arguments as acq_launch_rows, inverse) and the two-dwell column pass (epilogue ACQ_EPI_MAG2 /
 // _MAG2_ACC, n_cells_cols grid cells read from Qc) of the previous batch in ONE launch; only for plans acq_rows_cols_fusable() accepts

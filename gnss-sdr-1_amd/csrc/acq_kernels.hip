@@ -1296,7 +1296,7 @@ static constexpr bool acq_epi_two(int epi) { return epi == ACQ_EPI_MAG2 || epi =
 // ACQ_THREADS / 64 words of LDS; a caller that loops over blocks puts a __syncthreads() between them
 template <int N1, bool INV, int EPI>
 static __device__ __forceinline__ void acq_cols_body(const AcqFftPlan& plan, const float2* __restrict__ Q, float2* __restrict__ out, const AcqMagArgs& mag,
-    int xblk, int n_xblk, int cell, float* __restrict__ p1s, float* __restrict__ svs)
+    int xblk, int n_xblk, int cell, float* __restrict__ p1s, float* __restrict__ svs, float tong_scale = 0.0f)
 {
     const int N2 = plan.N2, N = plan.N;
     // Column of this thread.  The row-permuted epilogues (forward transforms) store natural index m = n2 + N2 k at (m % N1) N2 + m / N1:
@@ -1393,7 +1393,7 @@ static __device__ __forceinline__ void acq_cols_body(const AcqFftPlan& plan, con
                     // non-coherent accumulation: all previous grid values are fetched before the first store (the compiler
                     // cannot prove that g[idx(k)] and g[idx(k')] differ, so a load after a store would wait for it: N1 serial
                     // round trips made the accumulating launches 2.5x slower than the first dwell's)
-                    constexpr bool HAS_PREV = (EPI == ACQ_EPI_MAG_ACC || EPI == ACQ_EPI_MAG2_ACC || COMB_ACC);  // whether the grid holds earlier dwells is part of the instantiation:
+                    constexpr bool HAS_PREV = (EPI == ACQ_EPI_MAG_ACC || EPI == ACQ_EPI_MAG2_ACC || COMB_ACC || EPI == ACQ_EPI_TONG_ACC);  // whether the grid holds earlier dwells is part of the instantiation:
                     // the previous values are fetched up front (25 registers, the third instead of the fourth wave per SIMD) only where they exist
                     float prev[HAS_PREV ? N1 : 1];
 #pragma unroll
@@ -1435,6 +1435,13 @@ static __device__ __forceinline__ void acq_cols_body(const AcqFftPlan& plan, con
                                         {
                                             if (tmp) tmp[idx] = p;
                                             val = prev[HAS_PREV ? k : 0] + p;
+                                        }
+                                    else if (EPI == ACQ_EPI_TONG || EPI == ACQ_EPI_TONG_ACC)
+                                        {
+                                            // this dwell's |.|^2 normalised by its own input power: the product is rounded, then
+                                            // added (volk_32f_s32f_multiply_32f, then volk_32f_x2_add_32f; no contraction)
+                                            const float t = p * tong_scale;
+                                            val = (EPI == ACQ_EPI_TONG_ACC) ? prev[HAS_PREV ? k : 0] + t : t;
                                         }
 #if ACQ_COLS_NT & 2
                                     __builtin_nontemporal_store(val, &g[idx]);
@@ -1486,6 +1493,22 @@ __global__ __launch_bounds__(ACQ_THREADS, (N1 <= 25 ? (acq_epi_two(EPI) ? ACQ_CO
     __shared__ float p1[acq_epi_two(EPI) ? N1 * ACQ_THREADS : 1];
     __shared__ float sv[2 * (ACQ_THREADS / 64)];
     acq_cols_body<N1, INV, EPI>(plan, Q, out, mag, blockIdx.x, gridDim.x, blockIdx.y, p1, sv);
+}
+
+// Column pass of a Tong dwell (pcps_tong_acquisition_cc.cc:352-360).  A satellite whose detector has decided is frozen: the flag is
+// the same for the whole workgroup (blockIdx.y is its cell), read through the scalar unit, and the workgroup leaves before its
+// first vector load, barrier or LDS access -- the grid, the row maxima and the result of the deciding dwell stay as they are and
+// the pass moves no data for them.  s = 1 / (N^2 * N^2 * P) in float32 from the dwell's input power on the device.
+template <int N1, int EPI>
+__global__ __launch_bounds__(ACQ_THREADS, (N1 <= 25 ? ACQ_COLS_WAVES : 1)) void acq_cols_tong_kernel(AcqFftPlan plan, const float2* __restrict__ Q,
+    AcqMagArgs mag, const int* __restrict__ frozen, const float* __restrict__ power)
+{
+    const int cell = blockIdx.y;
+    if (__builtin_amdgcn_readfirstlane(frozen[cell / mag.n_bins]) != 0) return;
+    __shared__ float sv[2 * (ACQ_THREADS / 64)];
+    const float fnf = (float)plan.N * (float)plan.N;
+    const float s = 1.0f / (fnf * fnf * *power);
+    acq_cols_body<N1, true, EPI>(plan, Q, nullptr, mag, blockIdx.x, gridDim.x, cell, nullptr, sv, s);
 }
 
 #if ACQ_ROWS3_DBG
@@ -2631,6 +2654,43 @@ hipError_t acq_launch_cols(hipStream_t st, bool inverse, int epilogue, const Acq
         {
 #define CASE(K) \
     case K: return launch_cols_n1<K>(st, inverse, epilogue, plan, grid, Q, out, m);
+            CASE(1)
+            CASE(2)
+            CASE(3)
+            CASE(4)
+            CASE(5)
+            CASE(6)
+            CASE(8)
+            CASE(9)
+            CASE(10)
+            CASE(12)
+            CASE(15)
+            CASE(16)
+            CASE(20)
+            CASE(25)
+            CASE(32)
+            CASE(40)
+            CASE(50)
+#undef CASE
+        default:
+            return hipErrorInvalidValue;
+        }
+}
+
+hipError_t acq_launch_cols_tong(hipStream_t st, bool accumulate, const AcqFftPlan& plan, int n_cells, const float2* Q, const AcqMagArgs& mag,
+    const int* frozen, const float* power)
+{
+    if (!frozen || !power || mag.n_bins <= 0) return hipErrorInvalidValue;
+    dim3 grid(acq_cols_blocks(plan), n_cells);
+    switch (plan.N1)
+        {
+#define CASE(K)                                                                                                                          \
+    case K:                                                                                                                              \
+        if (accumulate)                                                                                                                  \
+            hipLaunchKernelGGL((acq_cols_tong_kernel<K, ACQ_EPI_TONG_ACC>), grid, dim3(ACQ_THREADS), 0, st, plan, Q, mag, frozen, power); \
+        else                                                                                                                             \
+            hipLaunchKernelGGL((acq_cols_tong_kernel<K, ACQ_EPI_TONG>), grid, dim3(ACQ_THREADS), 0, st, plan, Q, mag, frozen, power);     \
+        return hipGetLastError();
             CASE(1)
             CASE(2)
             CASE(3)

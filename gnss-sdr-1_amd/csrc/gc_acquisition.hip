@@ -5,6 +5,7 @@
 // same input block.
 #include "acq_kernels.h"
 #include "acq_quicksync_kernels.h"
+#include "acq_tong_kernels.h"
 #include "gc_internal.h"
 #include "gc_stream.h"
 #include <algorithm>
@@ -117,6 +118,18 @@ struct gc_acq
     float* d_cand_val = nullptr;       // [sat][f]: d_corr_output_f of the last dwell
     uint32_t* d_cand_delay = nullptr;  // [sat][f]: d_possible_delay
     size_t input_len() const { return fold ? consumed : fft_size; }  // samples of d_in / d_cvt and of a wipe-off row
+    // Tong engine (gc_acq_create_tong, pcps_tong_acquisition_cc.cc): fft_size = consumed = sampled_ms * samples_per_ms, the bin grid is
+    // inclusive.  Every dwell adds |.|^2 / (N^4 * its own input power) to the grid (acq_launch_cols_tong) and is followed by the
+    // decision kernel, which walks each running satellite's counter ON THE DEVICE and freezes the satellites that have decided: their
+    // column workgroups return at once from then on, so grid, row maxima and result stay those of the deciding dwell.  Dwells are
+    // never held back, nothing is pending behind one, and no call decides on the host.  gc_acq_reset() only marks the restart: the
+    // next dwell enqueues it (counters, flags, results) in front of its own work, on its own stream.
+    bool tong = false;
+    AcqTongParams tong_p{};
+    bool tong_restart = true;
+    AcqTongState* d_tong_state = nullptr;  // [sat]
+    int* d_tong_frozen = nullptr;          // [sat]
+    AcqTongState* h_tong_state = nullptr;  // pinned
 };
 
 static hipError_t acq_flush_inverse(gc_acq* a, hipStream_t st);
@@ -164,6 +177,9 @@ static void acq_release(gc_acq* a)
     (void)hipFree(a->d_code_time);
     (void)hipFree(a->d_cand_val);
     (void)hipFree(a->d_cand_delay);
+    (void)hipFree(a->d_tong_state);
+    (void)hipFree(a->d_tong_frozen);
+    if (a->h_tong_state) (void)hipHostFree(a->h_tong_state);
     if (a->h_results) (void)hipHostFree(a->h_results);
     for (int i = 0; i < 2; i++)
         {
@@ -239,8 +255,9 @@ static hipError_t acq_build_main_wipeoffs(gc_acq* a, hipStream_t st)
         }                                                                                              \
     while (0)
 
-// gc_acq_create (combine = 0), gc_acq_create_paired and gc_acq_create_quicksync (fold = f, conf prepared by the entry point)
-static gc_status acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, int combine, int fold, gc_acq** out)
+// gc_acq_create (combine = 0), gc_acq_create_paired, gc_acq_create_quicksync (fold = f, conf prepared by the entry point) and
+// gc_acq_create_tong (tong = its three counters, conf prepared by the entry point)
+static gc_status acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, int combine, int fold, gc_acq** out, const AcqTongParams* tong = nullptr)
 {
     GC_REQUIRE(n_sats > 0, "gc_acq_create: n_sats must be > 0");
     GC_REQUIRE(conf->sampled_ms > 0 && conf->samples_per_ms > 0.0f, "gc_acq_create: bad sizes");
@@ -278,6 +295,14 @@ static gc_status acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, in
             a->n_bins = 2 * conf->doppler_max / conf->doppler_step + 1;
             a->wipe_plan.N = a->wipe_plan.N2 = (int)a->consumed;
             a->wipe_plan.N1 = 1;
+        }
+    if (tong)
+        {
+            // pcps_tong_acquisition_cc.cc:107 (d_fft_size, no zero padding whatever the code length), :200-205 (the grid includes +doppler_max)
+            a->tong = true;
+            a->tong_p = *tong;
+            a->fft_size = a->eff = a->consumed;
+            a->n_bins = 2 * conf->doppler_max / conf->doppler_step + 1;
         }
     if (conf->num_doppler_bins_override > 0) a->n_bins = conf->num_doppler_bins_override;
     a->n_bins_main = a->n_bins;
@@ -363,6 +388,14 @@ static gc_status acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, in
             ACQ_TRY(hipMemset(a->d_code_time, 0, (size_t)n_sats * a->qs_code_len * sizeof(float2)));
             ACQ_TRY(hipMemset(a->d_cand_val, 0, (size_t)n_sats * fold * sizeof(float)));
             ACQ_TRY(hipMemset(a->d_cand_delay, 0, (size_t)n_sats * fold * sizeof(uint32_t)));
+        }
+    if (tong)
+        {
+            ACQ_TRY(hipMalloc(&a->d_tong_state, (size_t)n_sats * sizeof(AcqTongState)));
+            ACQ_TRY(hipMalloc(&a->d_tong_frozen, (size_t)n_sats * sizeof(int)));
+            ACQ_TRY(hipMemset(a->d_tong_state, 0, (size_t)n_sats * sizeof(AcqTongState)));
+            ACQ_TRY(hipMemset(a->d_tong_frozen, 0, (size_t)n_sats * sizeof(int)));
+            ACQ_TRY(hipHostMalloc(reinterpret_cast<void**>(&a->h_tong_state), (size_t)n_sats * sizeof(AcqTongState), hipHostMallocDefault));
         }
     ACQ_TRY(hipMalloc(&a->d_results, (size_t)n_sats * sizeof(gc_acq_result)));
     if (fold) ACQ_TRY(hipMemset(a->d_results, 0, (size_t)n_sats * sizeof(gc_acq_result)));  // the candidate check reads its winner from here
@@ -478,6 +511,42 @@ gc_status gc_acq_create_quicksync(gc_ctx* ctx, const gc_acq_conf* conf, int n_sa
     return acq_create(ctx, &c, n_sats, 0, (int)folding_factor, out);
 }
 
+gc_status gc_acq_create_tong(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, uint32_t tong_init_val, uint32_t tong_max_val, uint32_t tong_max_dwells,
+    gc_acq** out)
+{
+    GC_REQUIRE(ctx && conf && out, "gc_acq_create_tong: NULL argument");
+    *out = nullptr;
+    GC_REQUIRE(tong_init_val >= 1 && tong_init_val < tong_max_val, "gc_acq_create_tong: needs 1 <= tong_init_val (%u) < tong_max_val (%u)", tong_init_val,
+        tong_max_val);
+    GC_REQUIRE(tong_max_dwells >= 1, "gc_acq_create_tong: tong_max_dwells must be >= 1");
+    GC_REQUIRE(!conf->bit_transition_flag, "gc_acq_create_tong: the Tong search has no bit transition mode");
+    GC_REQUIRE(!conf->make_2_steps, "gc_acq_create_tong: the Tong search has no second step");
+    GC_REQUIRE(conf->samples_per_code >= 1.0f && conf->samples_per_code < 16777216.0f, "gc_acq_create_tong: bad samples_per_code");
+    // the engine's view of the configuration: one block of sampled_ms * samples_per_ms samples per dwell at that transform size, the
+    // grid accumulates until gc_acq_reset(), the decision belongs to the device; a doppler_step of 0 means 250 (the adapters' default)
+    gc_acq_conf c = *conf;
+    if (c.doppler_step == 0) c.doppler_step = 250;
+    c.ms_per_code = c.sampled_ms;
+    c.max_dwells = tong_max_dwells;
+    c.use_CFAR_algorithm_flag = 0;
+    c.num_doppler_bins_step2 = 0;
+    AcqTongParams p;
+    p.threshold = INFINITY;
+    p.init_val = tong_init_val;
+    p.max_val = tong_max_val;
+    p.max_dwells = tong_max_dwells;
+    return acq_create(ctx, &c, n_sats, 0, 0, out, &p);
+}
+
+gc_status gc_acq_tong_set_threshold(gc_acq* a, float threshold)
+{
+    GC_REQUIRE(a, "gc_acq_tong_set_threshold: NULL handle");
+    GC_REQUIRE(a->tong, "gc_acq_tong_set_threshold: not a Tong engine (gc_acq_create_tong)");
+    std::lock_guard<std::mutex> lk(a->ctx->mtx);
+    a->tong_p.threshold = threshold;  // travels with the decision kernel of every later dwell
+    return GC_OK;
+}
+
 gc_status gc_acq_destroy(gc_acq* a)
 {
     if (!a) return GC_OK;
@@ -531,6 +600,7 @@ gc_status gc_acq_set_local_code(gc_acq* a, int sat, const float* code)
 gc_status gc_acq_set_local_code_pair(gc_acq* a, int sat, const float* code_a, const float* code_b)
 {
     GC_REQUIRE(a && code_a && code_b, "gc_acq_set_local_code_pair: NULL argument");
+    GC_REQUIRE(!a->tong, "gc_acq_set_local_code_pair: a Tong engine takes one replica per slot (gc_acq_set_local_code)");
     GC_REQUIRE(a->combine, "gc_acq_set_local_code_pair: not a paired engine (gc_acq_create_paired)");
     GC_REQUIRE(!a->fold, "gc_acq_set_local_code_pair: a QuickSync engine takes one code period per slot (gc_acq_set_local_code)");
     GC_REQUIRE(sat >= 0 && sat < a->n_sats, "gc_acq_set_local_code_pair: satellite slot %d out of range", sat);
@@ -549,6 +619,7 @@ gc_status gc_acq_set_frequency_offset(gc_acq* a, int64_t offset_hz)
 {
     GC_REQUIRE(a, "gc_acq_set_frequency_offset: NULL handle");
     GC_REQUIRE(!a->fold, "gc_acq_set_frequency_offset: the QuickSync search has no frequency offset");
+    GC_REQUIRE(!a->tong, "gc_acq_set_frequency_offset: the Tong search has no frequency offset");
     gc_device_guard g(a->ctx->device);
     std::lock_guard<std::mutex> lk(a->ctx->mtx);
     if (offset_hz == a->freq_offset_hz && a->wipe_valid) return GC_OK;
@@ -572,6 +643,7 @@ gc_status gc_acq_reset(gc_acq* a)
     a->dwell_counter = 0;
     a->grid_logically_zero = true;
     a->inv_pending = false;  // a held-back dwell goes with the grid it would have been added to
+    a->tong_restart = true;  // Tong engine: counters, frozen flags and results restart in front of the next dwell, on its stream
     return GC_OK;
 }
 
@@ -579,6 +651,7 @@ gc_status gc_acq_set_step_two(gc_acq* a, int enable, float doppler_center_hz)
 {
     GC_REQUIRE(a, "gc_acq_set_step_two: NULL handle");
     GC_REQUIRE(!a->fold, "gc_acq_set_step_two: the QuickSync search has no second step");
+    GC_REQUIRE(!a->tong, "gc_acq_set_step_two: the Tong search has no second step");
     gc_device_guard g(a->ctx->device);
     std::lock_guard<std::mutex> lk(a->ctx->mtx);
     hipStream_t st = a->ctx->stream;
@@ -812,6 +885,67 @@ static hipError_t acq_enqueue_quicksync(gc_acq* a, const float2* x, hipStream_t 
     return e;
 }
 
+// one Tong dwell (pcps_tong_acquisition_cc.cc:310-415) of every satellite slot on `st`, x the float block of N samples
+static hipError_t acq_enqueue_tong(gc_acq* a, const float2* x, hipStream_t st)
+{
+    const size_t N = a->fft_size;
+    const int n_bins = (int)a->n_bins;
+    hipError_t e = hipSuccess;
+    if (a->tong_restart)
+        {
+            // set_state(1) / the restart of general_work's state 0 (:230-252, :273-295); the first dwell STORES its cells, so the grid needs no clearing
+            e = acq_tong_launch_restart(st, a->d_tong_state, a->d_tong_frozen, a->d_results, a->n_sats, a->tong_p);
+            if (e != hipSuccess) return e;
+            a->tong_restart = false;
+            a->dwell_counter = 0;
+        }
+    const bool accumulate = a->dwell_counter > 0;
+    a->dwell_counter++;
+    // input power of this block (:325-327), the block row-permuted, FFT(x * wipeoff[bin]) (:336-341)
+    e = acq_launch_input_power(st, x, (int)a->consumed, (int)N, a->d_power, nullptr, 0, 0);
+    if (e == hipSuccess) e = acq_launch_permute(st, x, nullptr, a->d_xw, a->plan, (int)a->consumed, 1, 0, 0, 0);
+    if (e == hipSuccess) e = acq_forward(a, st, 1);
+    // * conj(FFT(code)), IFFT, |.|^2 * s (+=) (:345-360) in batches of satellites.  The row pass computes the cells of frozen satellites
+    // as well; their column workgroups return at once
+    for (int s0 = 0; s0 < a->n_sats && e == hipSuccess; s0 += a->sats_per_batch)
+        {
+            const int ns = std::min(a->sats_per_batch, a->n_sats - s0);
+            e = acq_launch_rows(st, true, a->plan, ns * n_bins, a->d_X, AcqCellMap{1, n_bins}, a->d_codes + (size_t)s0 * N, AcqCellMap{n_bins, 1 << 30}, a->d_Q,
+                a->d_wN2, a->d_wN);
+            if (e != hipSuccess) break;
+            AcqMagArgs m;
+            m.grid = a->d_grid + (size_t)s0 * n_bins * N;
+            m.tmp = nullptr;
+            m.blk_max_val = a->d_blkv + (size_t)s0 * n_bins * a->n_blocks;
+            m.blk_max_idx = a->d_blki + (size_t)s0 * n_bins * a->n_blocks;
+            m.offset = 0;
+            m.eff = (int)a->eff;
+            m.n_bins = n_bins;
+            m.tmp_bin = n_bins - 1;
+            e = acq_launch_cols_tong(st, accumulate, a->plan, ns * n_bins, a->d_Q, m, a->d_tong_frozen + s0, a->d_power);
+        }
+    // maximum, result and decision of every running satellite (:363-415), with every dwell
+    if (e == hipSuccess)
+        {
+            AcqTongDecideArgs d;
+            d.blk_max_val = a->d_blkv;
+            d.blk_max_idx = a->d_blki;
+            d.input_power = a->d_power;
+            d.results = a->d_results;
+            d.state = a->d_tong_state;
+            d.frozen = a->d_tong_frozen;
+            d.n_bins = n_bins;
+            d.n_blocks = a->n_blocks;
+            d.fft_size = (int)N;
+            d.doppler_max = (int)a->conf.doppler_max;
+            d.doppler_step = (int)a->conf.doppler_step;
+            d.samples_per_code = (unsigned)a->conf.samples_per_code;
+            d.p = a->tong_p;
+            e = acq_tong_launch_decide(st, d, a->n_sats);
+        }
+    return e;
+}
+
 // one dwell of every satellite slot on `st`; the caller holds the context mutex
 static gc_status acq_enqueue(gc_acq* a, const void* dev_iq_in, int iq_format, hipStream_t st)
 {
@@ -826,6 +960,13 @@ static gc_status acq_enqueue(gc_acq* a, const void* dev_iq_in, int iq_format, hi
             hipError_t ec = acq_launch_convert(st, iq_format, dev_iq_in, a->d_cvt, (int)a->consumed);
             if (ec != hipSuccess) return gc_fail(GC_ERR_HIP, "gc_acq_dwell: input conversion failed: %s", hipGetErrorString(ec));
             dev_iq = a->d_cvt;
+        }
+    if (a->tong)
+        {
+            const hipError_t et = acq_enqueue_tong(a, dev_iq, st);
+            if (et != hipSuccess) return gc_fail(GC_ERR_HIP, "gc_acq_dwell: kernel launch failed: %s", hipGetErrorString(et));
+            a->grid_logically_zero = false;
+            return GC_OK;
         }
     if (a->fold)
         {
@@ -910,6 +1051,12 @@ gc_status gc_acq_dwell_enqueue(gc_acq* a, const void* dev_iq, void* stream)
 // results of the last dwell to the host; the caller holds the context mutex
 static gc_status acq_fetch(gc_acq* a, gc_acq_result* host_results, hipStream_t st)
 {
+    if (a->tong && a->tong_restart)
+        {
+            // a Tong search that has been reset and not run: the results the restart will write
+            std::memset(host_results, 0, sizeof(gc_acq_result) * a->n_sats);
+            return GC_OK;
+        }
     GC_HIP(acq_flush_inverse(a, st));
     GC_HIP(acq_flush_final(a, st));
     GC_HIP(hipMemcpyAsync(a->h_results, a->d_results, sizeof(gc_acq_result) * a->n_sats, hipMemcpyDeviceToHost, st));
@@ -985,6 +1132,88 @@ gc_status gc_acq_dwell_stream(gc_acq* a, gc_stream* s, uint64_t first_index, gc_
     rs = reads.commit();
     if (rs != GC_OK) return rs;
     return acq_fetch(a, host_results, st);
+}
+
+// {state, tong_count, dwell_count} of every satellite to the host; the caller holds the context mutex
+static gc_status acq_tong_fetch_status(gc_acq* a, struct gc_acq_tong_status* out, hipStream_t st)
+{
+    static_assert(sizeof(struct gc_acq_tong_status) == sizeof(AcqTongState), "gc_acq_tong_status is the device record");
+    if (a->tong_restart)
+        {
+            for (int s = 0; s < a->n_sats; s++)
+                {
+                    out[s].state = GC_ACQ_TONG_RUNNING;
+                    out[s].tong_count = a->tong_p.init_val;
+                    out[s].dwell_count = 0;
+                }
+            return GC_OK;
+        }
+    GC_HIP(hipMemcpyAsync(a->h_tong_state, a->d_tong_state, sizeof(AcqTongState) * a->n_sats, hipMemcpyDeviceToHost, st));
+    GC_HIP(hipStreamSynchronize(st));
+    std::memcpy(out, a->h_tong_state, sizeof(AcqTongState) * a->n_sats);
+    return GC_OK;
+}
+
+gc_status gc_acq_tong_status(gc_acq* a, struct gc_acq_tong_status* out)
+{
+    GC_REQUIRE(a && out, "gc_acq_tong_status: NULL argument");
+    GC_REQUIRE(a->tong, "gc_acq_tong_status: not a Tong engine (gc_acq_create_tong)");
+    gc_device_guard g(a->ctx->device);
+    std::lock_guard<std::mutex> lk(a->ctx->mtx);
+    return acq_tong_fetch_status(a, out, a->ctx->stream);
+}
+
+gc_status gc_acq_tong_search_stream(gc_acq* a, gc_stream* s, uint64_t first_index, uint32_t max_new_dwells, gc_acq_result* host_results,
+    struct gc_acq_tong_status* host_status)
+{
+    GC_REQUIRE(a && s && host_results, "gc_acq_tong_search_stream: NULL argument");
+    GC_REQUIRE(a->tong, "gc_acq_tong_search_stream: not a Tong engine (gc_acq_create_tong)");
+    GC_REQUIRE(s->ctx->device == a->ctx->device, "gc_acq_tong_search_stream: the stream lives on another GPU");
+    GC_REQUIRE(s->iq_format == a->iq_format, "gc_acq_tong_search_stream: stream format %d, acquisition format %d (gc_acq_set_input_format)",
+        s->iq_format, a->iq_format);
+    GC_REQUIRE(a->consumed <= s->mirror, "gc_acq_tong_search_stream: the block of %u samples is longer than the stream's max_window", a->consumed);
+    gc_device_guard g(a->ctx->device);
+    std::lock_guard<std::mutex> lk(a->ctx->mtx);
+    hipStream_t st = a->ctx->stream;
+    const uint32_t done = a->tong_restart ? 0u : a->dwell_counter;
+    const uint32_t left = done < a->tong_p.max_dwells ? a->tong_p.max_dwells - done : 0u;
+    const uint32_t n = std::min(max_new_dwells, left);
+    // all blocks are protected against eviction from here and checked before the first one is enqueued
+    gc_stream_read_set reads(st);
+    gc_status rs = reads.add(s, first_index);
+    if (rs != GC_OK) return rs;
+    const gc_stream_ticket& t = reads.ticket(0);
+    const uint64_t span = (uint64_t)n * a->consumed;
+    if (first_index + span > t.head)
+        return gc_fail(GC_ERR_INVALID, "gc_acq_tong_search_stream: blocks [%llu, +%llu) are not inside the stream's resident samples [%llu, %llu)",
+            (unsigned long long)first_index, (unsigned long long)span, (unsigned long long)t.oldest, (unsigned long long)t.head);
+    // back to back on one stream: no host decision, no synchronisation between the dwells
+    for (uint32_t k = 0; k < n; k++)
+        {
+            const uint64_t at = first_index + (uint64_t)k * a->consumed;
+            rs = acq_enqueue(a, s->d_ring + (at % s->capacity) * s->elem, a->iq_format, st);
+            if (rs != GC_OK) return rs;
+        }
+    rs = reads.commit();
+    if (rs != GC_OK) return rs;
+    rs = acq_fetch(a, host_results, st);
+    if (rs == GC_OK && host_status) rs = acq_tong_fetch_status(a, host_status, st);
+    return rs;
+}
+
+gc_status gc_tong_threshold(float pfa, uint32_t vector_length, uint32_t doppler_max, uint32_t doppler_step, float* out)
+{
+    GC_REQUIRE(out, "gc_tong_threshold: NULL argument");
+    GC_REQUIRE(vector_length >= 1 && doppler_step >= 1, "gc_tong_threshold: bad sizes");
+    // calculate_threshold of the adapters: the bins counted like init() counts them; the quantile of Exp(lambda) in closed form
+    uint32_t bins = 0;
+    for (int64_t d = -(int64_t)doppler_max; d <= (int64_t)doppler_max; d += (int64_t)doppler_step) bins++;
+    const uint32_t ncells = vector_length * bins;
+    const double exponent = 1.0 / (double)ncells;
+    const double val = std::pow(1.0 - pfa, exponent);
+    const double lambda = (double)vector_length;
+    *out = (float)(-std::log(1.0 - val) / lambda);
+    return GC_OK;
 }
 
 gc_status gc_acq_get_grid(gc_acq* a, int sat, float* host_grid)

@@ -305,6 +305,11 @@ API = {
     "gc_acq_quicksync_candidates": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_uint32), _fp]),
     "gc_quicksync_default_folding_factor": (C.c_int, [C.c_uint32, C.POINTER(C.c_uint32)]),
     "gc_quicksync_threshold": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
+    "gc_acq_create_tong": (C.c_int, [_vp, C.POINTER(AcqConf), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(_vp)]),
+    "gc_acq_tong_set_threshold": (C.c_int, [_vp, C.c_float]),
+    "gc_acq_tong_status": (C.c_int, [_vp, _vp]),
+    "gc_acq_tong_search_stream": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp]),
+    "gc_tong_threshold": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
     "gc_cccwsr_replicas": (C.c_int, [_fp, _fp, C.c_uint32, _fp, _fp]),
     "gc_e1_8ms_replicas": (C.c_int, [_fp, C.c_uint32, C.c_uint32, _fp, _fp]),
     "gc_ring_decimator_create": (C.c_int, [_vp, _vp, C.c_uint32, _fp, C.c_uint32, _vp, C.POINTER(_vp)]),
@@ -554,6 +559,21 @@ def quicksync_default_folding_factor(code_length):
     out = C.c_uint32()
     _check(load_library().gc_quicksync_default_folding_factor(int(code_length), C.byref(out)))
     return out.value
+
+
+def tong_threshold(pfa, vector_length, doppler_max, doppler_step):
+    """gc_tong_threshold: calculate_threshold of the Tong adapters."""
+    out = C.c_float()
+    _check(load_library().gc_tong_threshold(float(pfa), int(vector_length), int(doppler_max), int(doppler_step), C.byref(out)))
+    return out.value
+
+
+class AcqTongStatus(C.Structure):
+    """struct gc_acq_tong_status."""
+    _fields_ = [("state", C.c_int32), ("tong_count", C.c_uint32), ("dwell_count", C.c_uint32)]
+
+
+TONG_RUNNING, TONG_POSITIVE, TONG_NEGATIVE = 0, 1, 2
 
 
 def quicksync_threshold(pfa, code_length, folding_factor, doppler_max, doppler_step):
@@ -1186,15 +1206,21 @@ class PcpsAcquisition:
     replicas each (set_local_code_pair) and whose grid cells hold max(a, b) / a + b of the two |.|^2.
     folding_factor = f: the QuickSync engine (gc_acq_create_quicksync, pcps_quicksync_acquisition_cc.cc): fft_size is
     samples_per_code // f, a dwell consumes f * samples_per_code samples, set_local_code takes one code period, candidates(sat)
-    gives the f aliased delays and their time-domain correlations.  It excludes `combine`."""
+    gives the f aliased delays and their time-domain correlations.  It excludes `combine`.
+    tong = (init, max, max_dwells): the Tong engine (gc_acq_create_tong, pcps_tong_acquisition_cc.cc): every dwell adds its
+    power-normalised |.|^2 to the grid and is decided on the device; set_threshold, tong_search_stream and tong_status drive it.  It
+    excludes `combine` and `folding_factor`."""
 
     COMBINE = {"max": 1, "sum": 2}
 
     def __init__(self, ctx, n_sats, fs_in, sampled_ms, ms_per_code, samples_per_ms, samples_per_code, samples_per_chip,
             doppler_max, doppler_step, max_dwells=1, bit_transition_flag=False, use_cfar=True, num_doppler_bins_override=0,
-            make_2_steps=False, num_doppler_bins_step2=4, doppler_step2=125.0, combine=None, folding_factor=None):
+            make_2_steps=False, num_doppler_bins_step2=4, doppler_step2=125.0, combine=None, folding_factor=None, tong=None):
         if folding_factor is not None and combine is not None:
             raise ValueError("folding_factor (the QuickSync engine) excludes combine (the paired engine)")
+        if tong is not None and (combine is not None or folding_factor is not None):
+            raise ValueError("tong (the Tong engine) excludes combine and folding_factor")
+        self.tong = None if tong is None else tuple(int(v) for v in tong)
         self._ctx = ctx
         self.n_sats = n_sats
         self.combine = combine
@@ -1204,7 +1230,11 @@ class PcpsAcquisition:
             int(make_2_steps), num_doppler_bins_step2, doppler_step2)
         self.conf = conf
         self._h = _vp()
-        if folding_factor is not None:
+        if self.tong is not None:
+            if len(self.tong) != 3 or not all(0 <= v < 2 ** 32 for v in self.tong):
+                raise GnsscorrError(GC_ERR_INVALID, "tong = (init, max, max_dwells), got %r" % (tong,))
+            _check(load_library().gc_acq_create_tong(ctx._h, C.byref(conf), n_sats, self.tong[0], self.tong[1], self.tong[2], C.byref(self._h)))
+        elif folding_factor is not None:
             if not 0 <= int(folding_factor) < 2 ** 32:
                 raise GnsscorrError(GC_ERR_INVALID, "folding factor %r out of range" % (folding_factor,))
             _check(load_library().gc_acq_create_quicksync(ctx._h, C.byref(conf), n_sats, int(folding_factor), C.byref(self._h)))
@@ -1280,6 +1310,25 @@ class PcpsAcquisition:
         g = np.zeros((self.num_doppler_bins, self.fft_size), np.float32)
         _check(load_library().gc_acq_get_grid(self._h, sat, _f32p(g)))
         return g
+
+    def set_threshold(self, threshold):
+        """gc_acq_tong_set_threshold (Tong engine): used by the decisions of the dwells enqueued afterwards."""
+        _check(load_library().gc_acq_tong_set_threshold(self._h, float(threshold)))
+
+    def tong_status(self):
+        """gc_acq_tong_status: a list of AcqTongStatus (state, tong_count, dwell_count), one per satellite."""
+        st = (AcqTongStatus * self.n_sats)()
+        _check(load_library().gc_acq_tong_status(self._h, C.cast(st, _vp)))
+        return list(st)
+
+    def tong_search_stream(self, ring, first_index, max_new_dwells=None):
+        """gc_acq_tong_search_stream: up to max_new_dwells (default: all that are left of tong_max_dwells) dwells on consecutive
+        blocks of the ring, back to back, one fetch.  Returns (results, status)."""
+        res = (AcqResult * self.n_sats)()
+        st = (AcqTongStatus * self.n_sats)()
+        n = 0xFFFFFFFF if max_new_dwells is None else int(max_new_dwells)
+        _check(load_library().gc_acq_tong_search_stream(self._h, ring._h, int(first_index), n, C.cast(res, _vp), C.cast(st, _vp)))
+        return list(res), list(st)
 
     def candidates(self, sat):
         """gc_acq_quicksync_candidates: (possible_delay uint32[f], corr_output_f float32[f]) of the last dwell (QuickSync engine)."""

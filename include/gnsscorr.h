@@ -811,6 +811,52 @@ gc_status gc_quicksync_default_folding_factor(uint32_t code_length, uint32_t* ou
 /* The adapters' calculate_threshold: ncells = (code_length / folding_factor) * bins (integer division, bins counted inclusively),
  * lambda = code_length / (double)folding_factor, threshold = -log(1 - pow(1 - pfa, 1 / ncells)) / lambda. */
 gc_status gc_quicksync_threshold(float pfa, uint32_t code_length, uint32_t folding_factor, uint32_t doppler_max, uint32_t doppler_step, float* out);
+/* Tong engine (pcps_tong_acquisition_cc.cc): the reference's variable-dwell sequential detector.  With N = sampled_ms * samples_per_ms
+ * (the transform size: no zero padding, no bit transition; gc_acq_set_local_code takes N complex samples), every dwell adds
+ *   grid[b][k] += |IFFT(FFT(x * wipeoff[b]) * conj(FFT(code)))[k]|^2 * s,   s = 1 / (fnf * fnf * P),  fnf = (float)N * (float)N,
+ * P = mean |x|^2 of THIS dwell's block, all in float32, the product rounded before it is added (:310-360; the first dwell of a search
+ * stores).  Then, per satellite and ON THE DEVICE: d_mag = the largest cell (rows ascending, the first maximum of a row, a later row
+ * only with a strictly larger value, nothing wins against 0 or with NaN, :363-375), and the decision (:393-415)
+ *   dwell_count++;  if d_mag > threshold * dwell_count (float32): tong_count++, positive when it equals tong_max_val
+ *                   else:                                          tong_count--, negative when it reaches 0
+ *                   dwell_count >= tong_max_dwells: negative, also over a positive of the same dwell
+ * from tong_count = tong_init_val.  A satellite that has decided is FROZEN: later dwells leave its grid, its row maxima
+ * (GC_ACQ_PEEK_ROW_MAX), its gc_acq_result and its status as its deciding dwell left them, and their column pass moves no data for it.
+ *   Doppler bins    -doppler_max + b doppler_step for every value <= +doppler_max (inclusive: 41 bins for 5000 / 250, :200-205); a
+ *                   doppler_step of 0 means 250; num_doppler_bins_override as in gc_acq_create
+ *   conf fields     fs_in, sampled_ms, samples_per_ms, samples_per_code, doppler_max, doppler_step, num_doppler_bins_override
+ *   GC_ERR_INVALID  unless 1 <= tong_init_val < tong_max_val and tong_max_dwells >= 1; bit_transition_flag or make_2_steps set
+ * On such a handle gc_acq_fft_size reports N, N and the inclusive bin count; every dwell call (gc_acq_dwell, _dev, _enqueue, _stream) runs
+ * ONE Tong dwell, decision included -- dwells are never held back for one another; gc_acq_reset starts a new search (counters back to
+ * their initial values, nothing frozen, the grid reads as zero); gc_acq_get_grid gives the normalised grid; gc_acq_set_step_two,
+ * gc_acq_set_frequency_offset and gc_acq_set_local_code_pair return GC_ERR_INVALID.
+ * gc_acq_result: mag = test_statistics = d_mag, input_power = P of the dwell, indext / doppler_index / doppler_hz / acq_doppler_hz of
+ * d_mag's cell, acq_delay_samples = indext % (uint32_t)samples_per_code (integer, :371), both second_peak fields 0.  A dwell in which no
+ * cell wins (P = 0) keeps the cell fields of the dwell before it (zero at the start of a search), as Gnss_Synchro does. */
+gc_status gc_acq_create_tong(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, uint32_t tong_init_val, uint32_t tong_max_val, uint32_t tong_max_dwells,
+    gc_acq** out);
+/* d_threshold: one per engine, used by the decisions of the dwells enqueued after the call.  Default +inf: every dwell counts down. */
+gc_status gc_acq_tong_set_threshold(gc_acq* a, float threshold);
+enum { GC_ACQ_TONG_RUNNING = 0, GC_ACQ_TONG_POSITIVE = 1, GC_ACQ_TONG_NEGATIVE = 2 };
+/* Per satellite (the struct tag shares its name with the call below: write `struct gc_acq_tong_status`). */
+struct gc_acq_tong_status
+{
+    int32_t state;        /* GC_ACQ_TONG_RUNNING / _POSITIVE / _NEGATIVE */
+    uint32_t tong_count;  /* d_tong_count */
+    uint32_t dwell_count; /* the dwell that decided, or the last dwell run */
+};
+/* The status of all n_sats satellites (synchronises the context stream). */
+gc_status gc_acq_tong_status(gc_acq* a, struct gc_acq_tong_status* out /* n_sats */);
+/* Enqueues min(max_new_dwells, tong_max_dwells - dwells so far in this search) dwells on consecutive blocks of N samples of the ring,
+ * the first at absolute sample first_index, back to back on the context stream: no host decision and no synchronisation between
+ * them, one fetch of results (n_sats) and status (n_sats, may be NULL) at the end.  A second call continues the search where the
+ * first stopped.  A ring that does not hold all those samples is refused like gc_acq_dwell_stream refuses its block, before
+ * anything is enqueued. */
+gc_status gc_acq_tong_search_stream(gc_acq* a, gc_stream* ring, uint64_t first_index, uint32_t max_new_dwells, gc_acq_result* host_results,
+    struct gc_acq_tong_status* host_status);
+/* The Tong adapters' calculate_threshold in closed form: ncells = vector_length * bins (bins counted inclusively), lambda = vector_length,
+ * threshold = quantile(Exp(lambda), (1 - pfa)^(1 / ncells)) = -log(1 - (1 - pfa)^(1 / ncells)) / lambda. */
+gc_status gc_tong_threshold(float pfa, uint32_t vector_length, uint32_t doppler_max, uint32_t doppler_step, float* out);
 /* Inspection of the engine's device-resident intermediates (tests, failure dumps; synchronises the context stream; natural element
  * order whatever the layout in HBM).  `what`:
  *   GC_ACQ_PEEK_WIPEOFF   index = Doppler bin: the wipe-off row exp(-j phase) of the ACTIVE grid, d_grid_doppler_wipeoffs[bin]
