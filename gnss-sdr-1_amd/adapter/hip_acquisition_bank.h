@@ -20,6 +20,14 @@
  * cccwsr (Galileo E1 "1B" only): every satellite is searched on BOTH components the way pcps_cccwsr_acquisition_cc does (:316-370,
  * data and pilot correlations combined as d + jp and d - jp, the larger wins) -- a paired MAX engine (gc_acq_create_paired) whose slots
  * hold gc_cccwsr_replicas(E1-B, E1-C); statistic, threshold and result mapping stay those of the one-replica search.
+ *
+ * fine_doppler: after a search the detections -- and only they -- are refined in ONE call of the fine Doppler stage
+ * (gc_fine_doppler_estimate_stream, the estimate_Doppler of pcps_acquisition_fine_doppler_cc): on the ring the search read and at
+ * that ring's rate, over the 10 code periods that begin at the first dwell's first sample, zero padding 8, with
+ * GC_FINE_ALIGN_EXACT.  Acq_doppler_hz becomes the fine value (fs / (80 samples per code): 12.5 Hz for a 1 ms code) unless the stage
+ * reports GC_FINE_EDGE; fine_result() gives the stage's record.  The ring must hold those 10 code periods: when it does not (or the
+ * stage fails otherwise) the detections keep their coarse Doppler and last_status() is the stage's error.  With the flag off
+ * nothing changes.
  */
 #ifndef GNSSCORR_HIP_ACQUISITION_BANK_H_
 #define GNSSCORR_HIP_ACQUISITION_BANK_H_
@@ -40,7 +48,7 @@ public:
      *  doppler_max / doppler_step [Hz]; threshold on the block's statistic (pcps_acquisition.cc:565-665); max_dwells non-coherent dwells */
     hip_acquisition_bank(gc_ctx* ctx, gc_stream* ring, char system, const std::string& signal, const std::vector<uint32_t>& prns, int64_t fs_in, uint32_t doppler_max,
         uint32_t doppler_step, float threshold, uint32_t max_dwells = 1, bool use_cfar = true, int iq_format = GC_IQ_F32, bool use_acquisition_resampler = false,
-        bool cccwsr = false)
+        bool cccwsr = false, bool fine_doppler = false)
         : d_ring(ring), d_acq_ring(ring), d_system(system), d_signal(signal), d_prns(prns), d_threshold(threshold), d_max_dwells(std::max(1u, max_dwells))
     {
         double code_rate = 1.023e6, code_len = 1023.0;
@@ -107,6 +115,20 @@ public:
                 d_acq_ring = d_resampler->ring();
             }
         d_samples_per_code = static_cast<uint32_t>(std::floor(static_cast<double>(fs_in) / (code_rate / code_len)));
+        if (fine_doppler)
+            {
+                gc_fine_doppler_conf f;
+                std::memset(&f, 0, sizeof f);
+                f.fs_in = fs_in;
+                f.samples_per_code = d_samples_per_code;
+                f.prn_replicas = 10;
+                f.zero_padding_factor = 8;
+                f.window_hz = 1000.0f;
+                f.alignment = GC_FINE_ALIGN_EXACT;
+                d_status = gc_fine_doppler_create(ctx, &f, static_cast<int>(prns.size()), &d_fine);
+                if (d_status != GC_OK) return;
+                d_fine_results.resize(prns.size());
+            }
         // replicas: one code period at fs, tiled over the coherent time (the adapters' set_local_code)
         std::vector<float> one(2 * (d_samples_per_code + 16)), tiled(2 * static_cast<size_t>(consumed));
         std::vector<float> pilot, rep_a, rep_b;
@@ -126,6 +148,8 @@ public:
                         tiled[2 * i] = one[2 * (i % d_samples_per_code)];
                         tiled[2 * i + 1] = one[2 * (i % d_samples_per_code) + 1];
                     }
+                if (d_fine) d_status = gc_fine_doppler_set_code(d_fine, static_cast<int>(s), one.data());
+                if (d_status != GC_OK) return;
                 if (!cccwsr)
                     {
                         d_status = gc_acq_set_local_code(d_acq, static_cast<int>(s), tiled.data());
@@ -147,6 +171,7 @@ public:
     ~hip_acquisition_bank()
     {
         if (d_acq) gc_acq_destroy(d_acq);
+        if (d_fine) gc_fine_doppler_destroy(d_fine);
     }
     hip_acquisition_bank(const hip_acquisition_bank&) = delete;
     hip_acquisition_bank& operator=(const hip_acquisition_bank&) = delete;
@@ -194,6 +219,7 @@ public:
         for (size_t s = 0; s < d_prns.size(); s++)
             if (d_results[s].test_statistics > d_threshold) order.push_back(s);
         std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return d_results[a].test_statistics > d_results[b].test_statistics; });
+        if (d_fine) refine(first_index, order);
         for (size_t s : order)
             {
                 Gnss_Synchro g;
@@ -222,6 +248,12 @@ public:
         return found;
     }
 
+    //! fine_doppler: the stage's record of satellite `sat` in the last search (status 0: not detected, or the stage did not run)
+    const gc_fine_doppler_result& fine_result(size_t sat) const
+    {
+        static const gc_fine_doppler_result none{};
+        return sat < d_fine_results.size() ? d_fine_results[sat] : none;
+    }
     //! the statistic of every searched satellite in the last search (same order as `prns`)
     float statistic(size_t sat) const { return d_results[sat].test_statistics; }
     gc_status last_status() const { return d_status; }
@@ -230,11 +262,37 @@ public:
     uint32_t resampler_latency_samples() const { return d_latency; }
 
 private:
+    // the detections `order` of the search that began at first_index of the searched ring, in one call; acq_doppler_hz of d_results
+    // is replaced where the stage refined
+    void refine(uint64_t first_index, const std::vector<size_t>& order)
+    {
+        for (auto& r : d_fine_results) std::memset(&r, 0, sizeof r);
+        if (order.empty()) return;
+        std::vector<gc_fine_doppler_request> req(order.size());
+        std::vector<gc_fine_doppler_result> res(order.size());
+        for (size_t i = 0; i < order.size(); i++)
+            {
+                const gc_acq_result& r = d_results[order[i]];
+                req[i].slot = static_cast<uint32_t>(order[i]);
+                req[i].delay_samples = static_cast<uint32_t>(r.acq_delay_samples) % d_samples_per_code;
+                req[i].coarse_doppler_hz = r.acq_doppler_hz;
+            }
+        d_status = gc_fine_doppler_estimate_stream(d_fine, d_acq_ring, first_index, req.data(), static_cast<int>(req.size()), res.data());
+        if (d_status != GC_OK) return;
+        for (size_t i = 0; i < order.size(); i++)
+            {
+                d_fine_results[order[i]] = res[i];
+                if (res[i].status == GC_FINE_REFINED) d_results[order[i]].acq_doppler_hz = res[i].doppler_hz;
+            }
+    }
+
     gc_stream* d_ring;
     gc_stream* d_acq_ring;            // the ring the dwells read: d_ring, or the resampler's derived ring
     std::unique_ptr<hip_ring_decimator> d_resampler;
     uint32_t d_ratio = 1, d_latency = 0;
     gc_acq* d_acq = nullptr;
+    gc_fine_doppler* d_fine = nullptr;
+    std::vector<gc_fine_doppler_result> d_fine_results;
     bool d_ready = false;  // construction went through (every replica installed)
     char d_system;
     std::string d_signal;

@@ -11,6 +11,8 @@
  *   GpsL2MPcpsAcquisition, GpsL5iPcpsAcquisition, GalileoE5aPcpsAcquisition, BeidouB3iPcpsAcquisition (same directory)
  *   GalileoE1PcpsCccwsrAmbiguousAcquisition, GalileoE1Pcps8msAmbiguousAcquisition (same directory): both E1 components, or both sign
  *   hypotheses of an 8 ms replica, in one search -- backed by hip_pcps_paired_acquisition (at the end of this file)
+ *   GpsL1CaPcpsAcquisitionFineDoppler (same directory): the search that ends in a 12.5 Hz Doppler estimate -- backed by
+ *   hip_pcps_acquisition_fine_doppler (at the end of this file)
  * (item_type gr_complex only; `dump` / `dump_filename` / `dump_channel` write the reference's .mat
  * variables, see hip_pcps_acquisition::dump_results; the acquisition resampler and the GNU Radio
  * connect()/get_left_block() plumbing are outside this path).  Registration in a GNSS-SDR tree is one
@@ -22,6 +24,7 @@
 
 #include "hip_pcps_acquisition.h"
 #include "hip_pcps_paired_acquisition.h"
+#include "hip_pcps_acquisition_fine_doppler.h"
 #include <cmath>
 #include <memory>
 #include <string>
@@ -493,5 +496,102 @@ private:
 
 using GalileoE1PcpsCccwsrAmbiguousAcquisitionHip = GalileoE1PairedAcquisitionHip<hip_pcps_paired_acquisition::CCCWSR>;
 using GalileoE1Pcps8msAmbiguousAcquisitionHip = GalileoE1PairedAcquisitionHip<hip_pcps_paired_acquisition::E1_8MS>;
+
+/*! GpsL1CaPcpsAcquisitionFineDoppler (gps_l1_ca_pcps_acquisition_fine_doppler.cc:44-189) over hip_pcps_acquisition_fine_doppler.  Keys:
+ *  doppler_max (5000), coherent_integration_time_ms (1; read and, as in the reference, not used by the block), max_dwells (1), dump,
+ *  dump_filename ("./acquisition.mat"), blocking_on_standby (false); doppler_step and threshold come through the interface.
+ *  vector_length = round(fs / (1.023e6 / 1023)) = samples_per_ms; the local code is one sampled code period. */
+class GpsL1CaPcpsAcquisitionFineDopplerHip : public AcquisitionInterface
+{
+public:
+    GpsL1CaPcpsAcquisitionFineDopplerHip(ConfigurationInterface* configuration, const std::string& role, unsigned int in_streams, unsigned int out_streams)
+        : role_(role), in_streams_(in_streams), out_streams_(out_streams)
+    {
+        item_type_ = configuration->property(role + ".item_type", std::string("gr_complex"));
+        int64_t fs_in_deprecated = configuration->property("GNSS-SDR.internal_fs_hz", static_cast<int64_t>(2048000));
+        fs_in_ = configuration->property("GNSS-SDR.internal_fs_sps", fs_in_deprecated);
+        dump_ = configuration->property(role + ".dump", false);
+        dump_filename_ = configuration->property(role + ".dump_filename", std::string("./acquisition.mat"));
+        doppler_max_ = configuration->property(role + ".doppler_max", 5000);
+        sampled_ms_ = configuration->property(role + ".coherent_integration_time_ms", 1);
+        max_dwells_ = configuration->property(role + ".max_dwells", 1);
+        blocking_on_standby_ = configuration->property(role + ".blocking_on_standby", false);
+        vector_length_ = static_cast<unsigned int>(std::round(static_cast<double>(fs_in_) / (1.023e6 / 1023.0)));
+        acquisition_ = std::make_shared<hip_pcps_acquisition_fine_doppler>(max_dwells_, doppler_max_, fs_in_, static_cast<int32_t>(vector_length_), blocking_on_standby_, dump_,
+            dump_filename_);
+    }
+
+    std::string role() override { return role_; }
+    std::string implementation() override { return "GPS_L1_CA_PCPS_Acquisition_Fine_Doppler_HIP"; }
+    size_t item_size() override { return sizeof(gr_complex); }
+
+    void set_gnss_synchro(Gnss_Synchro* p_gnss_synchro) override
+    {
+        gnss_synchro_ = p_gnss_synchro;
+        acquisition_->set_gnss_synchro(gnss_synchro_);
+    }
+    void set_channel(unsigned int channel) override
+    {
+        channel_ = channel;
+        acquisition_->set_channel(channel_);
+    }
+    void set_channel_fsm(std::shared_ptr<ChannelFsm> channel_fsm) override { channel_fsm_ = channel_fsm; }
+    void set_threshold(float threshold) override
+    {
+        threshold_ = threshold;
+        acquisition_->set_threshold(threshold_);
+    }
+    void set_doppler_max(unsigned int doppler_max) override
+    {
+        doppler_max_ = doppler_max;
+        acquisition_->set_doppler_max(doppler_max_);
+    }
+    void set_doppler_step(unsigned int doppler_step) override
+    {
+        doppler_step_ = doppler_step;
+        acquisition_->set_doppler_step(doppler_step_);
+    }
+    void init() override { acquisition_->init(); }
+    void set_local_code() override
+    {
+        std::vector<gr_complex> code(vector_length_ + 8);
+        gc_gps_l1_ca_code_gen_complex_sampled(reinterpret_cast<float*>(code.data()), gnss_synchro_->PRN, static_cast<int32_t>(fs_in_), 0, nullptr);
+        acquisition_->set_local_code(code.data());
+    }
+    void set_state(int state) override { acquisition_->set_state(state); }
+    signed int mag() override { return static_cast<signed int>(acquisition_->mag()); }
+    void reset() override { acquisition_->set_active(true); }
+    void stop_acquisition() override {}
+    void set_resampler_latency(uint32_t) override {}
+
+    std::shared_ptr<hip_pcps_acquisition_fine_doppler> block() { return acquisition_; }
+    unsigned int vector_length() const { return vector_length_; }
+    unsigned int doppler_max() const { return doppler_max_; }
+    unsigned int sampled_ms() const { return sampled_ms_; }
+    unsigned int max_dwells() const { return max_dwells_; }
+    bool blocking_on_standby() const { return blocking_on_standby_; }
+    bool dump() const { return dump_; }
+    const std::string& dump_filename() const { return dump_filename_; }
+    float threshold() const { return threshold_; }
+
+private:
+    std::shared_ptr<hip_pcps_acquisition_fine_doppler> acquisition_;
+    std::string item_type_;
+    std::string role_;
+    std::string dump_filename_;
+    unsigned int in_streams_;
+    unsigned int out_streams_;
+    unsigned int vector_length_ = 0;
+    unsigned int channel_ = 0;
+    unsigned int doppler_max_ = 0;
+    unsigned int doppler_step_ = 0;
+    unsigned int sampled_ms_ = 1;
+    unsigned int max_dwells_ = 1;
+    bool dump_ = false, blocking_on_standby_ = false;
+    float threshold_ = 0.0f;
+    int64_t fs_in_ = 0;
+    std::shared_ptr<ChannelFsm> channel_fsm_;
+    Gnss_Synchro* gnss_synchro_ = nullptr;
+};
 
 #endif  // GNSSCORR_PCPS_ACQUISITION_ADAPTERS_H_

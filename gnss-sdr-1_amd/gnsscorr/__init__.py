@@ -310,6 +310,14 @@ API = {
     "gc_acq_tong_status": (C.c_int, [_vp, _vp]),
     "gc_acq_tong_search_stream": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp]),
     "gc_tong_threshold": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
+    "gc_fine_doppler_create": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(_vp)]),
+    "gc_fine_doppler_destroy": (C.c_int, [_vp]),
+    "gc_fine_doppler_set_code": (C.c_int, [_vp, C.c_int, _fp]),
+    "gc_fine_doppler_estimate_stream": (C.c_int, [_vp, _vp, C.c_uint64, _vp, C.c_int, _vp]),
+    "gc_fine_doppler_estimate": (C.c_int, [_vp, _fp, _vp, C.c_int, _vp]),
+    "gc_fine_doppler_spectrum": (C.c_int, [_vp, C.c_int, _fp]),
+    "gc_fine_doppler_window": (C.c_int, [C.c_int64, C.c_uint32, C.c_double, C.c_double, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "gc_fine_doppler_conf_size": (C.c_size_t, []),
     "gc_cccwsr_replicas": (C.c_int, [_fp, _fp, C.c_uint32, _fp, _fp]),
     "gc_e1_8ms_replicas": (C.c_int, [_fp, C.c_uint32, C.c_uint32, _fp, _fp]),
     "gc_ring_decimator_create": (C.c_int, [_vp, _vp, C.c_uint32, _fp, C.c_uint32, _vp, C.POINTER(_vp)]),
@@ -365,6 +373,9 @@ def load_library():
         if lib.gc_resampler_conf_size() != C.sizeof(ResamplerConf):
             raise GnsscorrError(GC_ERR_INVALID, "gc_resampler_conf is %d bytes in the library, %d here -- rebuild with __graft_entry__.build()"
                 % (lib.gc_resampler_conf_size(), C.sizeof(ResamplerConf)))
+        if lib.gc_fine_doppler_conf_size() != C.sizeof(FineDopplerConf):
+            raise GnsscorrError(GC_ERR_INVALID, "gc_fine_doppler_conf is %d bytes in the library, %d here -- rebuild with __graft_entry__.build()"
+                % (lib.gc_fine_doppler_conf_size(), C.sizeof(FineDopplerConf)))
         _lib = lib
     return _lib
 
@@ -574,6 +585,35 @@ class AcqTongStatus(C.Structure):
 
 
 TONG_RUNNING, TONG_POSITIVE, TONG_NEGATIVE = 0, 1, 2
+
+
+class FineDopplerConf(C.Structure):
+    """gc_fine_doppler_conf."""
+    _fields_ = [("fs_in", C.c_int64), ("samples_per_code", C.c_uint32), ("prn_replicas", C.c_uint32), ("zero_padding_factor", C.c_uint32),
+        ("window_hz", C.c_float), ("alignment", C.c_int32)]
+
+
+class FineDopplerRequest(C.Structure):
+    """gc_fine_doppler_request."""
+    _fields_ = [("slot", C.c_uint32), ("delay_samples", C.c_uint32), ("coarse_doppler_hz", C.c_double)]
+
+
+class FineDopplerResult(C.Structure):
+    """gc_fine_doppler_result."""
+    _fields_ = [("doppler_hz", C.c_double), ("bin", C.c_uint32), ("status", C.c_int32), ("peak", C.c_float), ("mean", C.c_float),
+        ("window_first_bin", C.c_uint32), ("window_bins", C.c_uint32)]
+
+
+FINE_ALIGN_REFERENCE, FINE_ALIGN_EXACT = 0, 1
+FINE_REFINED, FINE_EDGE = 1, 2
+
+
+def fine_doppler_window(fs_in, next_size, coarse_hz, window_hz=1000.0):
+    """gc_fine_doppler_window: (first_bin, bins), the circular run of {k : |f[k] - coarse_hz| < window_hz} of the block's float32
+    frequency table of next_size entries.  Host rule, no device."""
+    a, b = C.c_uint32(), C.c_uint32()
+    _check(load_library().gc_fine_doppler_window(int(fs_in), int(next_size), float(coarse_hz), float(window_hz), C.byref(a), C.byref(b)))
+    return a.value, b.value
 
 
 def quicksync_threshold(pfa, code_length, folding_factor, doppler_max, doppler_step):
@@ -1354,6 +1394,78 @@ class PcpsAcquisition:
     def close(self):
         if self._h:
             load_library().gc_acq_destroy(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FineDoppler:
+    """gc_fine_doppler: the fine Doppler stage of pcps_acquisition_fine_doppler_cc -- the Doppler of acquired satellites to
+    fs_in / (prn_replicas * zero_padding_factor * samples_per_code) from prn_replicas code periods, the code-wiped spectrum evaluated at
+    the bins within window_hz of each coarse value only.  alignment: "reference" (the block's std::rotate, one element short) or
+    "exact".  A request is (slot, delay_samples, coarse_doppler_hz)."""
+    ALIGNMENT = {"reference": FINE_ALIGN_REFERENCE, "exact": FINE_ALIGN_EXACT}
+
+    def __init__(self, ctx, n_slots, fs_in, samples_per_code, prn_replicas=10, zero_padding_factor=8, window_hz=1000.0, alignment="reference"):
+        self._h = _vp()
+        self._ctx = ctx
+        self.n_slots = int(n_slots)
+        # an unknown name reaches the library as an unknown alignment: GC_ERR_INVALID
+        self.conf = FineDopplerConf(int(fs_in), int(samples_per_code), int(prn_replicas), int(zero_padding_factor), float(window_hz),
+            self.ALIGNMENT.get(alignment, -1))
+        self.block_samples = int(samples_per_code) * int(prn_replicas)
+        self.next_size = self.block_samples * int(zero_padding_factor)
+        _check(load_library().gc_fine_doppler_create(ctx._h if ctx is not None else None, C.byref(self.conf), self.n_slots, C.byref(self._h)))
+        self._last_bins = []
+
+    def set_code(self, slot, code):
+        code = np.ascontiguousarray(code, np.complex64)
+        assert code.size == self.conf.samples_per_code, (code.size, self.conf.samples_per_code)
+        _check(load_library().gc_fine_doppler_set_code(self._h, int(slot), _c64p(code)))
+
+    @staticmethod
+    def _requests(requests):
+        req = (FineDopplerRequest * max(len(requests), 1))()
+        for i, (slot, delay, coarse) in enumerate(requests):
+            req[i] = FineDopplerRequest(int(slot), int(delay), float(coarse))
+        return req
+
+    def _done(self, res, n):
+        out = list(res)[:n]
+        self._last_bins = [r.window_bins for r in out]
+        return out
+
+    def estimate_stream(self, ring, first_index, requests):
+        """gc_fine_doppler_estimate_stream: a list of FineDopplerResult, one per request."""
+        req = self._requests(requests)
+        res = (FineDopplerResult * max(len(requests), 1))()
+        _check(load_library().gc_fine_doppler_estimate_stream(self._h, ring._h, int(first_index), C.cast(req, _vp), len(requests), C.cast(res, _vp)))
+        return self._done(res, len(requests))
+
+    def estimate(self, iq, requests):
+        """gc_fine_doppler_estimate on block_samples complex64 samples in host memory."""
+        iq = np.ascontiguousarray(iq, np.complex64)
+        assert iq.size >= self.block_samples, (iq.size, self.block_samples)
+        req = self._requests(requests)
+        res = (FineDopplerResult * max(len(requests), 1))()
+        _check(load_library().gc_fine_doppler_estimate(self._h, _c64p(iq), C.cast(req, _vp), len(requests), C.cast(res, _vp)))
+        return self._done(res, len(requests))
+
+    def spectrum(self, request_index):
+        """gc_fine_doppler_spectrum: p over the window of a request of the last call, window_bins float32 in run order."""
+        if not 0 <= request_index < len(self._last_bins):
+            raise GnsscorrError(GC_ERR_INVALID, "request %d of %d in the last call" % (request_index, len(self._last_bins)))
+        out = np.zeros(self._last_bins[request_index], np.float32)
+        _check(load_library().gc_fine_doppler_spectrum(self._h, int(request_index), _f32p(out)))
+        return out
+
+    def close(self):
+        if self._h:
+            load_library().gc_fine_doppler_destroy(self._h)
             self._h = _vp()
 
     def __del__(self):

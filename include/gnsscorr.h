@@ -1008,6 +1008,84 @@ gc_status gc_ring_resampler_info(gc_ring_resampler* r, uint64_t* src_consumed, u
  * power of two in 1..256.  bank may be NULL to ask for T alone.  GC_ERR_INVALID when T > 1024 or P T > 8192, and when P T > capacity. */
 gc_status gc_resampler_design(double fs_in, double fs_out, uint32_t phases, float* bank, int capacity, int* taps_per_phase);
 
+/* ------------------------------------------------------------------------ */
+/* Fine Doppler stage (pcps_acquisition_fine_doppler_cc.cc:400-479): the Doppler */
+/* of an acquired satellite to fs / (P Z N) -- 12.5 Hz for a 1 ms code, P = 10,   */
+/* Z = 8 -- from the P code periods the ring already holds.  It refines the       */
+/* result of any engine above (plain, paired, QuickSync, Tong).                  */
+/* ------------------------------------------------------------------------ */
+/* With N = samples_per_code, P = prn_replicas, Z = zero_padding_factor, Next = P N Z, x[0 .. P N) the samples from first_index on,
+ * s = delay_samples and fc = coarse_doppler_hz the block does
+ *   r'           the code rotated by std::rotate(r, r + (N - s), r + N - 1) when s != 0 (:405-409).  The last iterator leaves the final
+ *                element in place: r'[i] = code[N - s + i] for i < s - 1, code[i - (s - 1)] for s - 1 <= i < N - 1, code[N - 1] for
+ *                i = N - 1.  GC_FINE_ALIGN_REFERENCE is that; GC_FINE_ALIGN_EXACT is r'[i] = code[(i - s) mod N]
+ *   y[n]         x[n] r'[n mod N] for n < P N, zero up to Next
+ *   p[k]         |sum_n y[n] exp(-j 2 pi k n / Next)|^2, and k* the first largest p[k] in array order
+ *   f[k]         float32, from double arithmetic on float32 operands: ((float)fs / 2.0 * (float)k) / ((float)Next / 2.0) for
+ *                k < Next / 2, (-(float)fs / 2.0 * (float)(Next - k)) / ((float)Next / 2.0) above
+ *   acceptance   |f[k*] - fc| < 1000 in double: Acq_doppler_hz = f[k*], else the coarse value stays
+ * Here only the bins that can be accepted are computed, as a direct sum: the window {k : |(double)f[k] - fc| < window_hz}, one
+ * circular run (window_first_bin, window_bins) of array indices in ascending frequency (it may cross from index Next - 1 to 0, never
+ * Nyquist).  The twiddle phase is always 2 pi ((k n) mod Next) / Next of an integer reduced in 64 bits; products and sums are float32
+ * in an order that depends on the request and the samples alone, so a result's bits do not depend on the other requests of a call,
+ * on the ring's format or on where the block lies in the ring.
+ * DEVIATION: the block looks at the whole spectrum and keeps the coarse value when its maximum lies window_hz or more away; that
+ * maximum is never computed here.  The window's maximum is returned with peak, mean (sum |y|^2 = the mean of p over all Next bins, by
+ * Parseval: judge the peak against it) and GC_FINE_EDGE when the winner is the window's first or last bin in frequency order, which is
+ * what a maximum outside the window looks like from inside. */
+enum { GC_FINE_ALIGN_REFERENCE = 0, GC_FINE_ALIGN_EXACT = 1 };
+enum { GC_FINE_REFINED = 1, GC_FINE_EDGE = 2 };
+typedef struct gc_fine_doppler_conf
+{
+    int64_t fs_in;
+    uint32_t samples_per_code;    /* N */
+    uint32_t prn_replicas;        /* P, 1..50 (the block: 10) */
+    uint32_t zero_padding_factor; /* Z, 1..16 (the block: 8) */
+    float window_hz;              /* the block: 1000 */
+    int32_t alignment;            /* GC_FINE_ALIGN_REFERENCE / _EXACT */
+} gc_fine_doppler_conf;
+typedef struct gc_fine_doppler_request
+{
+    uint32_t slot;          /* whose code (gc_fine_doppler_set_code) */
+    uint32_t delay_samples; /* s < N */
+    double coarse_doppler_hz;
+} gc_fine_doppler_request;
+typedef struct gc_fine_doppler_result
+{
+    double doppler_hz; /* (double)f[bin], also with GC_FINE_EDGE */
+    uint32_t bin;      /* k*, the first largest p[k] of the window in array-index order */
+    int32_t status;    /* GC_FINE_REFINED / GC_FINE_EDGE */
+    float peak;        /* p[bin] */
+    float mean;        /* sum |y[n]|^2 */
+    uint32_t window_first_bin, window_bins;
+} gc_fine_doppler_result;
+typedef struct gc_fine_doppler gc_fine_doppler;
+/* GC_ERR_INVALID, before anything touches a device: NULL arguments, n_slots < 1, fs_in < 1, N = 0, P outside 1..50, Z outside 1..16,
+ * Next odd or above 2^24 (the table casts k to float), a window that is not finite and positive or reaches fs_in / 2, an unknown
+ * alignment, a window of more than 8192 bins. */
+gc_status gc_fine_doppler_create(gc_ctx* ctx, const gc_fine_doppler_conf* conf, int n_slots, gc_fine_doppler** out);
+gc_status gc_fine_doppler_destroy(gc_fine_doppler* fd);
+/* One code period, N complex float32 samples, of satellite slot `slot` (synchronous). */
+gc_status gc_fine_doppler_set_code(gc_fine_doppler* fd, int slot, const float* code);
+/* Refines n_requests (1 .. n_slots) requests on the P N samples of `ring` from absolute sample first_index on, in one launch, and
+ * waits for the results.  A slot may appear in several requests.  The ring must live on the handle's GPU; its format is taken from
+ * the ring; the block need only be resident: it may wrap the ring's end and need not fit the ring's max_window.  A read of the ring
+ * is reserved before the residency check; a block that is not resident is refused before anything is enqueued (GC_ERR_STATE when
+ * its first sample has been evicted, GC_ERR_INVALID when its end has not been pushed yet).
+ * GC_ERR_INVALID, before anything touches a device: NULL arguments, n_requests outside 1..n_slots, a slot outside the handle or
+ * without a code, delay_samples >= N, |coarse_doppler_hz| + window_hz >= fs_in / 2 or not finite, a window without a bin. */
+gc_status gc_fine_doppler_estimate_stream(gc_fine_doppler* fd, gc_stream* ring, uint64_t first_index, const gc_fine_doppler_request* requests,
+    int n_requests, gc_fine_doppler_result* results);
+/* The same on P N gr_complex samples in host memory. */
+gc_status gc_fine_doppler_estimate(gc_fine_doppler* fd, const float* host_iq, const gc_fine_doppler_request* requests, int n_requests,
+    gc_fine_doppler_result* results);
+/* Inspection: p over the window of request request_index of the last estimate call, window_bins floats in run order. */
+gc_status gc_fine_doppler_spectrum(gc_fine_doppler* fd, int request_index, float* host_p);
+/* The window rule on the host, no device: the circular run of {k : |(double)f[k] - coarse_hz| < window_hz}.  GC_ERR_INVALID for
+ * next odd, 0 or above 2^24, fs_in < 1, |coarse_hz| + window_hz >= fs_in / 2, a window that is not finite and positive. */
+gc_status gc_fine_doppler_window(int64_t fs_in, uint32_t next, double coarse_hz, double window_hz, uint32_t* first_bin, uint32_t* bins);
+size_t gc_fine_doppler_conf_size(void);
+
 #define GC_ABI_CHECK() \
     gc_abi_check(sizeof(gc_epoch_params), sizeof(gc_loop_conf), sizeof(gc_loop_record), sizeof(gc_loop_sync_conf), sizeof(gc_acq_conf), sizeof(gc_acq_result))
 
