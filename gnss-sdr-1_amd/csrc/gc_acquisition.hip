@@ -3,6 +3,7 @@
 // constructor sizes (:63-190), set_local_code (:239-274), init (:313-368),
 // acquisition_core (:668-770) -- batched over n_sats satellites that search the
 // same input block.
+#include "acq_caf_kernels.h"
 #include "acq_kernels.h"
 #include "acq_quicksync_kernels.h"
 #include "acq_tong_kernels.h"
@@ -104,7 +105,7 @@ struct gc_acq
     // the same spectra against replica B -- and the column pass combines the two |.|^2 of a grid cell before it writes it once
     // (ACQ_EPI_PMAX / _PSUM).  The inter-pass buffer is the one a held-back dwell pair would need, so dwells are never held back.
     int combine = 0;
-    int replicas() const { return combine ? 2 : 1; }
+    int replicas() const { return caf ? caf_p.replicas() : (combine ? 2 : 1); }
     // QuickSync engine (gc_acq_create_quicksync, pcps_quicksync_acquisition_cc.cc): 0, or the folding factor f.  fft_size is M = N / f
     // (N = samples_per_code), consumed is L = f N.  The wipe-off table holds L samples per bin in NATURAL order (the fold kernel and
     // the candidate check read it; no transform does), a dwell folds x * wipeoff into n_bins rows of M samples (acq_qs_fold_kernel,
@@ -130,6 +131,28 @@ struct gc_acq
     AcqTongState* d_tong_state = nullptr;  // [sat]
     int* d_tong_frozen = nullptr;          // [sat]
     AcqTongState* h_tong_state = nullptr;  // pinned
+    // CAF engine (gc_acq_create_caf, galileo_e5a_noncoherent_iq_acquisition_caf_cc.cc): fft_size = consumed = sampled_ms * samples_per_ms, the
+    // bin grid is inclusive, a slot holds R = (1 or 2 components) x (1 or 2 hypotheses) replicas in the order IA, QA, IB, QB (d_codes is
+    // [sat][R][N]).  The inverse row pass runs over R * n_bins cells per satellite, the column pass (ACQ_EPI_MAG, unchanged) writes the
+    // R |.|^2 planes of a batch and their block maxima, acq_caf_select_kernel makes the per-bin choice of hypothesis and builds the grid
+    // rows, and acq_caf_decide_kernel -- once per dwell -- the result, the keep rule and the CAF filter.  With R = 1 the column pass
+    // writes the grid itself.  Every dwell stands alone; the one thing kept between dwells is gc_acq_result::test_statistics on the
+    // device.  gc_acq_reset() only marks the restart: the next dwell zeroes the results in front of its own work, on its own stream.
+    struct CafParams
+    {
+        int both = 0, hyp = 1, half = 0, arithmetic = 0, bit_transition = 0;
+        int replicas() const { return (1 + both) * hyp; }
+    };
+    bool caf = false;
+    CafParams caf_p{};
+    bool caf_restart = true;
+    float* d_planes = nullptr;      // [batch sat][R][n_bins][N] (R >= 2)
+    float* d_plv = nullptr;         // their block maxima [batch sat][R][n_bins][n_blocks]
+    unsigned* d_pli = nullptr;
+    float* d_caf = nullptr;         // [sat][n_bins]
+    float* d_caf_i = nullptr;
+    float* d_caf_q = nullptr;
+    unsigned char* d_choice = nullptr;
 };
 
 static hipError_t acq_flush_inverse(gc_acq* a, hipStream_t st);
@@ -179,6 +202,13 @@ static void acq_release(gc_acq* a)
     (void)hipFree(a->d_cand_delay);
     (void)hipFree(a->d_tong_state);
     (void)hipFree(a->d_tong_frozen);
+    (void)hipFree(a->d_planes);
+    (void)hipFree(a->d_plv);
+    (void)hipFree(a->d_pli);
+    (void)hipFree(a->d_caf);
+    (void)hipFree(a->d_caf_i);
+    (void)hipFree(a->d_caf_q);
+    (void)hipFree(a->d_choice);
     if (a->h_tong_state) (void)hipHostFree(a->h_tong_state);
     if (a->h_results) (void)hipHostFree(a->h_results);
     for (int i = 0; i < 2; i++)
@@ -256,8 +286,9 @@ static hipError_t acq_build_main_wipeoffs(gc_acq* a, hipStream_t st)
     while (0)
 
 // gc_acq_create (combine = 0), gc_acq_create_paired, gc_acq_create_quicksync (fold = f, conf prepared by the entry point) and
-// gc_acq_create_tong (tong = its three counters, conf prepared by the entry point)
-static gc_status acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, int combine, int fold, gc_acq** out, const AcqTongParams* tong = nullptr)
+// gc_acq_create_tong (tong = its three counters, conf prepared by the entry point); gc_acq_create_caf (caf = its parameters, likewise)
+static gc_status acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, int combine, int fold, gc_acq** out, const AcqTongParams* tong = nullptr,
+    const gc_acq::CafParams* caf = nullptr)
 {
     GC_REQUIRE(n_sats > 0, "gc_acq_create: n_sats must be > 0");
     GC_REQUIRE(conf->sampled_ms > 0 && conf->samples_per_ms > 0.0f, "gc_acq_create: bad sizes");
@@ -301,6 +332,14 @@ static gc_status acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, in
             // pcps_tong_acquisition_cc.cc:107 (d_fft_size, no zero padding whatever the code length), :200-205 (the grid includes +doppler_max)
             a->tong = true;
             a->tong_p = *tong;
+            a->fft_size = a->eff = a->consumed;
+            a->n_bins = 2 * conf->doppler_max / conf->doppler_step + 1;
+        }
+    if (caf)
+        {
+            // galileo_e5a_noncoherent_iq_acquisition_caf_cc.cc:100 (d_fft_size, no zero padding of the engine's own), :300-307 (the grid includes +doppler_max)
+            a->caf = true;
+            a->caf_p = *caf;
             a->fft_size = a->eff = a->consumed;
             a->n_bins = 2 * conf->doppler_max / conf->doppler_step + 1;
         }
@@ -356,7 +395,7 @@ static gc_status acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, in
 #else
     a->roles = a->overlap = a->onchip = false;
 #endif
-    if (a->combine) a->roles = a->overlap = a->onchip = false;  // the experiment launches know one replica per satellite only
+    if (a->combine || a->caf) a->roles = a->overlap = a->onchip = false;  // the experiment launches know one replica per satellite only
     if (a->roles && n_sats > 1) a->q_stride = q_cells * N;  // second inter-pass buffer
     if (a->overlap && a->sats_per_batch < n_sats)
         {
@@ -396,6 +435,24 @@ static gc_status acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, in
             ACQ_TRY(hipMemset(a->d_tong_state, 0, (size_t)n_sats * sizeof(AcqTongState)));
             ACQ_TRY(hipMemset(a->d_tong_frozen, 0, (size_t)n_sats * sizeof(int)));
             ACQ_TRY(hipHostMalloc(reinterpret_cast<void**>(&a->h_tong_state), (size_t)n_sats * sizeof(AcqTongState), hipHostMallocDefault));
+        }
+    if (caf)
+        {
+            const size_t R = (size_t)a->replicas(), rows = (size_t)a->sats_per_batch * R * a->n_bins_alloc, vec = (size_t)n_sats * a->n_bins_alloc;
+            if (R > 1)
+                {
+                    ACQ_TRY(hipMalloc(&a->d_planes, rows * N * sizeof(float)));
+                    ACQ_TRY(hipMalloc(&a->d_plv, rows * a->n_blocks * sizeof(float)));
+                    ACQ_TRY(hipMalloc(&a->d_pli, rows * a->n_blocks * sizeof(unsigned)));
+                }
+            ACQ_TRY(hipMalloc(&a->d_caf, vec * sizeof(float)));
+            ACQ_TRY(hipMalloc(&a->d_caf_i, vec * sizeof(float)));
+            ACQ_TRY(hipMalloc(&a->d_caf_q, vec * sizeof(float)));
+            ACQ_TRY(hipMalloc(&a->d_choice, vec));
+            ACQ_TRY(hipMemset(a->d_caf, 0, vec * sizeof(float)));
+            ACQ_TRY(hipMemset(a->d_caf_i, 0, vec * sizeof(float)));
+            ACQ_TRY(hipMemset(a->d_caf_q, 0, vec * sizeof(float)));
+            ACQ_TRY(hipMemset(a->d_choice, 0, vec));
         }
     ACQ_TRY(hipMalloc(&a->d_results, (size_t)n_sats * sizeof(gc_acq_result)));
     if (fold) ACQ_TRY(hipMemset(a->d_results, 0, (size_t)n_sats * sizeof(gc_acq_result)));  // the candidate check reads its winner from here
@@ -547,6 +604,101 @@ gc_status gc_acq_tong_set_threshold(gc_acq* a, float threshold)
     return GC_OK;
 }
 
+gc_status gc_acq_create_caf(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, int both_components, int hypotheses, uint32_t caf_window_hz, int arithmetic,
+    gc_acq** out)
+{
+    GC_REQUIRE(conf && out, "gc_acq_create_caf: NULL argument");
+    *out = nullptr;
+    // what needs no device is checked before the context is looked at
+    GC_REQUIRE(both_components == 0 || both_components == 1, "gc_acq_create_caf: both_components %d is not 0 or 1", both_components);
+    GC_REQUIRE(hypotheses == 1 || hypotheses == 2, "gc_acq_create_caf: hypotheses %d is not 1 or 2", hypotheses);
+    GC_REQUIRE(arithmetic == GC_CAF_REFERENCE || arithmetic == GC_CAF_EXACT, "gc_acq_create_caf: unknown arithmetic %d", arithmetic);
+    GC_REQUIRE(conf->doppler_step > 0, "gc_acq_create_caf: doppler_step must be > 0 (the block has no default)");
+    GC_REQUIRE(!conf->make_2_steps, "gc_acq_create_caf: the CAF search has no second step");
+    GC_REQUIRE(!(conf->bit_transition_flag && conf->max_dwells < 1), "gc_acq_create_caf: bit_transition_flag needs max_dwells >= 1");
+    GC_REQUIRE(conf->samples_per_code >= 1.0f && conf->samples_per_code < 16777216.0f, "gc_acq_create_caf: bad samples_per_code");
+    const uint64_t n_bins = 2 * (uint64_t)conf->doppler_max / conf->doppler_step + 1;
+    GC_REQUIRE(n_bins <= ACQ_CAF_MAX_BINS, "gc_acq_create_caf: %llu Doppler bins, the engine takes at most %d", (unsigned long long)n_bins, ACQ_CAF_MAX_BINS);
+    const uint64_t half = (uint64_t)caf_window_hz / (2 * (uint64_t)conf->doppler_step);
+    if (caf_window_hz > 0)
+        {
+            // :689-704: H = 0 divides by zero (0.5 / H), fewer than 2 H + 1 bins read CAF_I out of range
+            GC_REQUIRE(half >= 1, "gc_acq_create_caf: a CAF window of %u Hz holds no bin of %u Hz to either side", caf_window_hz, conf->doppler_step);
+            GC_REQUIRE(n_bins >= 2 * half + 1, "gc_acq_create_caf: a CAF window of %llu bins to either side needs %llu Doppler bins, the grid has %llu",
+                (unsigned long long)half, (unsigned long long)(2 * half + 1), (unsigned long long)n_bins);
+        }
+    GC_REQUIRE(ctx, "gc_acq_create_caf: NULL context");
+    // the engine's view of the configuration: one block of sampled_ms * samples_per_ms samples per dwell at that transform size, every dwell
+    // stands alone; the bit transition flag only steers the keep rule of the decision kernel
+    gc_acq_conf c = *conf;
+    c.ms_per_code = c.sampled_ms;
+    c.bit_transition_flag = 0;
+    c.max_dwells = 1;
+    c.use_CFAR_algorithm_flag = 0;
+    c.num_doppler_bins_override = 0;
+    c.num_doppler_bins_step2 = 0;
+    gc_acq::CafParams p;
+    p.both = both_components;
+    p.hyp = hypotheses;
+    p.half = (int)half;
+    p.arithmetic = arithmetic;
+    p.bit_transition = conf->bit_transition_flag ? 1 : 0;
+    return acq_create(ctx, &c, n_sats, 0, 0, out, nullptr, &p);
+}
+
+gc_status gc_acq_set_local_code_iq(gc_acq* a, int sat, const float* code_i, const float* code_q)
+{
+    GC_REQUIRE(a && code_i, "gc_acq_set_local_code_iq: NULL argument");
+    GC_REQUIRE(a->caf, "gc_acq_set_local_code_iq: not a CAF engine (gc_acq_create_caf)");
+    GC_REQUIRE(code_q || !a->caf_p.both, "gc_acq_set_local_code_iq: an engine that searches both components needs code_q");
+    GC_REQUIRE(sat >= 0 && sat < a->n_sats, "gc_acq_set_local_code_iq: satellite slot %d out of range", sat);
+    gc_device_guard g(a->ctx->device);
+    std::lock_guard<std::mutex> lk(a->ctx->mtx);
+    hipStream_t st = a->ctx->stream;
+    const size_t N = a->fft_size, R = (size_t)a->replicas();
+    const size_t flip = std::min(N, (size_t)(uint32_t)a->conf.samples_per_code);
+    const float* comp[2] = {code_i, code_q};
+    // slots IA, QA, IB, QB (:234-282); B: the first code period negated
+    size_t slot = R * (size_t)sat;
+    for (int h = 0; h < a->caf_p.hyp; h++)
+        for (int c = 0; c <= a->caf_p.both; c++, slot++)
+            {
+                std::vector<float2> buf(N);
+                std::memcpy(buf.data(), comp[c], N * sizeof(float2));
+                if (h == 1)
+                    for (size_t i = 0; i < flip; i++) buf[i] = make_float2(-buf[i].x, -buf[i].y);
+                const gc_status s = acq_load_padded(a, st, buf, slot);  // synchronises
+                if (s != GC_OK) return s;
+            }
+    a->code_set[sat] = 1;
+    return GC_OK;
+}
+
+gc_status gc_acq_caf_vectors(gc_acq* a, int sat, float* caf, float* caf_i, float* caf_q, uint8_t* choice)
+{
+    GC_REQUIRE(a, "gc_acq_caf_vectors: NULL handle");
+    GC_REQUIRE(a->caf, "gc_acq_caf_vectors: not a CAF engine (gc_acq_create_caf)");
+    GC_REQUIRE(sat >= 0 && sat < a->n_sats, "gc_acq_caf_vectors: satellite slot %d out of range", sat);
+    gc_device_guard g(a->ctx->device);
+    std::lock_guard<std::mutex> lk(a->ctx->mtx);
+    const size_t n = a->n_bins, off = (size_t)sat * n;
+    if (a->caf_restart)
+        {
+            // reset and not run: what the first dwell starts from
+            if (caf) std::memset(caf, 0, n * sizeof(float));
+            if (caf_i) std::memset(caf_i, 0, n * sizeof(float));
+            if (caf_q) std::memset(caf_q, 0, n * sizeof(float));
+            if (choice) std::memset(choice, 0, n);
+            return GC_OK;
+        }
+    GC_HIP(hipStreamSynchronize(a->ctx->stream));
+    if (caf) GC_HIP(hipMemcpy(caf, a->d_caf + off, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (caf_i) GC_HIP(hipMemcpy(caf_i, a->d_caf_i + off, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (caf_q) GC_HIP(hipMemcpy(caf_q, a->d_caf_q + off, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (choice) GC_HIP(hipMemcpy(choice, a->d_choice + off, n, hipMemcpyDeviceToHost));
+    return GC_OK;
+}
+
 gc_status gc_acq_destroy(gc_acq* a)
 {
     if (!a) return GC_OK;
@@ -571,6 +723,7 @@ gc_status gc_acq_set_local_code(gc_acq* a, int sat, const float* code)
 {
     GC_REQUIRE(a && code, "gc_acq_set_local_code: NULL argument");
     GC_REQUIRE(!a->combine, "gc_acq_set_local_code: a paired engine takes two replicas per slot (gc_acq_set_local_code_pair)");
+    GC_REQUIRE(!a->caf, "gc_acq_set_local_code: a CAF engine takes its components through gc_acq_set_local_code_iq");
     GC_REQUIRE(sat >= 0 && sat < a->n_sats, "gc_acq_set_local_code: satellite slot %d out of range", sat);
     gc_device_guard g(a->ctx->device);
     std::lock_guard<std::mutex> lk(a->ctx->mtx);
@@ -601,6 +754,7 @@ gc_status gc_acq_set_local_code_pair(gc_acq* a, int sat, const float* code_a, co
 {
     GC_REQUIRE(a && code_a && code_b, "gc_acq_set_local_code_pair: NULL argument");
     GC_REQUIRE(!a->tong, "gc_acq_set_local_code_pair: a Tong engine takes one replica per slot (gc_acq_set_local_code)");
+    GC_REQUIRE(!a->caf, "gc_acq_set_local_code_pair: a CAF engine takes its components through gc_acq_set_local_code_iq");
     GC_REQUIRE(a->combine, "gc_acq_set_local_code_pair: not a paired engine (gc_acq_create_paired)");
     GC_REQUIRE(!a->fold, "gc_acq_set_local_code_pair: a QuickSync engine takes one code period per slot (gc_acq_set_local_code)");
     GC_REQUIRE(sat >= 0 && sat < a->n_sats, "gc_acq_set_local_code_pair: satellite slot %d out of range", sat);
@@ -620,6 +774,7 @@ gc_status gc_acq_set_frequency_offset(gc_acq* a, int64_t offset_hz)
     GC_REQUIRE(a, "gc_acq_set_frequency_offset: NULL handle");
     GC_REQUIRE(!a->fold, "gc_acq_set_frequency_offset: the QuickSync search has no frequency offset");
     GC_REQUIRE(!a->tong, "gc_acq_set_frequency_offset: the Tong search has no frequency offset");
+    GC_REQUIRE(!a->caf, "gc_acq_set_frequency_offset: the CAF search has no frequency offset");
     gc_device_guard g(a->ctx->device);
     std::lock_guard<std::mutex> lk(a->ctx->mtx);
     if (offset_hz == a->freq_offset_hz && a->wipe_valid) return GC_OK;
@@ -644,6 +799,7 @@ gc_status gc_acq_reset(gc_acq* a)
     a->grid_logically_zero = true;
     a->inv_pending = false;  // a held-back dwell goes with the grid it would have been added to
     a->tong_restart = true;  // Tong engine: counters, frozen flags and results restart in front of the next dwell, on its stream
+    a->caf_restart = true;   // CAF engine: the kept statistic and the results are zeroed in front of the next dwell, on its stream
     return GC_OK;
 }
 
@@ -652,6 +808,7 @@ gc_status gc_acq_set_step_two(gc_acq* a, int enable, float doppler_center_hz)
     GC_REQUIRE(a, "gc_acq_set_step_two: NULL handle");
     GC_REQUIRE(!a->fold, "gc_acq_set_step_two: the QuickSync search has no second step");
     GC_REQUIRE(!a->tong, "gc_acq_set_step_two: the Tong search has no second step");
+    GC_REQUIRE(!a->caf, "gc_acq_set_step_two: the CAF search has no second step");
     gc_device_guard g(a->ctx->device);
     std::lock_guard<std::mutex> lk(a->ctx->mtx);
     hipStream_t st = a->ctx->stream;
@@ -946,6 +1103,95 @@ static hipError_t acq_enqueue_tong(gc_acq* a, const float2* x, hipStream_t st)
     return e;
 }
 
+// one CAF dwell (galileo_e5a_noncoherent_iq_acquisition_caf_cc.cc:461-770) of every satellite slot on `st`, x the float block of N samples
+static hipError_t acq_enqueue_caf(gc_acq* a, const float2* x, hipStream_t st)
+{
+    const size_t N = a->fft_size;
+    const int n_bins = (int)a->n_bins, R = a->replicas();
+    hipError_t e = hipSuccess;
+    if (a->caf_restart)
+        {
+            // set_state(1) (:336-349): d_test_statistics = 0 and the Gnss_Synchro fields cleared; every dwell overwrites grid and vectors
+            e = hipMemsetAsync(a->d_results, 0, (size_t)a->n_sats * sizeof(gc_acq_result), st);
+            if (e != hipSuccess) return e;
+            a->caf_restart = false;
+        }
+    a->dwell_counter = 1;  // nothing accumulates
+    // input power of this block (:462-464), the block row-permuted, FFT(x * wipeoff[bin]) (:473-478)
+    e = acq_launch_input_power(st, x, (int)a->consumed, (int)N, a->d_power, nullptr, 0, 0);
+    if (e == hipSuccess) e = acq_launch_permute(st, x, nullptr, a->d_xw, a->plan, (int)a->consumed, 1, 0, 0, 0);
+    if (e == hipSuccess) e = acq_forward(a, st, 1);
+    const float fnf = (float)N * (float)N, fnf4 = fnf * fnf;
+    // * conj(FFT(replica)), IFFT, |.|^2 (:480-524) of the R replicas of a batch of satellites: cell = (sat * R + replica) * n_bins + bin
+    // reads spectrum cell % n_bins and code cell / n_bins of the batch's [sat][R] slots
+    for (int s0 = 0; s0 < a->n_sats && e == hipSuccess; s0 += a->sats_per_batch)
+        {
+            const int ns = std::min(a->sats_per_batch, a->n_sats - s0);
+            e = acq_launch_rows(st, true, a->plan, ns * R * n_bins, a->d_X, AcqCellMap{1, n_bins}, a->d_codes + (size_t)s0 * R * N, AcqCellMap{n_bins, 1 << 30},
+                a->d_Q, a->d_wN2, a->d_wN);
+            if (e != hipSuccess) break;
+            float* g_grid = a->d_grid + (size_t)s0 * n_bins * N;
+            float* g_blkv = a->d_blkv + (size_t)s0 * n_bins * a->n_blocks;
+            unsigned* g_blki = a->d_blki + (size_t)s0 * n_bins * a->n_blocks;
+            AcqMagArgs m;
+            m.grid = R > 1 ? a->d_planes : g_grid;  // one plane: it is the grid row
+            m.tmp = nullptr;
+            m.blk_max_val = R > 1 ? a->d_plv : g_blkv;
+            m.blk_max_idx = R > 1 ? a->d_pli : g_blki;
+            m.offset = 0;
+            m.eff = (int)a->eff;
+            m.n_bins = R * n_bins;
+            m.tmp_bin = R * n_bins - 1;
+            e = acq_launch_cols(st, true, ACQ_EPI_MAG, a->plan, ns * R * n_bins, a->d_Q, nullptr, &m);
+            if (e != hipSuccess || R == 1) continue;
+            AcqCafSelectArgs s;
+            s.planes = a->d_planes;
+            s.pl_max_val = a->d_plv;
+            s.pl_max_idx = a->d_pli;
+            s.grid = g_grid;
+            s.blk_max_val = g_blkv;
+            s.blk_max_idx = g_blki;
+            s.caf_i = a->d_caf_i + (size_t)s0 * n_bins;
+            s.caf_q = a->d_caf_q + (size_t)s0 * n_bins;
+            s.choice = a->d_choice + (size_t)s0 * n_bins;
+            s.n_bins = n_bins;
+            s.n_blocks = a->n_blocks;
+            s.N = (int)N;
+            s.both = a->caf_p.both;
+            s.hyp = a->caf_p.hyp;
+            s.arithmetic = a->caf_p.arithmetic;
+            s.fnf4 = fnf4;
+            e = acq_caf_launch_select(st, s, ns);
+        }
+    // d_mag, the keep rule, the result (:634-654), the CAF filter and its argmax (:685-770), with every dwell
+    if (e == hipSuccess)
+        {
+            AcqCafDecideArgs d;
+            d.blk_max_val = a->d_blkv;
+            d.blk_max_idx = a->d_blki;
+            d.input_power = a->d_power;
+            d.results = a->d_results;
+            d.caf = a->d_caf;
+            d.caf_i = a->d_caf_i;
+            d.caf_q = a->d_caf_q;
+            d.choice = a->d_choice;
+            d.n_bins = n_bins;
+            d.n_blocks = a->n_blocks;
+            d.fft_size = (int)N;
+            d.doppler_max = (int)a->conf.doppler_max;
+            d.doppler_step = (int)a->conf.doppler_step;
+            d.samples_per_code = (unsigned)a->conf.samples_per_code;
+            d.bit_transition = a->caf_p.bit_transition;
+            d.both = a->caf_p.both;
+            d.single_plane = R == 1 ? 1 : 0;
+            d.caf_half = a->caf_p.half;
+            d.arithmetic = a->caf_p.arithmetic;
+            d.fnf4 = fnf4;
+            e = acq_caf_launch_decide(st, d, a->n_sats);
+        }
+    return e;
+}
+
 // one dwell of every satellite slot on `st`; the caller holds the context mutex
 static gc_status acq_enqueue(gc_acq* a, const void* dev_iq_in, int iq_format, hipStream_t st)
 {
@@ -965,6 +1211,13 @@ static gc_status acq_enqueue(gc_acq* a, const void* dev_iq_in, int iq_format, hi
         {
             const hipError_t et = acq_enqueue_tong(a, dev_iq, st);
             if (et != hipSuccess) return gc_fail(GC_ERR_HIP, "gc_acq_dwell: kernel launch failed: %s", hipGetErrorString(et));
+            a->grid_logically_zero = false;
+            return GC_OK;
+        }
+    if (a->caf)
+        {
+            const hipError_t ec = acq_enqueue_caf(a, dev_iq, st);
+            if (ec != hipSuccess) return gc_fail(GC_ERR_HIP, "gc_acq_dwell: kernel launch failed: %s", hipGetErrorString(ec));
             a->grid_logically_zero = false;
             return GC_OK;
         }
@@ -1051,9 +1304,9 @@ gc_status gc_acq_dwell_enqueue(gc_acq* a, const void* dev_iq, void* stream)
 // results of the last dwell to the host; the caller holds the context mutex
 static gc_status acq_fetch(gc_acq* a, gc_acq_result* host_results, hipStream_t st)
 {
-    if (a->tong && a->tong_restart)
+    if ((a->tong && a->tong_restart) || (a->caf && a->caf_restart))
         {
-            // a Tong search that has been reset and not run: the results the restart will write
+            // a Tong or CAF search that has been reset and not run: the results the restart will write
             std::memset(host_results, 0, sizeof(gc_acq_result) * a->n_sats);
             return GC_OK;
         }
@@ -1290,7 +1543,7 @@ gc_status gc_acq_peek(gc_acq* a, int what, int index, float* host_out)
         }
     else if (what == GC_ACQ_PEEK_CODE)
         {
-            // paired engine: index = 2 * sat + replica
+            // paired engine: index = 2 * sat + replica; CAF engine: index = R * sat + replica
             GC_REQUIRE(index >= 0 && index < a->replicas() * a->n_sats, "gc_acq_peek: code slot %d out of range", index);
             src = a->d_codes + (size_t)index * N;
         }

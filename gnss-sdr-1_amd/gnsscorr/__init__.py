@@ -310,6 +310,9 @@ API = {
     "gc_acq_tong_status": (C.c_int, [_vp, _vp]),
     "gc_acq_tong_search_stream": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint32, _vp, _vp]),
     "gc_tong_threshold": (C.c_int, [C.c_float, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
+    "gc_acq_create_caf": (C.c_int, [_vp, C.POINTER(AcqConf), C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_int, C.POINTER(_vp)]),
+    "gc_acq_set_local_code_iq": (C.c_int, [_vp, C.c_int, _fp, _fp]),
+    "gc_acq_caf_vectors": (C.c_int, [_vp, C.c_int, _fp, _fp, _fp, C.POINTER(C.c_uint8)]),
     "gc_fine_doppler_create": (C.c_int, [_vp, _vp, C.c_int, C.POINTER(_vp)]),
     "gc_fine_doppler_destroy": (C.c_int, [_vp]),
     "gc_fine_doppler_set_code": (C.c_int, [_vp, C.c_int, _fp]),
@@ -605,6 +608,7 @@ class FineDopplerResult(C.Structure):
 
 
 FINE_ALIGN_REFERENCE, FINE_ALIGN_EXACT = 0, 1
+CAF_REFERENCE, CAF_EXACT = 0, 1
 FINE_REFINED, FINE_EDGE = 1, 2
 
 
@@ -1249,17 +1253,25 @@ class PcpsAcquisition:
     gives the f aliased delays and their time-domain correlations.  It excludes `combine`.
     tong = (init, max, max_dwells): the Tong engine (gc_acq_create_tong, pcps_tong_acquisition_cc.cc): every dwell adds its
     power-normalised |.|^2 to the grid and is decided on the device; set_threshold, tong_search_stream and tong_status drive it.  It
-    excludes `combine` and `folding_factor`."""
+    excludes `combine` and `folding_factor`.
+    caf = dict(both_components=, hypotheses=, window_hz=, arithmetic="reference" | "exact"): the CAF engine (gc_acq_create_caf,
+    galileo_e5a_noncoherent_iq_acquisition_caf_cc.cc): up to four replicas per slot (set_local_code_iq), the stronger sign hypothesis
+    of each component chosen per Doppler bin on the device, the CAF Doppler filter; caf_vectors(sat) reads CAF, CAF_I, CAF_Q and the
+    choice bytes.  It excludes `combine`, `folding_factor` and `tong`."""
 
     COMBINE = {"max": 1, "sum": 2}
+    CAF_ARITHMETIC = {"reference": CAF_REFERENCE, "exact": CAF_EXACT}
 
     def __init__(self, ctx, n_sats, fs_in, sampled_ms, ms_per_code, samples_per_ms, samples_per_code, samples_per_chip,
             doppler_max, doppler_step, max_dwells=1, bit_transition_flag=False, use_cfar=True, num_doppler_bins_override=0,
-            make_2_steps=False, num_doppler_bins_step2=4, doppler_step2=125.0, combine=None, folding_factor=None, tong=None):
+            make_2_steps=False, num_doppler_bins_step2=4, doppler_step2=125.0, combine=None, folding_factor=None, tong=None, caf=None):
         if folding_factor is not None and combine is not None:
             raise ValueError("folding_factor (the QuickSync engine) excludes combine (the paired engine)")
         if tong is not None and (combine is not None or folding_factor is not None):
             raise ValueError("tong (the Tong engine) excludes combine and folding_factor")
+        if caf is not None and (combine is not None or folding_factor is not None or tong is not None):
+            raise ValueError("caf (the CAF engine) excludes combine, folding_factor and tong")
+        self.caf = None if caf is None else dict(caf)
         self.tong = None if tong is None else tuple(int(v) for v in tong)
         self._ctx = ctx
         self.n_sats = n_sats
@@ -1270,7 +1282,17 @@ class PcpsAcquisition:
             int(make_2_steps), num_doppler_bins_step2, doppler_step2)
         self.conf = conf
         self._h = _vp()
-        if self.tong is not None:
+        if self.caf is not None:
+            unknown = set(self.caf) - {"both_components", "hypotheses", "window_hz", "arithmetic"}
+            if unknown:
+                raise ValueError("caf: unknown keys %s" % sorted(unknown))
+            window = int(self.caf.get("window_hz", 0))
+            if not 0 <= window < 2 ** 32:
+                raise GnsscorrError(GC_ERR_INVALID, "caf window_hz %r out of range" % (window,))
+            # an unknown name reaches the library as an unknown arithmetic: GC_ERR_INVALID
+            _check(load_library().gc_acq_create_caf(ctx._h if ctx is not None else None, C.byref(conf), n_sats, int(self.caf.get("both_components", 0)),
+                int(self.caf.get("hypotheses", 1)), window, self.CAF_ARITHMETIC.get(self.caf.get("arithmetic", "reference"), -1), C.byref(self._h)))
+        elif self.tong is not None:
             if len(self.tong) != 3 or not all(0 <= v < 2 ** 32 for v in self.tong):
                 raise GnsscorrError(GC_ERR_INVALID, "tong = (init, max, max_dwells), got %r" % (tong,))
             _check(load_library().gc_acq_create_tong(ctx._h, C.byref(conf), n_sats, self.tong[0], self.tong[1], self.tong[2], C.byref(self._h)))
@@ -1301,6 +1323,22 @@ class PcpsAcquisition:
         need = self.fft_size // 2 if self.conf.bit_transition_flag else self.consumed_samples
         assert code_a.size >= need and code_b.size >= need, (code_a.size, code_b.size, need)
         _check(load_library().gc_acq_set_local_code_pair(self._h, sat, _c64p(code_a), _c64p(code_b)))
+
+    def set_local_code_iq(self, sat, code_i, code_q=None):
+        """gc_acq_set_local_code_iq (CAF engine): fft_size complex samples per component; the library derives the B replicas."""
+        code_i = np.ascontiguousarray(code_i, np.complex64)
+        assert code_i.size >= self.fft_size, (code_i.size, self.fft_size)
+        if code_q is not None:
+            code_q = np.ascontiguousarray(code_q, np.complex64)
+            assert code_q.size >= self.fft_size, (code_q.size, self.fft_size)
+        _check(load_library().gc_acq_set_local_code_iq(self._h, sat, _c64p(code_i), None if code_q is None else _c64p(code_q)))
+
+    def caf_vectors(self, sat):
+        """gc_acq_caf_vectors: (CAF, CAF_I, CAF_Q float32[num_doppler_bins], choice uint8[num_doppler_bins]) of the last dwell."""
+        n = self.num_doppler_bins
+        caf, caf_i, caf_q, choice = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint8)
+        _check(load_library().gc_acq_caf_vectors(self._h, sat, _f32p(caf), _f32p(caf_i), _f32p(caf_q), choice.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return caf, caf_i, caf_q, choice
 
     def reset(self):
         _check(load_library().gc_acq_reset(self._h))
@@ -1381,7 +1419,8 @@ class PcpsAcquisition:
 
     def peek(self, what, index):
         """gc_acq_peek: a device-resident intermediate in natural order (complex64[fft_size], or float32[num_doppler_bins, 2]
-        = (row maximum, its index) for PEEK_ROW_MAX).  PEEK_CODE on a paired engine: index = 2 * sat + replica."""
+        = (row maximum, its index) for PEEK_ROW_MAX).  PEEK_CODE on a paired engine: index = 2 * sat + replica; on a CAF engine
+        index = R * sat + replica."""
         if what == self.PEEK_ROW_MAX:
             out = np.zeros((self.num_doppler_bins, 2), np.float32)
         elif what == self.PEEK_WIPEOFF and self.folding_factor is not None:

@@ -857,6 +857,55 @@ gc_status gc_acq_tong_search_stream(gc_acq* a, gc_stream* ring, uint64_t first_i
 /* The Tong adapters' calculate_threshold in closed form: ncells = vector_length * bins (bins counted inclusively), lambda = vector_length,
  * threshold = quantile(Exp(lambda), (1 - pfa)^(1 / ncells)) = -log(1 - (1 - pfa)^(1 / ncells)) / lambda. */
 gc_status gc_tong_threshold(float pfa, uint32_t vector_length, uint32_t doppler_max, uint32_t doppler_step, float* out);
+/* CAF engine (galileo_e5a_noncoherent_iq_acquisition_caf_cc.cc): the reference's E5a acquisition for 1 to 3 ms of coherent integration.
+ * N = sampled_ms * samples_per_ms is transform size and block length (no bit-transition padding, no second step); every dwell stands
+ * alone, overwrites the grid and is never held back.  A slot holds R = (1 + both_components) * hypotheses replicas in the order
+ * IA, QA, IB, QB, where B is A with its first code period [0, (uint32_t)samples_per_code) negated (:258-280).
+ * Per dwell: P = mean |x|^2; fnf4 = fnf * fnf, fnf = (float)N * (float)N.  Per Doppler bin b and replica X, with the plane
+ * X = |IFFT(FFT(x * wipeoff[b]) * conj(FFT(X)))|^2: (kX, mX) = its first maximum, nX = mX / fnf4 (float32).  I takes A when
+ * hypotheses == 1 or nIA >= nIB, else B; Q likewise with nQA >= nQB (:533, :543).  CAF_I[b] / CAF_Q[b] = the raw maximum of the chosen
+ * I / Q plane; grid row b = chosen I plane (+ chosen Q plane, float32, I first), (k_b, m_b) its first maximum.
+ * Per dwell: d_mag = the largest m_b / fnf4, bins ascending, a later bin only with a strictly larger value, nothing wins against 0 or
+ * with NaN (:635).  The device keeps ONE statistic per satellite (gc_acq_reset zeroes it): with bit_transition_flag off, or when
+ * kept < d_mag / P, the kept statistic := d_mag / P and indext, doppler_index, doppler_hz, acq_doppler_hz and acq_delay_samples =
+ * indext % (uint32_t)samples_per_code follow d_mag's cell; otherwise they stay those of the earlier dwell (:645-653).  The block makes
+ * that test at every running maximum of the bin walk; d_mag / P is monotone in d_mag, so testing the final maximum is the same.
+ * A dwell in which no cell wins (an all-zero block: P = 0, every plane 0) changes neither the kept statistic nor the cell fields:
+ * the statistic is then the one of the dwell before (0 after a reset), never 0 / 0.
+ * CAF filter (caf_window_hz > 0, :685-770): H = caf_window_hz / (2 * doppler_step) (integer), CAF[d] = the triangular-weighted mean
+ * of CAF_I around d plus that of CAF_Q, float32 running sums in index order with the block's three denominators
+ * (csrc/acq_caf_filter.h); the first maximum of CAF overwrites doppler_index, doppler_hz and acq_doppler_hz in EVERY dwell, whatever
+ * the keep rule said (:768-770).
+ * `arithmetic` chooses between the block as written and the block as meant; the two differ in two places:
+ *   GC_CAF_REFERENCE  (default, 0) nQB = IB[kQB] / fnf4 -- :523 reads d_magnitudeIB at QB's index -- and the filter weight is
+ *                     1 - wf * (float)(unsigned)(d - i) in the I sums of the head (d < H) and middle sections and in the Q sum of the
+ *                     middle section, where the block has no abs(): for i > d the difference wraps to 2^32 - (i - d)
+ *   GC_CAF_EXACT      nQB = QB[kQB] / fnf4, weight 1 - wf * |d - i| everywhere
+ * CAF_Q[b] is the chosen Q plane's own maximum in both (:560).  REFERENCE is the default because a receiver configured for the
+ * reference block is expected to report what that block reports.
+ *   Doppler bins    -doppler_max + b doppler_step for every value <= +doppler_max (inclusive, :300-307); at most 4096 bins
+ *   conf fields     fs_in, sampled_ms, samples_per_ms, samples_per_code, doppler_max, doppler_step, max_dwells, bit_transition_flag
+ *   GC_ERR_INVALID  hypotheses outside {1, 2}; both_components outside {0, 1}; unknown arithmetic; doppler_step == 0 (the block has no
+ *                   default); bit_transition_flag with max_dwells < 1; make_2_steps; caf_window_hz > 0 with H == 0 or fewer than
+ *                   2 H + 1 bins (the block reads out of range or divides by zero there); more than 4096 bins
+ * On such a handle gc_acq_fft_size reports N, N and the inclusive bin count; gc_acq_set_local_code_iq sets a slot; every dwell call
+ * (gc_acq_dwell, _dev, _enqueue / _flush / _fetch_results, _stream) and both integer input formats work; gc_acq_get_grid and
+ * GC_ACQ_PEEK_ROW_MAX read the grid rows; GC_ACQ_PEEK_CODE takes index = R * satellite slot + replica; gc_acq_set_local_code,
+ * gc_acq_set_local_code_pair, gc_acq_set_step_two and gc_acq_set_frequency_offset return GC_ERR_INVALID.
+ * gc_acq_result: mag = d_mag of this dwell, input_power = P, test_statistics = the kept statistic, both second_peak fields 0.
+ * The decision state machine (max_dwells dwells, then kept statistic > threshold) lives with the caller
+ * (adapter/hip_e5a_noncoherent_iq_acquisition_caf.h); its threshold is gc_tong_threshold(pfa, N, doppler_max, doppler_step). */
+enum { GC_CAF_REFERENCE = 0, GC_CAF_EXACT = 1 };
+gc_status gc_acq_create_caf(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, int both_components, int hypotheses, uint32_t caf_window_hz,
+    int arithmetic, gc_acq** out);
+/* set_local_code (:234-282) of slot `sat`: N complex samples each; the library derives the B replicas.  code_q may be NULL only
+ * without both_components (it is ignored then).  Zero padding is the caller's: a code with zeros behind it and hypotheses = 1.
+ * CAF engines only: GC_ERR_INVALID on any other handle. */
+gc_status gc_acq_set_local_code_iq(gc_acq* a, int sat, const float* code_i, const float* code_q);
+/* CAF, CAF_I, CAF_Q (num_doppler_bins floats each) and the choice bytes (bit 0: I took B, bit 1: Q took B) of slot `sat` in the last
+ * dwell; each output may be NULL.  `caf` reads as zeros when the filter is off, everything as zeros before the first dwell of a search.
+ * Synchronises the context stream: call it behind the fetch of a dwell enqueued on another stream. */
+gc_status gc_acq_caf_vectors(gc_acq* a, int sat, float* caf, float* caf_i, float* caf_q, uint8_t* choice);
 /* Inspection of the engine's device-resident intermediates (tests, failure dumps; synchronises the context stream; natural element
  * order whatever the layout in HBM).  `what`:
  *   GC_ACQ_PEEK_WIPEOFF   index = Doppler bin: the wipe-off row exp(-j phase) of the ACTIVE grid, d_grid_doppler_wipeoffs[bin]
