@@ -23,6 +23,8 @@ GC_IQ_F32, GC_IQ_I16, GC_IQ_I8 = range(3)
 # gc_raw_real_format: real raw samples, for Conditioner only (float32 / int16 / int8 one per sample; 2 bits, four samples per byte)
 GC_RAW_REAL_F32, GC_RAW_REAL_I16, GC_RAW_REAL_I8, GC_RAW_REAL_2BIT = range(16, 20)
 GC_RESAMP_DIRECT, GC_RESAMP_POLYPHASE = range(2)
+GC_SIGGEN_TABLES_AUTO, GC_SIGGEN_TABLES_HBM, GC_SIGGEN_TABLES_LDS = range(3)
+GC_SIGGEN_MAX_SATS, GC_SIGGEN_MAX_TABLE, GC_SIGGEN_MAX_SECONDARY = 32, 49104, 100
 
 
 class GnsscorrError(RuntimeError):
@@ -183,6 +185,33 @@ class ResamplerConf(C.Structure):
 assert C.sizeof(ResamplerConf) == 40
 
 
+class SiggenComponent(C.Structure):
+    """gc_siggen_component: one component of a generated satellite (table, secondary code, data, axis, gain)."""
+    _fields_ = [
+        ("table", C.POINTER(C.c_float)), ("secondary", C.POINTER(C.c_int8)), ("secondary_len", C.c_uint32), ("periods_per_symbol", C.c_uint32),
+        ("period_offset", C.c_uint32), ("axis", C.c_int32), ("gain", C.c_float), ("reserved", C.c_uint32),
+    ]
+
+
+class SiggenSat(C.Structure):
+    """gc_siggen_sat: one satellite of a SignalGenerator."""
+    _fields_ = [
+        ("doppler_hz", C.c_double), ("carrier_phase0_turns", C.c_double), ("code_phase0_periods", C.c_double), ("code_periods_per_sample", C.c_double),
+        ("amplitude", C.c_double), ("table_len", C.c_uint32), ("n_components", C.c_uint32), ("comp", SiggenComponent * 2),
+    ]
+
+
+class SiggenConf(C.Structure):
+    """gc_siggen_conf: the scene of a SignalGenerator."""
+    _fields_ = [
+        ("fs_hz", C.c_double), ("noise_sigma", C.c_double), ("seed", C.c_uint64), ("t0", C.c_uint64), ("n_sats", C.c_uint32),
+        ("table_placement", C.c_uint32), ("sats", C.POINTER(SiggenSat)),
+    ]
+
+
+assert C.sizeof(SiggenComponent) == 40 and C.sizeof(SiggenSat) == 128 and C.sizeof(SiggenConf) == 48
+
+
 # every symbol include/gnsscorr.h declares: name -> (restype, argtypes)
 _vp = C.c_void_p
 _fp = C.POINTER(C.c_float)
@@ -337,6 +366,18 @@ API = {
     "gc_ring_resampler_update": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gc_ring_resampler_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gc_resampler_design": (C.c_int, [C.c_double, C.c_double, C.c_uint32, _fp, C.c_int, C.POINTER(C.c_int)]),
+    "gc_siggen_component_size": (C.c_size_t, []),
+    "gc_siggen_sat_size": (C.c_size_t, []),
+    "gc_siggen_conf_size": (C.c_size_t, []),
+    "gc_signal_generator_create": (C.c_int, [_vp, C.POINTER(SiggenConf), _vp, C.POINTER(_vp)]),
+    "gc_signal_generator_destroy": (C.c_int, [_vp]),
+    "gc_signal_generator_generate": (C.c_int, [_vp, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "gc_signal_generator_info": (C.c_int, [_vp, C.POINTER(C.c_uint64)]),
+    "gc_signal_generator_set_output_scale": (C.c_int, [_vp, C.c_float]),
+    "gc_signal_generator_output_info": (C.c_int, [_vp, C.POINTER(C.c_int32), _fp, C.POINTER(C.c_uint64)]),
+    "gc_signal_generator_plan": (C.c_int, [C.POINTER(SiggenSat), C.c_double] + [C.POINTER(C.c_uint64)] * 4),
+    "gc_siggen_reference_satellite": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint32, C.c_double, C.c_double, C.c_uint32, C.c_uint32, C.c_double, C.c_double,
+        C.c_int, C.c_int, C.c_double, C.POINTER(SiggenSat), _fp, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_double)]),
 }
 
 _lib = None
@@ -376,6 +417,10 @@ def load_library():
         if lib.gc_resampler_conf_size() != C.sizeof(ResamplerConf):
             raise GnsscorrError(GC_ERR_INVALID, "gc_resampler_conf is %d bytes in the library, %d here -- rebuild with __graft_entry__.build()"
                 % (lib.gc_resampler_conf_size(), C.sizeof(ResamplerConf)))
+        for what, mirror in (("gc_siggen_component", SiggenComponent), ("gc_siggen_sat", SiggenSat), ("gc_siggen_conf", SiggenConf)):
+            if getattr(lib, what + "_size")() != C.sizeof(mirror):
+                raise GnsscorrError(GC_ERR_INVALID, "%s is %d bytes in the library, %d here -- rebuild with __graft_entry__.build()"
+                    % (what, getattr(lib, what + "_size")(), C.sizeof(mirror)))
         if lib.gc_fine_doppler_conf_size() != C.sizeof(FineDopplerConf):
             raise GnsscorrError(GC_ERR_INVALID, "gc_fine_doppler_conf is %d bytes in the library, %d here -- rebuild with __graft_entry__.build()"
                 % (lib.gc_fine_doppler_conf_size(), C.sizeof(FineDopplerConf)))
@@ -955,6 +1000,110 @@ class RingResampler(_DerivedRing):
         self.conf = ResamplerConf(float(fs_in), float(fs_out), self.mode, phases, taps, 0, None if self.bank is None else _f32p(self.bank))
         self._h = _vp()
         _check(load_library().gc_ring_resampler_create(ctx._h, src._h, C.byref(self.conf), out._h, C.byref(self._h)))
+
+
+class SiggenSatellite:
+    """One satellite of a SignalGenerator: the gc_siggen_sat and the arrays its pointers lead into.  components: one or two dicts
+    with `table` (float32 [table_len], one code period) and optionally `secondary` (+-1, int8 [<= 100]), `periods_per_symbol`
+    (0: no data), `period_offset`, `axis` (0 real, 1 imaginary) and `gain`."""
+
+    def __init__(self, doppler_hz, code_periods_per_sample, components, amplitude=1.0, carrier_phase0_turns=0.0, code_phase0_periods=0.0):
+        components = list(components)
+        if not 1 <= len(components) <= 2:
+            raise ValueError("a satellite has one or two components")
+        self._keep = []
+        self.c = SiggenSat()
+        self.c.doppler_hz, self.c.carrier_phase0_turns = float(doppler_hz), float(carrier_phase0_turns)
+        self.c.code_phase0_periods, self.c.code_periods_per_sample = float(code_phase0_periods), float(code_periods_per_sample)
+        self.c.amplitude = float(amplitude)
+        self.c.n_components = len(components)
+        self.tables, self.secondaries = [], []
+        for i, comp in enumerate(components):
+            table = np.ascontiguousarray(comp["table"], np.float32)
+            if i and table.size != self.tables[0].size:
+                raise ValueError("both components have table_len entries")
+            self.tables.append(table)
+            sec = comp.get("secondary")
+            sec = None if sec is None else np.ascontiguousarray(sec, np.int8)
+            self.secondaries.append(sec)
+            k = self.c.comp[i]
+            k.table = _f32p(table)
+            k.secondary = None if sec is None else sec.ctypes.data_as(C.POINTER(C.c_int8))
+            k.secondary_len = 0 if sec is None else int(sec.size)
+            k.periods_per_symbol = int(comp.get("periods_per_symbol", 0))
+            k.period_offset = int(comp.get("period_offset", 0))
+            k.axis = int(comp.get("axis", 0))
+            k.gain = float(comp.get("gain", 1.0))
+        self.c.table_len = int(self.tables[0].size)
+
+    @classmethod
+    def _from_c(cls, sat, tables, secondaries):
+        """Wraps a gc_siggen_sat the library filled; `tables` / `secondaries` are the arrays its pointers lead into."""
+        self = cls.__new__(cls)
+        self.c = sat
+        self._keep = [tables, secondaries]
+        n = int(sat.table_len)
+        self.tables = [tables[i, :n] for i in range(int(sat.n_components))]
+        self.secondaries = [secondaries[i, :int(sat.comp[i].secondary_len)] if sat.comp[i].secondary_len else None for i in range(int(sat.n_components))]
+        return self
+
+
+def siggen_plan(sat, fs_hz):
+    """gc_signal_generator_plan (host only): the Q0.64 words (code_step_q, code_phase0_q, carr_step_q, carr_phase0_q) of a
+    SiggenSatellite at the stream rate fs_hz -- floor(x 2^64) of each quantity in [0, 1)."""
+    w = [C.c_uint64(0) for _ in range(4)]
+    _check(load_library().gc_signal_generator_plan(C.byref(sat.c), float(fs_hz), *[C.byref(x) for x in w]))
+    return tuple(int(x.value) for x in w)
+
+
+def siggen_reference_satellite(system, signal, prn, cn0_db, doppler_hz, delay_chips, delay_sec, fs, bw_bb=1.0, data_flag=False, noise_flag=True,
+        intermediate_freq_hz=4e6):
+    """gc_siggen_reference_satellite: one satellite of the reference's Signal_Generator configuration (system "G" / "R" / "E", signal
+    "1C" / "1G" / "1B" / "5X").  Returns (SiggenSatellite, noise_sigma)."""
+    tables = np.zeros((2, GC_SIGGEN_MAX_TABLE), np.float32)
+    secondaries = np.zeros((2, GC_SIGGEN_MAX_SECONDARY), np.int8)
+    sat, sigma = SiggenSat(), C.c_double(0.0)
+    _check(load_library().gc_siggen_reference_satellite(system.encode(), signal.encode(), int(prn), float(cn0_db), float(doppler_hz), int(delay_chips),
+        int(delay_sec), float(fs), float(bw_bb), int(bool(data_flag)), int(bool(noise_flag)), float(intermediate_freq_hz), C.byref(sat), _f32p(tables),
+        GC_SIGGEN_MAX_TABLE, secondaries.ctypes.data_as(C.POINTER(C.c_int8)), C.byref(sigma)))
+    return SiggenSatellite._from_c(sat, tables, secondaries), float(sigma.value)
+
+
+class SignalGenerator(_RingStage):
+    """gc_signal_generator: the source stage of a ring.  A HIP kernel synthesises the scene of `sats` (SiggenSatellite, 1..32) plus
+    Gaussian noise of `noise_sigma` per part straight into `out_ring` (an empty GC_IQ_F32 IqStream, or an integer one after
+    accept_quantised_output()); ring sample i is scenario sample t0 + i, a closed form of that number alone.  generate(n) appends."""
+    _C = "gc_signal_generator"
+    _PLACEMENTS = {"auto": GC_SIGGEN_TABLES_AUTO, "hbm": GC_SIGGEN_TABLES_HBM, "lds": GC_SIGGEN_TABLES_LDS}
+
+    def __init__(self, ctx, out_ring, fs_hz, sats, noise_sigma=0.0, seed=0, t0=0, table_placement="auto"):
+        self._ctx = ctx
+        self._ring = out_ring
+        self.sats = list(sats)
+        self._sats_c = (SiggenSat * max(1, len(self.sats)))(*[s.c for s in self.sats])
+        self.conf = SiggenConf(float(fs_hz), float(noise_sigma), int(seed), int(t0), len(self.sats), self._PLACEMENTS[table_placement], self._sats_c)
+        self._h = _vp()
+        _check(load_library().gc_signal_generator_create(ctx._h, C.byref(self.conf), out_ring._h, C.byref(self._h)))
+
+    def generate(self, n_samples):
+        """Appends n_samples samples (asynchronous on the ring's copy stream); returns the absolute number of the first."""
+        first = C.c_uint64(0)
+        self._call("generate", int(n_samples), C.byref(first))
+        return int(first.value)
+
+    def info(self):
+        """Samples generated so far (the ring's head)."""
+        head = C.c_uint64(0)
+        self._call("info", C.byref(head))
+        return int(head.value)
+
+    def set_output_scale(self, scale):
+        """gc_signal_generator_set_output_scale: as Conditioner.set_output_scale; only before the first generate."""
+        self._call("set_output_scale", C.c_float(float(scale)))
+
+    def output_info(self):
+        """gc_signal_generator_output_info (synchronous): (output ring's format, scale, clipped components so far)."""
+        return self._output_info()
 
 
 class HipMulticorrelatorRealCodes:

@@ -1135,6 +1135,140 @@ gc_status gc_fine_doppler_spectrum(gc_fine_doppler* fd, int request_index, float
 gc_status gc_fine_doppler_window(int64_t fs_in, uint32_t next, double coarse_hz, double window_hz, uint32_t* first_bin, uint32_t* bins);
 size_t gc_fine_doppler_conf_size(void);
 
+/* ------------------------------------------------------------------------ */
+/* Signal generator: a synthetic multi-satellite scene written ON THE DEVICE   */
+/* into a ring -- the image of the reference's Signal_Generator source         */
+/* (src/algorithms/signal_generator/, block signal_generator_c.cc).  A         */
+/* generator is the producer of its ring, as a conditioner is, but has no      */
+/* input.  As for every ring stage, a sample's bits are a closed form of its   */
+/* ABSOLUTE number and never depend on the call, the tile or the piece of the  */
+/* ring it lands in.                                                          */
+/*                                                                            */
+/* Ring sample i carries scenario sample t = t0 + i (uint64, wraps).  All      */
+/* phases are exact integers on Q0.64 fixed point.  For satellite s (its       */
+/* index in the configuration, from 0; 1..32 satellites):                      */
+/*   code     U = code_phase0_q + t code_step_q   (128 bits, exact)            */
+/*            k = U >> 64  the code period,  f = U mod 2^64  the place in it   */
+/*            e = (f table_len) >> 64                                          */
+/*   component c (1 or 2):  v_c = table_c[e] gain_c sym_c sec_c                */
+/*            table_c  one code period, table_len equally spaced float32       */
+/*                     entries (1..49104)                                      */
+/*            sec_c  = secondary_c[(k + period_offset_c) mod secondary_len_c], */
+/*                     +-1, length <= 100; 1 when absent                       */
+/*            sym_c  = a random +-1 held for periods_per_symbol_c code periods */
+/*                     (0: no data, 1), symbol number                          */
+/*                     j = (k + period_offset_c) / periods_per_symbol_c        */
+/*            b_s    = sum_c (axis_c ? j v_c : v_c)                            */
+/*   carrier  theta = (carr_phase0_q + t carr_step_q) mod 2^64, in turns;      */
+/*            w_s = exp(j 2 pi theta / 2^64), evaluated from the signed upper  */
+/*            32 bits of theta rounded to float32                              */
+/*   sample   x[i] = sum_s amplitude_s b_s w_s + sigma (g_re + j g_im)         */
+/*            float32, satellites in index order, noise last                   */
+/*   random   Philox4x32-10, key (seed_lo, seed_hi).  Noise of sample t:       */
+/*            counter (t_lo, t_hi, 0, 0) -> x0..x3,                            */
+/*            u1 = ((x0 >> 8) + 1) 2^-24, u2 = (x1 >> 8) 2^-24,                */
+/*            r = sqrt(-2 ln u1), (g_re, g_im) = r (cos 2 pi u2, sin 2 pi u2). */
+/*            Symbol j of component c of satellite s: counter                  */
+/*            (j_lo, j_hi, 2 s + c, 1); +1 when x0 & 1 == 0, else -1.          */
+/* The doubles of gc_siggen_sat become Q0.64 words by ONE rule, floor(x 2^64)  */
+/* of x in [0, 1), exact for a double:                                         */
+/*   code_step_q   = floor(code_periods_per_sample 2^64)                       */
+/*   code_phase0_q = floor(code_phase0_periods 2^64)                           */
+/*   carr_step_q   = floor(frac(doppler_hz / fs_hz) 2^64)   quotient in IEEE   */
+/*                   double, frac(q) = q - floor(q) (1 becomes 0): a negative   */
+/*                   frequency is the two's complement step                    */
+/*   carr_phase0_q = floor(frac(carrier_phase0_turns) 2^64)                    */
+/* gc_signal_generator_plan returns them without a device.                     */
+/*                                                                            */
+/* The output ring: an empty GC_IQ_F32 ring, or an empty integer ring opened    */
+/* with gc_stream_accept_quantised_output, which receives the conditioner's     */
+/* quantisation of the same float32 samples ("Integer output rings" above).    */
+/*                                                                            */
+/* NOT mirrored from the reference block: its unseeded                         */
+/* std::default_random_engine (noise and data bits here are functions of       */
+/* `seed`), and the PRN / PRN - 1 index slip of its E5a initialisation         */
+/* (signal_generator_c.cc:111 against :399).                                   */
+/* ------------------------------------------------------------------------ */
+#define GC_SIGGEN_MAX_SATS 32
+#define GC_SIGGEN_MAX_TABLE 49104 /* 4092 chips x 12: one period of E1 CBOC */
+#define GC_SIGGEN_MAX_SECONDARY 100
+enum { GC_SIGGEN_TABLES_AUTO = 0, GC_SIGGEN_TABLES_HBM = 1, GC_SIGGEN_TABLES_LDS = 2 };
+typedef struct gc_siggen_component
+{
+    const float* table;          /* table_len floats (copied at create) */
+    const int8_t* secondary;     /* secondary_len values +-1 (copied), or NULL */
+    uint32_t secondary_len;      /* 0..100 */
+    uint32_t periods_per_symbol; /* 0: no data */
+    uint32_t period_offset;
+    int32_t axis;                /* 0: real part, 1: imaginary part */
+    float gain;
+    uint32_t reserved;           /* 0 */
+} gc_siggen_component;
+typedef struct gc_siggen_sat
+{
+    double doppler_hz;              /* carrier frequency in the stream, any sign */
+    double carrier_phase0_turns;
+    double code_phase0_periods;     /* in [0, 1) */
+    double code_periods_per_sample; /* in (0, 1) */
+    double amplitude;
+    uint32_t table_len;             /* entries per code period, both components */
+    uint32_t n_components;          /* 1 or 2 */
+    gc_siggen_component comp[2];
+} gc_siggen_sat;
+typedef struct gc_siggen_conf
+{
+    double fs_hz;
+    double noise_sigma;       /* per part; 0: no noise */
+    uint64_t seed;
+    uint64_t t0;              /* scenario sample of ring sample 0 */
+    uint32_t n_sats;          /* 1..32 */
+    uint32_t table_placement; /* GC_SIGGEN_TABLES_AUTO, or one placement forced (_LDS: GC_ERR_INVALID when the tables do not fit) */
+    const gc_siggen_sat* sats;
+} gc_siggen_conf;
+size_t gc_siggen_component_size(void);
+size_t gc_siggen_sat_size(void);
+size_t gc_siggen_conf_size(void);
+typedef struct gc_signal_generator gc_signal_generator;
+/* out_ring: an empty ring of the context (see above); the generator is its only producer from here on (gc_stream_push* on it
+ * return GC_ERR_STATE) until gc_signal_generator_destroy, and keeps a reference on it.  Every argument is checked before anything
+ * touches a device (GC_ERR_INVALID); tables and secondary codes are copied. */
+gc_status gc_signal_generator_create(gc_ctx* ctx, const gc_siggen_conf* conf, gc_stream* out_ring, gc_signal_generator** out);
+gc_status gc_signal_generator_destroy(gc_signal_generator* g);
+/* Appends n_samples samples; first_index (optional): the absolute number of the first of them.  Asynchronous on the ring's copy
+ * stream (gc_stream_synchronize waits for it); waits, like every producer, for launches that still read what it evicts.  More
+ * samples than the ring holds are appended in order, in several pieces.  One call runs at a time. */
+gc_status gc_signal_generator_generate(gc_signal_generator* g, uint64_t n_samples, uint64_t* first_index);
+/* The ring's head: samples generated so far. */
+gc_status gc_signal_generator_info(gc_signal_generator* g, uint64_t* head);
+/* gc_conditioner_set_output_scale / gc_conditioner_output_info for the generator: the scale only before the first
+ * gc_signal_generator_generate (GC_ERR_STATE afterwards), GC_ERR_INVALID for a scale that is not finite and positive and for a
+ * GC_IQ_F32 ring. */
+gc_status gc_signal_generator_set_output_scale(gc_signal_generator* g, float scale);
+gc_status gc_signal_generator_output_info(gc_signal_generator* g, int32_t* out_format, float* scale, uint64_t* clipped_components);
+/* The four Q0.64 words of one satellite by the rule above, on the host, no device (any pointer may be NULL). */
+gc_status gc_signal_generator_plan(const gc_siggen_sat* sat, double fs_hz, uint64_t* code_step_q, uint64_t* code_phase0_q, uint64_t* carr_step_q,
+    uint64_t* carr_phase0_q);
+/* One satellite of the reference block's configuration (SignalSource.system_i, .signal_i, .PRN_i, .CN0_dB_i, .doppler_Hz_i,
+ * .delay_chips_i, .delay_sec_i, .fs_hz, .BW_BB, .data_flag, .noise_flag) as a gc_siggen_sat, with the code generators above:
+ *   "G" "1C"  one BPSK component of 1023 entries, N = round(fs / 1 kHz), code step 1 / N, 20 periods per symbol with data_flag;
+ *             the noise-free sequence is gc_gps_l1_ca_code_gen_complex_sampled(prn, fs, 1023 - delay_chips), repeated
+ *   "R" "1G"  the same with the 511-chip code; carrier = intermediate_freq_hz + 562.5 kHz x channel(prn) + doppler (the block
+ *             hard-codes 4 MHz and says "must be set by the user")
+ *   "E" "1B"  component 0: E1-B CBOC, 12 entries per chip, gain +1, one period per symbol; component 1: E1-C CBOC, gain -1, the
+ *             25-chip secondary code, no data
+ *   "E" "5X"  component 0: the I code, real axis, the 20-chip secondary code, 20 periods per symbol; component 1: the Q code,
+ *             imaginary axis, the PRN's 100-chip secondary code; period_offset = delay_sec for both
+ * amplitude = sqrt(10^(CN0 / 10) / (BW_BB fs / 2)), with a further 1 / sqrt(2) for Galileo; 1 when noise_flag is 0 (*noise_sigma:
+ * 1 or 0).  code_phase0 lies one sample less 2^-16 behind the start of the (delayed) period, so that the floor of the table index
+ * is the samplers' ceil((i + 1) L / N) - 1, evaluated exactly.  For G / R at 2.048, 4 and 6.625 Msps that is the sampled generator
+ * sample for sample; where a sampler's float32 quotient lands an entry off (one sample per period at 25 Msps, isolated samples of the
+ * CBOC tables) the generator keeps the formula.  Data symbols change at the satellite's own code-period boundary.
+ * tables / secondaries: caller memory for 2 x table_capacity floats and 2 x 100 int8 that sat->comp[] will point into; they must
+ * outlive gc_signal_generator_create.  table_capacity >= the signal's table length (GC_SIGGEN_MAX_TABLE always suffices). */
+gc_status gc_siggen_reference_satellite(const char* system, const char* signal, uint32_t prn, double cn0_db, double doppler_hz, uint32_t delay_chips,
+    uint32_t delay_sec, double fs_hz, double bw_bb, int data_flag, int noise_flag, double intermediate_freq_hz, gc_siggen_sat* sat, float* tables,
+    uint32_t table_capacity, int8_t* secondaries, double* noise_sigma);
+
 #define GC_ABI_CHECK() \
     gc_abi_check(sizeof(gc_epoch_params), sizeof(gc_loop_conf), sizeof(gc_loop_record), sizeof(gc_loop_sync_conf), sizeof(gc_acq_conf), sizeof(gc_acq_result))
 
