@@ -23,6 +23,8 @@ GC_IQ_F32, GC_IQ_I16, GC_IQ_I8 = range(3)
 # gc_raw_real_format: real raw samples, for Conditioner only (float32 / int16 / int8 one per sample; 2 bits, four samples per byte)
 GC_RAW_REAL_F32, GC_RAW_REAL_I16, GC_RAW_REAL_I8, GC_RAW_REAL_2BIT = range(16, 20)
 GC_RESAMP_DIRECT, GC_RESAMP_POLYPHASE = range(2)
+GC_NOTCH_FULL, GC_NOTCH_LITE = range(2)
+GC_NOTCH_FLOOR_REFERENCE, GC_NOTCH_FLOOR_LINEAR = range(2)
 GC_SIGGEN_TABLES_AUTO, GC_SIGGEN_TABLES_HBM, GC_SIGGEN_TABLES_LDS = range(3)
 GC_SIGGEN_MAX_SATS, GC_SIGGEN_MAX_TABLE, GC_SIGGEN_MAX_SECONDARY = 32, 49104, 100
 
@@ -183,6 +185,18 @@ class ResamplerConf(C.Structure):
 
 
 assert C.sizeof(ResamplerConf) == 40
+
+
+class NotchConf(C.Structure):
+    """gc_notch_conf: the notch filter ring stage (the reference's Notch_Filter / Notch_Filter_Lite)."""
+    _fields_ = [
+        ("pfa", C.c_float), ("threshold", C.c_float), ("p_c_factor", C.c_float), ("length", C.c_uint32), ("segments_est", C.c_uint32),
+        ("segments_reset", C.c_uint32), ("segments_coeff", C.c_uint32), ("mode", C.c_int32), ("noise_floor", C.c_int32),
+        ("reserved", C.c_uint32 * 3),
+    ]
+
+
+assert C.sizeof(NotchConf) == 48
 
 
 class SiggenComponent(C.Structure):
@@ -366,6 +380,12 @@ API = {
     "gc_ring_resampler_update": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gc_ring_resampler_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gc_resampler_design": (C.c_int, [C.c_double, C.c_double, C.c_uint32, _fp, C.c_int, C.POINTER(C.c_int)]),
+    "gc_notch_conf_size": (C.c_size_t, []),
+    "gc_ring_notch_create": (C.c_int, [_vp, _vp, C.POINTER(NotchConf), _vp, C.POINTER(_vp)]),
+    "gc_ring_notch_destroy": (C.c_int, [_vp]),
+    "gc_ring_notch_update": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "gc_ring_notch_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "gc_ring_notch_state": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _fp, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), _fp, _fp]),
     "gc_siggen_component_size": (C.c_size_t, []),
     "gc_siggen_sat_size": (C.c_size_t, []),
     "gc_siggen_conf_size": (C.c_size_t, []),
@@ -417,6 +437,9 @@ def load_library():
         if lib.gc_resampler_conf_size() != C.sizeof(ResamplerConf):
             raise GnsscorrError(GC_ERR_INVALID, "gc_resampler_conf is %d bytes in the library, %d here -- rebuild with __graft_entry__.build()"
                 % (lib.gc_resampler_conf_size(), C.sizeof(ResamplerConf)))
+        if lib.gc_notch_conf_size() != C.sizeof(NotchConf):
+            raise GnsscorrError(GC_ERR_INVALID, "gc_notch_conf is %d bytes in the library, %d here -- rebuild with __graft_entry__.build()"
+                % (lib.gc_notch_conf_size(), C.sizeof(NotchConf)))
         for what, mirror in (("gc_siggen_component", SiggenComponent), ("gc_siggen_sat", SiggenSat), ("gc_siggen_conf", SiggenConf)):
             if getattr(lib, what + "_size")() != C.sizeof(mirror):
                 raise GnsscorrError(GC_ERR_INVALID, "%s is %d bytes in the library, %d here -- rebuild with __graft_entry__.build()"
@@ -1000,6 +1023,41 @@ class RingResampler(_DerivedRing):
         self.conf = ResamplerConf(float(fs_in), float(fs_out), self.mode, phases, taps, 0, None if self.bank is None else _f32p(self.bank))
         self._h = _vp()
         _check(load_library().gc_ring_resampler_create(ctx._h, src._h, C.byref(self.conf), out._h, C.byref(self._h)))
+
+
+class RingNotch(_DerivedRing):
+    """gc_ring_notch: the GC_IQ_F32 ring `out` derived on the device from the GC_IQ_F32 ring `src` (pushed, or fed by a Conditioner or
+    another derived ring) at the same rate, with continuous-wave interference notched out: the reference's Notch_Filter (mode "full")
+    and Notch_Filter_Lite (mode "lite", one coefficient per `segments_coeff` filtered segments).  Defaults: the reference adapter's.
+    noise_floor "reference" is the block's mean of decibels (biased low: it flags most pure-noise segments), "linear" the mean of
+    powers over the same bins.  threshold None: the upper-pfa chi-squared quantile with 2 * length degrees of freedom.  update()
+    appends the segments the source's samples so far complete."""
+    _C = "gc_ring_notch"
+    _MODES = {"full": GC_NOTCH_FULL, "lite": GC_NOTCH_LITE, GC_NOTCH_FULL: GC_NOTCH_FULL, GC_NOTCH_LITE: GC_NOTCH_LITE}
+    _FLOORS = {"reference": GC_NOTCH_FLOOR_REFERENCE, "linear": GC_NOTCH_FLOOR_LINEAR, GC_NOTCH_FLOOR_REFERENCE: GC_NOTCH_FLOOR_REFERENCE,
+        GC_NOTCH_FLOOR_LINEAR: GC_NOTCH_FLOOR_LINEAR}
+
+    def __init__(self, ctx, src, out, pfa=0.001, p_c_factor=0.9, length=32, segments_est=12500, segments_reset=5000000, mode="full",
+            segments_coeff=1, noise_floor="reference", threshold=None):
+        if mode not in self._MODES:
+            raise ValueError("mode is 'full' or 'lite'")
+        if noise_floor not in self._FLOORS:
+            raise ValueError("noise_floor is 'reference' or 'linear'")
+        self._ctx = ctx
+        self._src = src
+        self._ring = out
+        self.conf = NotchConf(float(pfa), 0.0 if threshold is None else float(threshold), float(p_c_factor), int(length), int(segments_est),
+            int(segments_reset), int(segments_coeff), self._MODES[mode], self._FLOORS[noise_floor])
+        self._h = _vp()
+        _check(load_library().gc_ring_notch_create(ctx._h, src._h, C.byref(self.conf), out._h, C.byref(self._h)))
+
+    def state(self):
+        """gc_ring_notch_state (synchronous): dict(segments_decided, segments_filtered, noise_power, n_segments, active, threshold, last)."""
+        d, f, n, act = C.c_uint64(0), C.c_uint64(0), C.c_uint32(0), C.c_int32(0)
+        noise, thr, last = C.c_float(0.0), C.c_float(0.0), (C.c_float * 2)(0.0, 0.0)
+        _check(load_library().gc_ring_notch_state(self._h, C.byref(d), C.byref(f), C.byref(noise), C.byref(n), C.byref(act), C.byref(thr), last))
+        return dict(segments_decided=int(d.value), segments_filtered=int(f.value), noise_power=float(noise.value), n_segments=int(n.value),
+            active=bool(act.value), threshold=float(thr.value), last=complex(last[0], last[1]))
 
 
 class SiggenSatellite:

@@ -1058,6 +1058,114 @@ gc_status gc_ring_resampler_info(gc_ring_resampler* r, uint64_t* src_consumed, u
 gc_status gc_resampler_design(double fs_in, double fs_out, uint32_t phases, float* bank, int capacity, int* taps_per_phase);
 
 /* ------------------------------------------------------------------------ */
+/* Notch filter ring stage: continuous-wave interference excised ON THE        */
+/* DEVICE -- the reference's input filters Notch_Filter and Notch_Filter_Lite   */
+/* (src/algorithms/input_filter/gnuradio_blocks/notch_cc.cc, notch_lite_cc.cc,  */
+/* adapters .../adapters/notch_filter.cc, notch_filter_lite.cc).  A GC_IQ_F32   */
+/* source ring in, a GC_IQ_F32 output ring out, at the same rate: output m is   */
+/* source sample m, copied or filtered.  It is a ring of its own and not a pass */
+/* inside the conditioner: the filter reads x[n-1] as it was BEFORE filtering,  */
+/* so it cannot overwrite its own input the way pulse blanking does.            */
+/* ------------------------------------------------------------------------ */
+/* The samples are x[n], n the absolute sample number, x[-1] = 0.  Segment s is [sL, (s+1)L).
+ *
+ * State: n = 0 (uint32), active = false, noise = 0, last = (0,0), z0 = (0,0), cn = 0.  All arithmetic is float32 with contraction
+ * off, unless said otherwise.
+ *
+ *   for s = 0, 1, 2, ...            (a segment is processed only when all L samples are in the source ring)
+ *     if n < segments_est and not active:
+ *         noise = (float(n) * noise + F[s]) / float(n + 1);   out = x, bit for bit
+ *     else:
+ *         E = sum over the segment of re^2 + im^2
+ *         if E / noise > threshold:
+ *             if not active: active = true; last = (0,0); (lite: cn = 0)
+ *             filter the segment (below)
+ *         else:
+ *             if n > segments_reset: n = 0
+ *             active = false;   out = x, bit for bit
+ *     n = n + 1
+ *
+ * The filter, GC_NOTCH_FULL, for every sample k of the segment in order:
+ *     c = x[k] * conj(x[k-1])
+ *     z = c / |c|, (1,0) when |c| = 0     -- the reference's exp(j * atan2(c.im, c.re)) without the trigonometry: the same unit
+ *                                            vector to rounding, from one square root and two divisions
+ *     b = x[k] - z * x[k-1]
+ *     a = (p * z.re, p * z.im)            p = p_c_factor
+ *     out[k] = b + a * last
+ *     last = out[k]
+ * The filter, GC_NOTCH_LITE:
+ *     when cn == 0, a new coefficient:  th1 = atan2f of x[sL+1] * conj(x[sL]);  th2 = atan2f of x[sL+L-1] * conj(x[sL+L-2]);
+ *                                       z0 = (cosf(th), sinf(th)) with th = (th1 + th2) / 2
+ *     then the same recursion with z = z0 for every sample;  then cn = (cn + 1) % segments_coeff
+ *     z0 survives a passing segment, as in the reference.
+ *
+ * out[k] = b + a * last composes, sample after sample, to one affine map (A, B) per segment.  The device carries last from segment
+ * to segment through these composites, last' = B + A * last, and computes the outputs of a segment by the recursion above from the
+ * last carried INTO it: the last carried on differs from the segment's final output by rounding (it is what gc_ring_notch_state
+ * reports), and every bit is a function of the stream alone.
+ *
+ * The noise floor F[s]:
+ *   1. X[k] is the L-point DFT of the segment, summed directly in sample order with twiddles rounded from double: the order is a
+ *      function of the segment alone.
+ *   2. P[k] = 10 * log10f(|X[k]|^2 + 1e-20f)
+ *   3. mean = sum(P) / L  and  cut = mean + 15                       (sums in bin order)
+ *   4. kept bins are those with P[k] <= cut
+ *   5. GC_NOTCH_FLOOR_REFERENCE:  fl = mean of P over the kept bins;  F = float(pow(10.0, double(fl) / 10.0) / double(float(2L))).
+ *      This is the block as written: VOLK's power spectrum with normalisation 1, its spectral noise floor with 15 dB exclusion,
+ *      and std::pow.
+ *   6. GC_NOTCH_FLOOR_LINEAR:     F = mean of |X[k]|^2 over the same kept bins, divided by float(2L)
+ *
+ * threshold: the upper pfa quantile of a chi-squared distribution with 2L degrees of freedom (gc_chi2_upper_quantile), rounded to
+ * float32, unless the caller supplies one (0: compute it) -- the pulse blanking convention.
+ *
+ * Quirks kept from the reference:
+ *   Bias.        Averaging decibels biases the REFERENCE floor low by about e^-0.577: for L = 32 and complex Gaussian noise of power
+ *                1 it gives noise about 0.25 where pulse blanking's E / float(2L) gives 0.5.  At pfa = 1e-3 (threshold 104.7) it
+ *                then flags about 80 % of pure-noise segments (the median E / noise is about 125).  GC_NOTCH_FLOOR_LINEAR is the
+ *                unbiased alternative (it flags none of them, and with a tone present exactly the segments the tone covers), after
+ *                the precedent of the CAF engine's arithmetic = reference | exact.  The default is the reference's.
+ *   Blind spot.  A tone already present while the floor is estimated raises the floor and is never flagged.
+ *   Reset.       After a reset n becomes 1, not 0, as in pulse blanking: the re-estimate starts as the mean of the OLD floor and one
+ *                new segment.  n wraps where the reference's int32 overflows.
+ *
+ * Outputs, flags, state and counters are bit-identical however the source was pushed and however the updates were cut, also where
+ * the output ring's wrap cuts a segment in two; unflagged segments are copied bit for bit. */
+enum { GC_NOTCH_FULL = 0, GC_NOTCH_LITE = 1 };
+enum { GC_NOTCH_FLOOR_REFERENCE = 0, GC_NOTCH_FLOOR_LINEAR = 1 };
+typedef struct gc_notch_conf
+{
+    float pfa;               /* false-alarm probability of one segment, 0 < pfa < 1 */
+    float threshold;         /* 0: computed from pfa and length; otherwise finite and > 0, used as is */
+    float p_c_factor;        /* p, the pole's radius: 0 <= p < 1 */
+    uint32_t length;         /* L, samples per segment, 2..1024 (the noise-floor estimate uses a direct DFT) */
+    uint32_t segments_est;   /* segments of a noise-floor estimate, >= 1 */
+    uint32_t segments_reset; /* a passing segment with n above this starts a new estimate */
+    uint32_t segments_coeff; /* GC_NOTCH_LITE: filtered segments per coefficient, >= 1 (also in full mode, where it is unused) */
+    int32_t mode;            /* GC_NOTCH_FULL or GC_NOTCH_LITE */
+    int32_t noise_floor;     /* GC_NOTCH_FLOOR_REFERENCE or GC_NOTCH_FLOOR_LINEAR */
+    uint32_t reserved[3];    /* 0 */
+} gc_notch_conf; /* 48 bytes */
+size_t gc_notch_conf_size(void);
+typedef struct gc_ring_notch gc_ring_notch;
+/* src_ring: a GC_IQ_F32 ring of the context, empty or still holding sample 0 (GC_ERR_STATE otherwise), of more than L samples.
+ * out_ring: an empty GC_IQ_F32 ring of the same context; the stage is its only producer from here on (gc_stream_push* on it return
+ * GC_ERR_STATE) until gc_ring_notch_destroy.  Rings of another format: GC_ERR_INVALID.  The stage keeps a reference on both rings.
+ * The configuration is checked before anything touches a device (GC_ERR_INVALID). */
+gc_status gc_ring_notch_create(gc_ctx* ctx, gc_stream* src_ring, const gc_notch_conf* conf, gc_stream* out_ring, gc_ring_notch** out);
+gc_status gc_ring_notch_destroy(gc_ring_notch* f);
+/* Appends every segment the source's samples so far complete: afterwards the output ring's head is floor(source head / L) * L.
+ * first_out / n_out (optional): the absolute number of the first new output and their count.  Asynchronous on the output ring's copy
+ * stream; the launches wait for the newest source push, and no source push evicts what they read.  GC_ERR_STATE, with nothing
+ * changed, when source sample m0 - 1 (m0 = the output head; sample 0 for m0 = 0) is no longer resident.  One update runs at a time. */
+gc_status gc_ring_notch_update(gc_ring_notch* f, uint64_t* first_out, uint64_t* n_out);
+/* The source head the newest successful update saw, and the output ring's head (any pointer may be NULL). */
+gc_status gc_ring_notch_info(gc_ring_notch* f, uint64_t* src_consumed, uint64_t* out_head);
+/* Segments decided and filtered so far, the noise floor, n, active, the threshold in use and last as (re, im) in last_re_im[2] (any
+ * pointer may be NULL).  Synchronous: waits for the updates so far and copies the state back from the device. */
+gc_status gc_ring_notch_state(gc_ring_notch* f, uint64_t* segments_decided, uint64_t* segments_filtered, float* noise_power, uint32_t* n_segments,
+    int32_t* active, float* threshold, float* last_re_im);
+
+/* ------------------------------------------------------------------------ */
 /* Fine Doppler stage (pcps_acquisition_fine_doppler_cc.cc:400-479): the Doppler */
 /* of an acquired satellite to fs / (P Z N) -- 12.5 Hz for a 1 ms code, P = 10,   */
 /* Z = 8 -- from the P code periods the ring already holds.  It refines the       */
