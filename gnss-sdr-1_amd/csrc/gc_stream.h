@@ -15,6 +15,12 @@ struct gc_hip_event_policy
     static bool record(hipEvent_t e, hipStream_t st) { return hipEventRecord(e, st) == hipSuccess; }
 };
 
+// samples behind the mirror that belong to the ring's storage and stay zero, samples each guard band holds at least, and the
+// byte the bands are filled with (gc_stream.hip has the layout and what each is for)
+static const uint64_t GC_STREAM_SLACK = 2;
+static const uint64_t GC_STREAM_GUARD_SAMPLES = 1024;
+static const int GC_STREAM_GUARD_BYTE = 0xA5;
+
 struct gc_stream
 {
     gc_ctx* ctx = nullptr;
@@ -23,7 +29,9 @@ struct gc_stream
     size_t elem = 8;         // bytes per complex sample
     uint64_t capacity = 0;   // samples in the ring
     uint64_t mirror = 0;     // samples repeated behind the ring so that a window never has to wrap
-    char* d_ring = nullptr;  // (capacity + mirror) * elem bytes
+    char* d_ring = nullptr;  // (capacity + mirror + GC_STREAM_SLACK) * elem bytes inside d_base, behind the front guard band
+    char* d_base = nullptr;  // the allocation (hipFree takes this): guard band, ring storage, guard band (layout: gc_stream.hip)
+    size_t guard_bytes = 0;  // bytes of each guard band: a multiple of 4096
     uint64_t head = 0;       // absolute index one past the newest sample
     hipStream_t copy_stream = nullptr;
     hipEvent_t pushed = nullptr;  // completion of the newest push
@@ -67,6 +75,9 @@ gc_status gc_stream_produce(gc_stream* s, uint64_t n_samples, uint64_t* first_in
 
 void gc_stream_keep(gc_stream* s);
 void gc_stream_drop(gc_stream* s);
+
+// samples of storage at d_ring: ring, mirror and slack
+static inline uint64_t gc_stream_storage_samples(const gc_stream* s) { return s->capacity + s->mirror + GC_STREAM_SLACK; }
 
 // oldest absolute index still resident (a push in progress counts as done)
 static inline uint64_t gc_stream_oldest(const gc_stream* s)

@@ -7,14 +7,31 @@
 // and, when that is < max_window, also at capacity + a % capacity.  Kernels index with absolute sample
 // numbers (TrkChan::ring_len).  Pushes run on the stream's own HIP stream through pinned staging slots and
 // overlap with compute; a push waits only for kernels that may still read the samples it evicts.
+//
+// The allocation, front to back:
+//
+//   guard | ring: capacity | mirror: max_window | slack: GC_STREAM_SLACK | guard
+//
+// d_ring points at the ring.  The slack is two samples behind the mirror -- one aligned pair of samples, the unit in which the
+// tracking kernels fetch a window (trk_device.hpp): a margin of one such pair behind the last position a window can touch, kept
+// since the first ring.  No load needs it: a window starts below capacity and holds at most max_window samples, so its last
+// sample lies at or below position capacity + max_window - 2 and the aligned pair that holds it ends inside the mirror; whole
+// chunks are fetched inside [0, capacity) alone and ragged ends sample by sample (load_masked), and ring_window.h reads nothing
+// behind the ring's end.  No writer stores there either: the slack stays zero for the ring's life
+// (tests/test_ring_contract_gpu.py compares it after every update).
+// The guard bands are storage no writer and no reader has any business in: each holds at least the largest tile of any
+// producer (1024 outputs), rounded up to a multiple of 4096 bytes -- so that d_ring keeps the allocation's alignment -- and is
+// filled with GC_STREAM_GUARD_BYTE at creation.  gc_stream_debug_guards compares them with that byte: a store of a producer
+// kernel in front of the ring or past capacity + max_window + slack shows there instead of in a neighbouring allocation.
 #include "gc_stream.h"
 #include <algorithm>
 #include <cstring>
+#include <vector>
 
 static void stream_release(gc_stream* s)
 {
     if (s->copy_stream) (void)hipStreamSynchronize(s->copy_stream);
-    (void)hipFree(s->d_ring);
+    (void)hipFree(s->d_base);
     for (int i = 0; i < gc_stream::kSlots; i++)
         {
             if (s->h_slot[i]) (void)hipHostFree(s->h_slot[i]);
@@ -98,8 +115,16 @@ gc_status gc_stream_create(gc_ctx* ctx, int iq_format, uint64_t capacity_samples
     s->capacity = capacity_samples;
     s->mirror = max_window_samples;
     s->slot_bytes = (size_t)4 << 20;
-    hipError_t e = hipMalloc(&s->d_ring, (size_t)(s->capacity + s->mirror + 2) * s->elem);
-    if (e == hipSuccess) e = hipMemset(s->d_ring, 0, (size_t)(s->capacity + s->mirror + 2) * s->elem);
+    s->guard_bytes = ((size_t)GC_STREAM_GUARD_SAMPLES * s->elem + 4095u) & ~(size_t)4095u;
+    const size_t storage_bytes = (size_t)gc_stream_storage_samples(s) * s->elem;
+    hipError_t e = hipMalloc(&s->d_base, s->guard_bytes + storage_bytes + s->guard_bytes);
+    if (e == hipSuccess)
+        {
+            s->d_ring = s->d_base + s->guard_bytes;
+            e = hipMemset(s->d_base, GC_STREAM_GUARD_BYTE, s->guard_bytes);
+        }
+    if (e == hipSuccess) e = hipMemset(s->d_ring, 0, storage_bytes);
+    if (e == hipSuccess) e = hipMemset(s->d_ring + storage_bytes, GC_STREAM_GUARD_BYTE, s->guard_bytes);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&s->pushed, hipEventDisableTiming);
     for (int i = 0; i < gc_stream::kSlots && e == hipSuccess; i++)
@@ -299,6 +324,38 @@ gc_status gc_stream_read(gc_stream* s, uint64_t first_index, uint64_t n_samples,
             dst += (size_t)len * s->elem;
             idx += len;
             left -= len;
+        }
+    return GC_OK;
+}
+
+gc_status gc_stream_debug_read_storage(gc_stream* s, uint64_t first_position, uint64_t n_samples, void* host_out)
+{
+    GC_REQUIRE(s && (host_out || n_samples == 0), "gc_stream_debug_read_storage: NULL argument");
+    const uint64_t total = gc_stream_storage_samples(s);
+    GC_REQUIRE(first_position <= total && n_samples <= total - first_position,
+        "gc_stream_debug_read_storage: positions [%llu, +%llu) are outside the ring's storage of %llu samples (ring, mirror and slack)",
+        (unsigned long long)first_position, (unsigned long long)n_samples, (unsigned long long)total);
+    gc_device_guard g(s->ctx->device);
+    // as gc_stream_read: no push starts while the storage is copied, and what has been enqueued has landed
+    std::lock_guard<std::mutex> no_push(s->push_mtx);
+    GC_HIP(hipStreamSynchronize(s->copy_stream));
+    if (n_samples) GC_HIP(hipMemcpy(host_out, s->d_ring + first_position * s->elem, (size_t)n_samples * s->elem, hipMemcpyDeviceToHost));
+    return GC_OK;
+}
+
+gc_status gc_stream_debug_guards(gc_stream* s, int32_t* front_intact, int32_t* back_intact)
+{
+    GC_REQUIRE(s && front_intact && back_intact, "gc_stream_debug_guards: NULL argument");
+    gc_device_guard g(s->ctx->device);
+    std::lock_guard<std::mutex> no_push(s->push_mtx);
+    GC_HIP(hipStreamSynchronize(s->copy_stream));
+    std::vector<unsigned char> band(s->guard_bytes);
+    const char* at[2] = {s->d_base, s->d_ring + (size_t)gc_stream_storage_samples(s) * s->elem};
+    int32_t* intact[2] = {front_intact, back_intact};
+    for (int i = 0; i < 2; i++)
+        {
+            GC_HIP(hipMemcpy(band.data(), at[i], band.size(), hipMemcpyDeviceToHost));
+            *intact[i] = std::all_of(band.begin(), band.end(), [](unsigned char b) { return b == GC_STREAM_GUARD_BYTE; }) ? 1 : 0;
         }
     return GC_OK;
 }

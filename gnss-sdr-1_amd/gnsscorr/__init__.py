@@ -264,6 +264,8 @@ API = {
     "gc_stream_info": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gc_stream_synchronize": (C.c_int, [_vp]),
     "gc_stream_read": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp]),
+    "gc_stream_debug_read_storage": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp]),
+    "gc_stream_debug_guards": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "gc_stream_accept_quantised_output": (C.c_int, [_vp]),
     "gc_conditioner_conf_size": (C.c_size_t, []),
     "gc_conditioner_create": (C.c_int, [_vp, C.POINTER(ConditionerConf), _fp, _vp, C.POINTER(_vp)]),
@@ -778,6 +780,21 @@ class IqStream:
         out = np.zeros(int(n) if per == 1 else (int(n), per), dt)
         _check(load_library().gc_stream_read(self._h, int(first_index), int(n), out.ctypes.data_as(_vp)))
         return out
+
+    def read_storage(self, position, n):
+        """gc_stream_debug_read_storage (diagnostic): the raw storage positions [position, position + n) -- the ring, then its
+        mirror, then two samples of slack -- in the ring's format, with no residency check.  Synchronous."""
+        dt, per = self._DTYPES[self.iq_format]
+        out = np.zeros(int(n) if per == 1 else (int(n), per), dt)
+        _check(load_library().gc_stream_debug_read_storage(self._h, int(position), int(n), out.ctypes.data_as(_vp)))
+        return out
+
+    def guards_intact(self):
+        """gc_stream_debug_guards (diagnostic): (front, back) -- whether the guard band in front of the ring's storage and the
+        one behind it still hold the byte they were filled with."""
+        front, back = C.c_int32(0), C.c_int32(0)
+        _check(load_library().gc_stream_debug_guards(self._h, C.byref(front), C.byref(back)))
+        return bool(front.value), bool(back.value)
 
     def close(self):
         if self._h:

@@ -188,6 +188,17 @@ gc_status gc_stream_synchronize(gc_stream* s);
 /* Copies the resident window [first_index, first_index + n_samples) to host memory in the ring's format (tests, failure dumps).
  * Synchronous: waits for the pushes so far.  GC_ERR_STATE when the window is not resident. */
 gc_status gc_stream_read(gc_stream* s, uint64_t first_index, uint64_t n_samples, void* host_out);
+/* DIAGNOSTICS (tests, failure dumps; nothing a receiver needs).  A ring's storage is capacity_samples, then the mirror of
+ * max_window_samples, then 2 samples of slack that nothing writes; in front of it and behind it lies a guard band filled with a
+ * fixed byte at creation.
+ * gc_stream_debug_read_storage copies the RAW storage positions [first_position, first_position + n_samples), anywhere in
+ * [0, capacity_samples + max_window_samples + 2), to host memory in the ring's format, without any residency check: what a kernel
+ * that reads a window through the mirror sees.  Synchronous: waits for what has been enqueued on the ring.  GC_ERR_INVALID when
+ * the range leaves the storage.
+ * gc_stream_debug_guards copies both guard bands to the host and reports, as 1 or 0, whether every byte of the band in front of
+ * the ring and of the band behind it still holds the fill: a 0 means that something stored outside the ring's storage. */
+gc_status gc_stream_debug_read_storage(gc_stream* s, uint64_t first_position, uint64_t n_samples, void* host_out);
+gc_status gc_stream_debug_guards(gc_stream* s, int32_t* front_intact, int32_t* back_intact);
 
 /* ------------------------------------------------------------------------ */
 /* Signal conditioner: a frequency-translating FIR decimator in front of a      */
