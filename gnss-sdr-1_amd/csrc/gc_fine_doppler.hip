@@ -4,6 +4,7 @@
 #include "gc_stream.h"
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 static_assert((int)GC_FINE_ALIGN_REFERENCE == (int)FINE_ALIGN_REFERENCE && (int)GC_FINE_ALIGN_EXACT == (int)FINE_ALIGN_EXACT, "one alignment code");
@@ -14,35 +15,21 @@ static const uint64_t FINE_MAX_WINDOW_BINS = 8192;
 struct gc_fine_doppler
 {
     gc_ctx* ctx = nullptr;
-    gc_ctx_ref ctx_ref;
+    gc_ctx_ref ctx_ref;  // before the buffers: the context outlives their frees (gc_internal.h)
     gc_fine_doppler_conf conf;
     int n_slots = 0;
     uint32_t total = 0, next = 0, n_tiles = 0, stride = 0;
     std::vector<char> has_code;
-    float2* d_codes = nullptr;
-    float2* d_block = nullptr;  // the host entry point's samples
-    AcqFineRequest* d_req = nullptr;
-    AcqFineRequest* h_req = nullptr;
-    float2* d_partial = nullptr;
-    float* d_energy = nullptr;
-    float* d_spec = nullptr;
-    gc_fine_doppler_result* d_results = nullptr;
-    gc_fine_doppler_result* h_results = nullptr;
+    gc_dev_buf<float2> d_codes;
+    gc_dev_buf<float2> d_block;  // the host entry point's samples
+    gc_dev_buf<AcqFineRequest> d_req;
+    gc_host_buf<AcqFineRequest> h_req;
+    gc_dev_buf<float2> d_partial;
+    gc_dev_buf<float> d_energy, d_spec;
+    gc_dev_buf<gc_fine_doppler_result> d_results;
+    gc_host_buf<gc_fine_doppler_result> h_results;
     std::vector<uint32_t> last_bins;  // window_bins of the last call's requests
 };
-
-static void fine_release(gc_fine_doppler* f)
-{
-    (void)hipFree(f->d_codes);
-    (void)hipFree(f->d_block);
-    (void)hipFree(f->d_req);
-    (void)hipFree(f->d_partial);
-    (void)hipFree(f->d_energy);
-    (void)hipFree(f->d_spec);
-    (void)hipFree(f->d_results);
-    if (f->h_req) (void)hipHostFree(f->h_req);
-    if (f->h_results) (void)hipHostFree(f->h_results);
-}
 
 // the requests of one call as the kernels take them; no device is touched
 static gc_status fine_resolve(gc_fine_doppler* f, const char* who, const gc_fine_doppler_request* requests, int n_requests, std::vector<AcqFineRequest>& out)
@@ -144,7 +131,7 @@ gc_status gc_fine_doppler_create(gc_ctx* ctx, const gc_fine_doppler_conf* conf, 
         (unsigned long long)FINE_MAX_WINDOW_BINS);
     GC_REQUIRE(ctx, "gc_fine_doppler_create: NULL context");
     gc_device_guard g(ctx->device);
-    gc_fine_doppler* f = new gc_fine_doppler();
+    std::unique_ptr<gc_fine_doppler> f(new gc_fine_doppler());  // behind the guard: freed on its device if an allocation fails
     f->ctx = ctx;
     f->ctx_ref.bind(ctx);
     f->conf = *conf;
@@ -155,35 +142,29 @@ gc_status gc_fine_doppler_create(gc_ctx* ctx, const gc_fine_doppler_conf* conf, 
     f->stride = (uint32_t)max_bins;
     f->has_code.assign(n_slots, 0);
     const size_t ns = (size_t)n_slots;
-    hipError_t e = hipMalloc(&f->d_codes, sizeof(float2) * ns * conf->samples_per_code);
-    if (e == hipSuccess) e = hipMalloc(&f->d_block, sizeof(float2) * f->total);
-    if (e == hipSuccess) e = hipMalloc(&f->d_req, sizeof(AcqFineRequest) * ns);
-    if (e == hipSuccess) e = hipMalloc(&f->d_partial, sizeof(float2) * ns * f->n_tiles * f->stride);
-    if (e == hipSuccess) e = hipMalloc(&f->d_energy, sizeof(float) * ns * f->n_tiles);
-    if (e == hipSuccess) e = hipMalloc(&f->d_spec, sizeof(float) * ns * f->stride);
-    if (e == hipSuccess) e = hipMalloc(&f->d_results, sizeof(gc_fine_doppler_result) * ns);
-    if (e == hipSuccess) e = hipHostMalloc(&f->h_req, sizeof(AcqFineRequest) * ns);
-    if (e == hipSuccess) e = hipHostMalloc(&f->h_results, sizeof(gc_fine_doppler_result) * ns);
-    if (e != hipSuccess)
-        {
-            fine_release(f);
-            delete f;
-            return gc_fail(GC_ERR_HIP, "gc_fine_doppler_create: allocation failed: %s", hipGetErrorString(e));
-        }
-    *out = f;
+    hipError_t e = f->d_codes.alloc(ns * conf->samples_per_code);
+    if (e == hipSuccess) e = f->d_block.alloc(f->total);
+    if (e == hipSuccess) e = f->d_req.alloc(ns);
+    if (e == hipSuccess) e = f->d_partial.alloc(ns * f->n_tiles * f->stride);
+    if (e == hipSuccess) e = f->d_energy.alloc(ns * f->n_tiles);
+    if (e == hipSuccess) e = f->d_spec.alloc(ns * f->stride);
+    if (e == hipSuccess) e = f->d_results.alloc(ns);
+    if (e == hipSuccess) e = f->h_req.alloc(ns);
+    if (e == hipSuccess) e = f->h_results.alloc(ns);
+    if (e != hipSuccess) return gc_fail(GC_ERR_HIP, "gc_fine_doppler_create: allocation failed: %s", hipGetErrorString(e));
+    *out = f.release();
     return GC_OK;
 }
 
 gc_status gc_fine_doppler_destroy(gc_fine_doppler* f)
 {
     GC_REQUIRE(f, "gc_fine_doppler_destroy: NULL handle");
+    gc_device_guard g(f->ctx->device);
     {
-        gc_device_guard g(f->ctx->device);
         std::lock_guard<std::mutex> lk(f->ctx->mtx);
         (void)hipStreamSynchronize(f->ctx->stream);
-        fine_release(f);
     }
-    delete f;
+    delete f;  // the buffers go with it, on their device; the mutex may go with the context
     return GC_OK;
 }
 

@@ -7,6 +7,8 @@
 #include <cstdarg>
 #include <atomic>
 #include <cstdio>
+#include <cstring>
+#include <memory>
 #include <mutex>
 
 // Experiment switches (measured-slower kernels and their tuning variables) exist only in builds made with
@@ -88,6 +90,52 @@ struct gc_device_guard
         if (prev >= 0) (void)hipSetDevice(prev);
     }
 };
+
+// Move-only owners of hipMalloc (gc_dev_buf<T>) and hipHostMalloc (gc_host_buf<T>) memory, as members of a handle struct: the
+// handle's destructor frees them, so a create function that fails half way and a destroy function need no list of frees.  Declare
+// the handle's gc_ctx_ref BEFORE its buffers (members are destroyed in reverse order: the context outlives the frees) and delete the
+// handle under a gc_device_guard of its device.  A buffer converts to T*, so launch sites read as they would with a plain pointer.
+struct gc_device_mem
+{
+    static hipError_t alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+    static hipError_t zero(void* p, size_t bytes) { return hipMemset(p, 0, bytes); }
+    static void release(void* p) { (void)hipFree(p); }
+};
+
+struct gc_pinned_mem
+{
+    static hipError_t alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    static hipError_t zero(void* p, size_t bytes) { return std::memset(p, 0, bytes), hipSuccess; }
+    static void release(void* p) { (void)hipHostFree(p); }
+};
+
+template <typename T, typename Mem>
+struct gc_owned_buf
+{
+    struct Release
+    {
+        void operator()(T* q) const { Mem::release(q); }
+    };
+    std::unique_ptr<T, Release> p;
+    // n elements, uninitialised or zero-filled (synchronously); what was held before is freed first
+    hipError_t alloc(size_t n, bool zero_fill = false)
+    {
+        p.reset();
+        void* q = nullptr;
+        const hipError_t e = Mem::alloc(&q, n * sizeof(T));
+        if (e != hipSuccess) return e;
+        p.reset(static_cast<T*>(q));
+        return zero_fill ? Mem::zero(q, n * sizeof(T)) : hipSuccess;
+    }
+    void reset() { p.reset(); }
+    T* get() const { return p.get(); }
+    operator T*() const { return p.get(); }
+};
+
+template <typename T>
+using gc_dev_buf = gc_owned_buf<T, gc_device_mem>;
+template <typename T>
+using gc_host_buf = gc_owned_buf<T, gc_pinned_mem>;
 
 static inline hipStream_t gc_pick_stream(gc_ctx* ctx, void* stream)
 {
