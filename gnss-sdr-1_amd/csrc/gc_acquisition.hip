@@ -1252,7 +1252,8 @@ static gc_status acq_search_stream(gc_acq* a, const char* who, gc_stream* s, uin
     if (rs != GC_OK) return rs;
     const gc_stream_ticket& t = reads.ticket(0);
     const uint64_t span = (uint64_t)n * a->sz.consumed;
-    if (first_index + span > t.head)
+    // (head - first_index, not first_index + span: the sum wraps for an index near 2^64)
+    if (first_index > t.head || span > t.head - first_index)
         return gc_fail(GC_ERR_INVALID, "%s: blocks [%llu, +%llu) are not inside the stream's resident samples [%llu, %llu)", who,
             (unsigned long long)first_index, (unsigned long long)span, (unsigned long long)t.oldest, (unsigned long long)t.head);
     for (uint32_t k = 0; k < n; k++)

@@ -199,7 +199,8 @@ gc_status gc_fine_doppler_estimate_stream(gc_fine_doppler* f, gc_stream* s, uint
     rs = reads.add(s, first_index);
     if (rs != GC_OK) return rs;
     const gc_stream_ticket& t = reads.ticket(0);
-    if (first_index + f->total > t.head)
+    // (head - first_index, not first_index + total: the sum wraps for an index near 2^64)
+    if (first_index > t.head || f->total > t.head - first_index)
         return gc_fail(GC_ERR_INVALID, "%s: block [%llu, +%u) is not inside the stream's resident samples [%llu, %llu)", who,
             (unsigned long long)first_index, f->total, (unsigned long long)t.oldest, (unsigned long long)t.head);
     rs = fine_enqueue(f, s->d_ring, (unsigned)s->capacity, first_index, s->iq_format, req, st);

@@ -4,8 +4,9 @@
 // at 1 / D of the rate.  Nothing crosses the host link a second time.
 //
 // The life cycle is the derived ring's (gc_ring_stage.h); the decimator's own are its arguments, its writer and its index
-// functions: output m is always source sample mD -- the decimator starts at sample 0 of the source -- and reads back to
-// max(0, mD - (T - 1)).  The taps of the reference's acquisition resampler come from gc_acq_resampler_plan (gc_numerics.cpp).
+// functions: output m is always source sample mD and reads back to max(0, mD - (T - 1)) -- on a source at origin 0 the decimator
+// starts at output 0, whose window reaches in front of the stream; on a source with another origin at the first output whose whole
+// window lies at or above it (gc_derived_ring_open).  The taps of the reference's acquisition resampler come from gc_acq_resampler_plan (gc_numerics.cpp).
 //
 // The output ring may have any gc_iq_format: the kernel's store epilogue (cond_store_epilogue.h, the conditioner's) scales, clamps
 // and rounds into a GC_IQ_I16 / GC_IQ_I8 ring and counts the clipped components.
@@ -74,15 +75,16 @@ gc_status gc_ring_decimator_create(gc_ctx* ctx, gc_stream* src_ring, uint32_t de
     GC_REQUIRE(out_ring->iq_format == GC_IQ_F32 || out_ring->quantised_output,
         "gc_ring_decimator_create: the output ring must be GC_IQ_F32, or an integer ring opened with gc_stream_accept_quantised_output");
     gc_ring_decimator* d = new gc_ring_decimator();
-    st = gc_derived_ring_open(who, &d->ring, ctx, src_ring, out_ring);
+    d->decimation = decimation;
+    d->n_taps = n_taps;
+    const rdec_writer index_rule(d);
+    st = gc_derived_ring_open(who, &d->ring, ctx, src_ring, out_ring, &index_rule, n_taps - 1);
     if (st != GC_OK)
         {
             delete d;
             return st;
         }
     gc_device_guard g(ctx->device);
-    d->decimation = decimation;
-    d->n_taps = n_taps;
     hipError_t e = hipMalloc(&d->d_taps, sizeof(float) * n_taps);
     if (e == hipSuccess) e = hipMemcpy(d->d_taps, taps, sizeof(float) * n_taps, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = gc_quantised_output_alloc(&d->quant, out_ring);

@@ -112,19 +112,23 @@ gc_status gc_ring_resampler_create(gc_ctx* ctx, gc_stream* src_ring, const gc_re
         GC_REQUIRE(out_ring->iq_format == src_ring->iq_format,
             "gc_ring_resampler_create: direct mode moves samples as they are: the output ring must have the source ring's format");
     gc_ring_resampler* d = new gc_ring_resampler();
-    st = gc_derived_ring_open(who, &d->ring, ctx, src_ring, out_ring);
+    d->ratio = ratio;
+    if (poly)
+        {
+            d->log2_phases = log2_of(conf->phases);
+            d->taps = (int)conf->taps_per_phase;
+        }
+    const rres_writer index_rule(d);
+    st = gc_derived_ring_open(who, &d->ring, ctx, src_ring, out_ring, &index_rule, (uint64_t)(d->taps - 1));
     if (st != GC_OK)
         {
             delete d;
             return st;
         }
     gc_device_guard g(ctx->device);
-    d->ratio = ratio;
     hipError_t e = hipSuccess;
     if (poly)
         {
-            d->log2_phases = log2_of(conf->phases);
-            d->taps = (int)conf->taps_per_phase;
             // rows at the pitch the kernel keeps them at in LDS
             const int pitch = ring_resamp_bank_pitch(d->taps);
             std::vector<float> rows((size_t)conf->phases * pitch, 0.0f);

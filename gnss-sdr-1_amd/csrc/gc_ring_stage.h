@@ -74,9 +74,16 @@ struct gc_derived_writer : gc_ring_writer
 // them come the stage's own arguments, before anything that needs a device or a ring.
 // NULL arguments (`handle_out`: where create returns the handle), the same ring twice, a ring of another context
 gc_status gc_derived_ring_check(const char* who, const gc_ctx* ctx, const gc_stream* src, const gc_stream* out, const void* handle_out);
-// a source that no longer holds sample 0, an output ring that is not empty or has a producer; then `r` is bound: it keeps the
-// context and both rings and is the output ring's producer until gc_derived_ring_release
-gc_status gc_derived_ring_open(const char* who, gc_derived_ring* r, gc_ctx* ctx, gc_stream* src, gc_stream* out);
+// a source that no longer holds its first sample, an output ring that is not empty or has a producer; then `r` is bound: it keeps
+// the context and both rings and is the output ring's producer until gc_derived_ring_release.
+// A source with an origin other than 0 (gc_stream_debug_set_origin, or the output ring of such a stage) is taken only by a stage
+// that passes its `index_rule` (nullptr: GC_ERR_STATE, the message names the origin) and only while nothing has been evicted
+// since the origin.  The stage's first output is then the first m whose whole window -- `history` source samples in front of its
+// newest one -- lies at or above the origin, index_rule->available_at(origin + history); the output ring receives that m as ITS
+// origin and r->out_head starts there, so nothing in front of the source's origin is ever read.
+static const uint64_t GC_DERIVED_MAX_SOURCE_ORIGIN = 1ull << 55;  // times the largest rate ratio (64) it stays below GC_STREAM_MAX_ORIGIN
+gc_status gc_derived_ring_open(const char* who, gc_derived_ring* r, gc_ctx* ctx, gc_stream* src, gc_stream* out, const gc_derived_writer* index_rule = nullptr,
+    uint64_t history = 0);
 // after a failed gc_derived_ring_open as well; the stage frees what its kernels read AFTER it (it waits for them)
 void gc_derived_ring_release(gc_derived_ring* r);
 // <stage>_update behind the handle check.  who: the public function; noun: "decimator", "resampler".  More outputs than the ring

@@ -77,17 +77,44 @@ gc_status gc_derived_ring_check(const char* who, const gc_ctx* ctx, const gc_str
     return GC_OK;
 }
 
-gc_status gc_derived_ring_open(const char* who, gc_derived_ring* r, gc_ctx* ctx, gc_stream* src, gc_stream* out)
+gc_status gc_derived_ring_open(const char* who, gc_derived_ring* r, gc_ctx* ctx, gc_stream* src, gc_stream* out, const gc_derived_writer* index_rule,
+    uint64_t history)
 {
+    uint64_t origin = 0;
     {
         std::lock_guard<std::mutex> lk(src->mtx);
-        if (gc_stream_oldest(src) != 0)
+        origin = src->origin;
+        if (origin != 0 && !index_rule)
+            return gc_fail(GC_ERR_STATE, "%s: the source ring starts at origin %llu: this stage reads a source that starts at sample 0 only", who,
+                (unsigned long long)origin);
+        if (origin == 0 && gc_stream_oldest(src) != 0)
             return gc_fail(GC_ERR_STATE, "%s: the source ring no longer holds sample 0 (its oldest sample is %llu)", who,
                 (unsigned long long)gc_stream_oldest(src));
+        if (gc_stream_oldest(src) != origin)
+            return gc_fail(GC_ERR_STATE, "%s: the source ring no longer holds its origin, sample %llu (its oldest sample is %llu)", who,
+                (unsigned long long)origin, (unsigned long long)gc_stream_oldest(src));
+        GC_REQUIRE(origin <= GC_DERIVED_MAX_SOURCE_ORIGIN, "%s: the source ring's origin %llu is above 2^55", who, (unsigned long long)origin);
+    }
+    // origin 0: output 0, whose window reaches in front of the stream and reads zeros there, as ever.  Any other origin: the first
+    // output whose whole window lies at or above it -- as many outputs as have their newest sample below origin + history come before
+    const uint64_t first_out = origin != 0 ? index_rule->available_at(origin + history) : 0;
+    {
+        // (claim would report the head of such a ring as samples that have been pushed)
+        std::lock_guard<std::mutex> lk(out->mtx);
+        if (out->origin != 0 && out->head == out->origin && !out->kernel_fed)
+            return gc_fail(GC_ERR_STATE, "%s: the output ring has an origin of its own (%llu): a derived ring receives its origin from the stage", who,
+                (unsigned long long)out->origin);
     }
     const unsigned why = gc_ring_stage_claim(out);
     GC_REQUIRE(!(why & GC_RING_HAS_SAMPLES), "%s: samples have been pushed into the output ring already", who);
     if (why) return gc_fail(GC_ERR_STATE, "%s: the output ring already has a producer on the device", who);
+    if (first_out != 0)
+        {
+            std::lock_guard<std::mutex> no_push(out->push_mtx);
+            std::lock_guard<std::mutex> lk(out->mtx);
+            gc_stream_set_origin_locked(out, first_out);
+        }
+    r->out_head = first_out;
     r->ctx = ctx;
     r->ctx_ref.bind(ctx);
     r->src = src;

@@ -33,6 +33,8 @@ struct gc_stream
     char* d_base = nullptr;  // the allocation (hipFree takes this): guard band, ring storage, guard band (layout: gc_stream.hip)
     size_t guard_bytes = 0;  // bytes of each guard band: a multiple of 4096
     uint64_t head = 0;       // absolute index one past the newest sample
+    uint64_t origin = 0;     // absolute index of the first sample the ring ever holds: 0, or what gc_stream_set_origin_locked set
+    bool origin_set = false; // an origin has been given (once, to an empty ring): by gc_stream_debug_set_origin or by a derived stage
     hipStream_t copy_stream = nullptr;
     hipEvent_t pushed = nullptr;  // completion of the newest push
     bool has_pushed = false;
@@ -84,6 +86,19 @@ static inline uint64_t gc_stream_oldest(const gc_stream* s)
 {
     const uint64_t o = s->head > s->capacity ? s->head - s->capacity : 0;
     return o > s->evicting_below ? o : s->evicting_below;
+}
+
+// largest origin a ring takes: head arithmetic and index * decimation products stay far below 2^64 behind it
+static const uint64_t GC_STREAM_MAX_ORIGIN = 1ull << 62;
+// The ring starts at `origin` as if that many samples had been pushed and evicted: head, the oldest resident sample and the first
+// push's first_index are `origin`, whose storage position is origin % capacity.  The caller holds push_mtx and mtx and has checked
+// that the ring is empty (head 0), has no producer and no origin yet.
+static inline void gc_stream_set_origin_locked(gc_stream* s, uint64_t origin)
+{
+    s->origin = origin;
+    s->origin_set = true;
+    s->head = origin;
+    s->evicting_below = origin;
 }
 
 // A reserved read of the ring: slot of the reader table + the resident range [oldest, head) at the moment of the reservation.

@@ -5,7 +5,8 @@
 // Layout: a ring of `capacity` samples in HBM followed by a mirror of its first `max_window` samples, so
 // that any window of <= max_window samples is contiguous wherever it starts: sample a lives at a % capacity
 // and, when that is < max_window, also at capacity + a % capacity.  Kernels index with absolute sample
-// numbers (TrkChan::ring_len).  Pushes run on the stream's own HIP stream through pinned staging slots and
+// numbers (TrkChan::ring_len), 64 bits wide and counted from the ring's origin: 0, or what gc_stream_debug_set_origin (a test's
+// handle) or a derived stage gave the empty ring, which then starts as if that many samples had been pushed and evicted.  Pushes run on the stream's own HIP stream through pinned staging slots and
 // overlap with compute; a push waits only for kernels that may still read the samples it evicts.
 //
 // The allocation, front to back:
@@ -295,7 +296,7 @@ gc_status gc_stream_accept_quantised_output(gc_stream* s)
     std::lock_guard<std::mutex> no_push(s->push_mtx);
     std::lock_guard<std::mutex> lk(s->mtx);
     if (s->kernel_fed) return gc_fail(GC_ERR_STATE, "gc_stream_accept_quantised_output: the ring already has a producer on the device");
-    if (s->head != 0) return gc_fail(GC_ERR_STATE, "gc_stream_accept_quantised_output: samples have been pushed into the ring already");
+    if (s->head != s->origin) return gc_fail(GC_ERR_STATE, "gc_stream_accept_quantised_output: samples have been pushed into the ring already");
     s->quantised_output = true;
     return GC_OK;
 }
@@ -357,6 +358,19 @@ gc_status gc_stream_debug_guards(gc_stream* s, int32_t* front_intact, int32_t* b
             GC_HIP(hipMemcpy(band.data(), at[i], band.size(), hipMemcpyDeviceToHost));
             *intact[i] = std::all_of(band.begin(), band.end(), [](unsigned char b) { return b == GC_STREAM_GUARD_BYTE; }) ? 1 : 0;
         }
+    return GC_OK;
+}
+
+gc_status gc_stream_debug_set_origin(gc_stream* s, uint64_t origin)
+{
+    GC_REQUIRE(s, "gc_stream_debug_set_origin: NULL handle");
+    GC_REQUIRE(origin <= GC_STREAM_MAX_ORIGIN, "gc_stream_debug_set_origin: origin %llu is above 2^62", (unsigned long long)origin);
+    std::lock_guard<std::mutex> no_push(s->push_mtx);
+    std::lock_guard<std::mutex> lk(s->mtx);
+    if (s->kernel_fed) return gc_fail(GC_ERR_STATE, "gc_stream_debug_set_origin: the ring has a producer on the device");
+    if (s->origin_set) return gc_fail(GC_ERR_STATE, "gc_stream_debug_set_origin: the ring has an origin already (%llu)", (unsigned long long)s->origin);
+    if (s->head != 0) return gc_fail(GC_ERR_STATE, "gc_stream_debug_set_origin: samples have been pushed into the ring already");
+    gc_stream_set_origin_locked(s, origin);
     return GC_OK;
 }
 

@@ -431,6 +431,10 @@ static gc_status batch_launch(gc_trk_batch* b, int n_epochs, const gc_epoch_para
             const gc_status rs = reads.add(rings[i], floor);
             if (rs != GC_OK) return rs;
             const gc_stream_ticket& t = reads.ticket((int)i);
+            // a floor above the head protects nothing: a later push would evict, unhindered, whatever the records of this launch read
+            if (floor != GC_STREAM_FLOOR_OLDEST && floor > t.head)
+                return gc_fail(GC_ERR_INVALID, "gc_trk_batch_run: the read floor %llu lies above the stream's resident samples [%llu, %llu)",
+                    (unsigned long long)floor, (unsigned long long)t.oldest, (unsigned long long)t.head);
             if (ends && (*ends)[i] > t.head)
                 return gc_fail(GC_ERR_INVALID, "gc_trk_batch_run: a window ends at sample %llu, the stream's resident samples are [%llu, %llu)",
                     (unsigned long long)(*ends)[i], (unsigned long long)t.oldest, (unsigned long long)t.head);
@@ -472,7 +476,8 @@ gc_status gc_trk_batch_run(gc_trk_batch* b, int n_epochs, const gc_epoch_params*
                     gc_stream_info(r, &oldest, &head, nullptr);
                     GC_REQUIRE((uint64_t)p.n_samples <= r->mirror, "gc_trk_batch_run: job %zu is longer than the stream's max_window %llu", j,
                         (unsigned long long)r->mirror);
-                    GC_REQUIRE(p.sample_offset >= oldest && p.sample_offset + (uint64_t)p.n_samples <= head,
+                    // (head - sample_offset, not sample_offset + n_samples: the sum wraps for an offset near 2^64)
+                    GC_REQUIRE(p.sample_offset >= oldest && p.sample_offset <= head && (uint64_t)p.n_samples <= head - p.sample_offset,
                         "gc_trk_batch_run: job %zu window [%llu, +%d) is not inside the stream's resident samples [%llu, %llu)", j,
                         (unsigned long long)p.sample_offset, p.n_samples, (unsigned long long)oldest, (unsigned long long)head);
                     const size_t ri = std::find(rings.begin(), rings.end(), r) - rings.begin();
@@ -481,7 +486,7 @@ gc_status gc_trk_batch_run(gc_trk_batch* b, int n_epochs, const gc_epoch_params*
                 }
             else
                 {
-                    GC_REQUIRE(p.sample_offset + (uint64_t)p.n_samples <= c.n_iq,
+                    GC_REQUIRE(p.sample_offset <= c.n_iq && (uint64_t)p.n_samples <= c.n_iq - p.sample_offset,
                         "gc_trk_batch_run: job %zu window [%llu, +%d) exceeds the channel's %llu samples", j,
                         (unsigned long long)p.sample_offset, p.n_samples, (unsigned long long)c.n_iq);
                 }

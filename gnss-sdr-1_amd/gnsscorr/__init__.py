@@ -266,6 +266,7 @@ API = {
     "gc_stream_read": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp]),
     "gc_stream_debug_read_storage": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _vp]),
     "gc_stream_debug_guards": (C.c_int, [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "gc_stream_debug_set_origin": (C.c_int, [_vp, C.c_uint64]),
     "gc_stream_accept_quantised_output": (C.c_int, [_vp]),
     "gc_conditioner_conf_size": (C.c_size_t, []),
     "gc_conditioner_create": (C.c_int, [_vp, C.POINTER(ConditionerConf), _fp, _vp, C.POINTER(_vp)]),
@@ -795,6 +796,15 @@ class IqStream:
         front, back = C.c_int32(0), C.c_int32(0)
         _check(load_library().gc_stream_debug_guards(self._h, C.byref(front), C.byref(back)))
         return bool(front.value), bool(back.value)
+
+    def set_origin(self, origin):
+        """gc_stream_debug_set_origin (diagnostic): the empty ring starts at sample number `origin` (<= 2^62) as if that many samples
+        had been pushed and evicted.  Once, before the first push and before a stage claims the ring.  Returns self."""
+        origin = int(origin)
+        if not 0 <= origin < 1 << 64:
+            raise ValueError("origin is outside 0 .. 2^64 - 1")
+        _check(load_library().gc_stream_debug_set_origin(self._h, origin))
+        return self
 
     def close(self):
         if self._h:

@@ -196,9 +196,24 @@ gc_status gc_stream_read(gc_stream* s, uint64_t first_index, uint64_t n_samples,
  * that reads a window through the mirror sees.  Synchronous: waits for what has been enqueued on the ring.  GC_ERR_INVALID when
  * the range leaves the storage.
  * gc_stream_debug_guards copies both guard bands to the host and reports, as 1 or 0, whether every byte of the band in front of
- * the ring and of the band behind it still holds the fill: a 0 means that something stored outside the ring's storage. */
+ * the ring and of the band behind it still holds the fill: a 0 means that something stored outside the ring's storage.
+ * gc_stream_debug_set_origin makes an empty ring start at sample number `origin` instead of 0, as if `origin` samples had been
+ * pushed and evicted: gc_stream_info reports oldest_index == head_index == origin, the first push returns first_index == origin
+ * and lands at storage position origin % capacity_samples (mirror included), everything below `origin` is not resident to any
+ * reader, and the storage stays zero-filled.  It lets a test run the readers of a ring at the sample numbers of a stream that has
+ * been running for hours (past 2^31, 2^32, 2^53) without pushing that many samples; a receiver never calls it.  Allowed once, on a
+ * ring that holds nothing and has no producer on the device (GC_ERR_STATE otherwise, nothing changes); an origin above 2^62 is
+ * GC_ERR_INVALID -- a condition of this hook, which keeps head arithmetic and index * decimation products of a test from
+ * wrapping, not a limit of the ring.  Origin 0, the default, is a ring as it always was.
+ * A ring with an origin other than 0 can be the SOURCE of a gc_ring_decimator and of a gc_ring_resampler, while nothing has been
+ * evicted from it since the origin: the stage's first output is the first one whose whole input window lies at or above the
+ * origin, and the output ring receives that output's number as its own origin (so nothing in front of the origin is ever read).
+ * gc_ring_notch_create refuses such a source with GC_ERR_STATE; a gc_conditioner and a gc_signal_generator number their own
+ * input and take an output ring with origin 0 only, and so does every derived stage: an OUTPUT ring gets its origin from the
+ * stage, never from this call. */
 gc_status gc_stream_debug_read_storage(gc_stream* s, uint64_t first_position, uint64_t n_samples, void* host_out);
 gc_status gc_stream_debug_guards(gc_stream* s, int32_t* front_intact, int32_t* back_intact);
+gc_status gc_stream_debug_set_origin(gc_stream* s, uint64_t origin);
 
 /* ------------------------------------------------------------------------ */
 /* Signal conditioner: a frequency-translating FIR decimator in front of a      */
@@ -464,7 +479,10 @@ gc_status gc_trk_batch_set_input_dev(gc_trk_batch* b, int ch, const void* dev_iq
  * ABSOLUTE sample number of that stream and n_samples <= the stream's max_window.  gc_trk_batch_run checks
  * every window against the resident range; gc_trk_batch_run_dev cannot (parameters live in HBM): tell it the
  * oldest sample its launches read with set_read_floor so that later pushes need not wait for them (default:
- * everything resident, i.e. the next evicting push waits for the launch). */
+ * everything resident, i.e. the next evicting push waits for the launch).  A floor below the resident range
+ * is GC_ERR_STATE at the launch, a floor above the ring's head GC_ERR_INVALID: it would protect nothing the
+ * launch reads.  A window whose sample_offset + n_samples passes 2^64 is refused like any other that is not
+ * resident. */
 gc_status gc_trk_batch_set_input_stream(gc_trk_batch* b, int ch, gc_stream* s);
 gc_status gc_trk_batch_set_read_floor(gc_trk_batch* b, uint64_t oldest_index_read);
 /* Correlates n_epochs epochs of every channel.  dev_params: n_channels*n_epochs

@@ -48,6 +48,26 @@ def condition(raw, taps, decimation, translate_hz, fs_in, first_out=0, n_out=Non
     return y
 
 
+def decimate_from(origin, samples, taps, decimation, head=None):
+    """The ring decimator (no mixer) on a source whose first sample `samples[0]` has the absolute number `origin`: (m0, y) with
+    y[j] = sum_k h[k] x[(m0 + j) D - k] (complex128) for every output the source samples below `head` (an absolute number; all of
+    `samples` by default) complete, from the first output m0 whose whole window lies at or above the origin on:
+    m0 = ceil((origin + T - 1) / D).  Nothing in front of the origin is read.  Index arithmetic in Python integers."""
+    x = to_complex(samples)
+    h = np.asarray(taps, np.float64)
+    D, T = int(decimation), len(h)
+    origin = int(origin)
+    head = origin + len(x) if head is None else int(head)
+    m0 = -((-(origin + T - 1)) // D)
+    m1 = max(m0, -((-head) // D))  # outputs m with m D < head
+    rel = np.array([m * D - origin for m in range(m0, m1)], np.int64)
+    assert rel.size == 0 or (rel[0] >= T - 1 and rel[-1] < len(x))
+    y = np.zeros(len(rel), np.complex128)
+    for k in range(T):
+        y += h[k] * x[rel - k]
+    return m0, y
+
+
 def error_bound(taps, raw):
     """(T + 16) 2^-23 sum|h| max|x|: one float32 rounding per product and per sum, plus a few ulp for the mixer."""
     h = np.asarray(taps, np.float64)

@@ -88,6 +88,61 @@ def polyphase(raw, bank, fs_in, fs_out, head=None):
     return y
 
 
+def first_output(kind, step, origin, taps=1):
+    """The first output m whose whole window -- source samples n_m - (taps - 1) .. n_m -- lies at or above `origin`: as many
+    outputs as have their source sample below origin + taps - 1 come before it.  Python integers."""
+    return available(kind, step, int(origin) + int(taps) - 1)
+
+
+def _exact_source_index(kind, step, m):
+    """n_m as Python integers, for output numbers of any size."""
+    if kind == DOWN:
+        return [-((-v * M) // step) for v in m]
+    if kind == UP:
+        return [((v + 1) * step) // M for v in m]
+    if kind == POLY:
+        return [(v * step) // M for v in m]
+    return list(m)
+
+
+def direct_from(origin, samples, fs_in, fs_out, head=None):
+    """Direct mode on a source whose first sample `samples[0]` has the absolute number `origin`: (m0, outputs) with m0 the first
+    output whose source sample lies at or above the origin and outputs[j] = sample number n_{m0 + j}, for every output the source
+    samples below `head` (an absolute number; all of `samples` by default) complete.  Index arithmetic in Python integers."""
+    samples = np.asarray(samples)
+    origin = int(origin)
+    kind, step = direct_ratio(fs_in, fs_out)
+    head = origin + len(samples) if head is None else int(head)
+    m0 = first_output(kind, step, origin)
+    m1 = max(m0, available(kind, step, head))
+    n = _exact_source_index(kind, step, range(m0, m1))
+    assert all(origin <= v < head for v in n)
+    return m0, samples[np.array([v - origin for v in n], np.int64)]
+
+
+def polyphase_from(origin, samples, bank, fs_in, fs_out, head=None):
+    """Polyphase mode on a source that starts at the absolute number `origin`: (m0, outputs as complex128) from the first output
+    whose whole window of T samples lies at or above the origin on; nothing in front of the origin is read."""
+    x = to_complex(samples)
+    H = np.asarray(bank, np.float64)
+    P, T = H.shape
+    log2p = int(P).bit_length() - 1
+    origin = int(origin)
+    kind, inc = poly_ratio(fs_in, fs_out)
+    head = origin + len(x) if head is None else int(head)
+    m0 = first_output(kind, inc, origin, T)
+    m1 = max(m0, available(kind, inc, head))
+    ms = range(m0, m1)
+    n = _exact_source_index(kind, inc, ms)
+    assert all(origin + T - 1 <= v < head for v in n)
+    rel = np.array([v - origin for v in n], np.int64)
+    p = np.array([((v * inc) & (M - 1)) >> (32 - log2p) for v in ms], np.int64)
+    y = np.zeros(len(rel), np.complex128)
+    for k in range(T):
+        y += H[p, k] * x[rel - k]
+    return m0, y
+
+
 def error_bound(bank, raw):
     """(T + 16) 2^-23 max_p sum_k |H[p][k]| max|x|: one float32 rounding per product and per sum over the worst phase row."""
     H = np.abs(np.asarray(bank, np.float64))

@@ -6,7 +6,11 @@ append(samples) is one call of a producer.  A call of more than `capacity` sampl
 derived rings' update and the signal generator do that; gc_stream_push and the conditioner refuse such a call), each run is
 cut at the wrap as gc_stream_produce cuts it, and each piece (pos, len) is written to pos .. pos + len and, where pos < max_window,
 its first min(len, max_window - pos) samples to capacity + pos as well.  Every piece and every call is recorded: classify() says
-which of the piece classes a schedule has reached, tests/ring_contract_cases.py names them."""
+which of the piece classes a schedule has reached, tests/ring_contract_cases.py names them.
+
+origin: the ring starts at that absolute sample number (gc_stream_debug_set_origin, or the origin a derived stage gives its output
+ring) as if `origin` samples had been appended and evicted: the first piece lands at origin % capacity, the storage stays zero, and
+resident() is [max(origin, head - capacity), head).  All of it in Python integers, whatever the size of the origin."""
 import numpy as np
 
 SLACK = 2
@@ -14,13 +18,14 @@ CLASSES = ("A", "B", "C", "D_even", "D_odd", "E", "F_capacity-1", "F_0", "F_wind
 
 
 class RingModel:
-    def __init__(self, capacity, max_window, dtype, per=1):
+    def __init__(self, capacity, max_window, dtype, per=1, origin=0):
         """dtype / per: complex64 / 1 for a GC_IQ_F32 ring ([n] arrays), int16 or int8 / 2 for the integer rings ([n, 2])."""
-        assert 0 < max_window and 2 * max_window <= capacity
+        assert 0 < max_window and 2 * max_window <= capacity and int(origin) >= 0
         self.capacity, self.max_window = int(capacity), int(max_window)
         self.total = self.capacity + self.max_window + SLACK
         self.storage = np.zeros(self.total if per == 1 else (self.total, per), dtype)
-        self.head = 0
+        self.origin = int(origin)
+        self.head = self.origin
         self.pieces = []  # (pos, len) of every contiguous piece, in order
         self.calls = []   # samples of every append
 
@@ -44,6 +49,14 @@ class RingModel:
             self.pieces.append((pos, n))
             self.head += n
             done += n
+
+    def resident(self):
+        """(oldest, head) as gc_stream_info reports them."""
+        return max(self.origin, self.head - self.capacity), self.head
+
+    def position(self, index):
+        """Storage position of the absolute sample number `index`."""
+        return int(index) % self.capacity
 
     def region(self, position):
         return "ring" if position < self.capacity else "mirror" if position < self.capacity + self.max_window else "slack"

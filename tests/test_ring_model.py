@@ -39,6 +39,53 @@ def test_model_is_the_definition_on_random_schedules(capacity, window):
         assert all(n > 0 and pos + n <= capacity for pos, n in m.pieces)
 
 
+def _by_definition_from(capacity, window, origin, samples):
+    """The same with sample number origin + i for samples[i]: Python integers, one sample at a time."""
+    storage = np.zeros(capacity + window + ring_model.SLACK, samples.dtype)
+    for i, v in enumerate(samples):
+        p = (origin + i) % capacity
+        storage[p] = v
+        if p < window:
+            storage[capacity + p] = v
+    return storage
+
+
+@pytest.mark.parametrize("origin", [0, 1, 3000, (1 << 31) - 49, (1 << 32) - 1501, (1 << 40) + 12345, (1 << 53) + 1, 1 << 62])
+@pytest.mark.parametrize("capacity, window", [(3001, 96), (101, 7), (20, 1)])
+def test_model_with_an_origin_is_the_definition(capacity, window, origin):
+    """Positions, mirror parts and the resident range of pushes that start at an origin, on schedules that wrap the ring more than
+    twice behind it."""
+    rng = np.random.Generator(np.random.PCG64(capacity + origin % 1000))
+    calls = [int(n) for n in rng.integers(0, capacity + 1, 10)] + [1, capacity, capacity - 1]
+    rng.shuffle(calls)
+    assert sum(calls) > 2 * capacity
+    x = (np.arange(sum(calls)) + 1).astype(np.int32)
+    m = ring_model.RingModel(capacity, window, np.int32, origin=origin)
+    assert m.resident() == (origin, origin) and not m.storage.any()
+    first = 0
+    for n in calls:
+        at = len(m.pieces)
+        m.append(x[first:first + n])
+        if n:
+            assert m.pieces[at][0] == (origin + first) % capacity == m.position(origin + first)
+        first += n
+        assert isinstance(m.head, int) and m.head == origin + first
+        assert m.resident() == (max(origin, origin + first - capacity), origin + first)
+        assert np.array_equal(m.storage, _by_definition_from(capacity, window, origin, x[:first])), n
+        assert not m.storage[capacity + window:].any()
+    assert sum(n for _, n in m.pieces) == len(x) and all(n > 0 and pos + n <= capacity for pos, n in m.pieces)
+    # a ring at origin 0 that first receives origin % capacity other samples holds the later ones at the same positions
+    lead = origin % capacity
+    twin = ring_model.RingModel(capacity, window, np.int32)
+    twin.append(np.full(lead, -7, np.int32))
+    twin.append(x)
+    assert twin.head - lead == m.head - origin
+    keep = min(len(x), capacity)  # the newest `keep` samples are resident in both
+    for i in range(len(x) - keep, len(x)):
+        assert m.position(origin + i) == twin.position(lead + i)
+    assert np.array_equal(twin.storage, m.storage)  # more than a ring's worth was appended: nothing of the lead is left
+
+
 def test_two_component_samples_and_the_first_difference():
     m = ring_model.RingModel(10, 4, np.int16, per=2)
     x = np.arange(1, 27, dtype=np.int16).reshape(13, 2)
