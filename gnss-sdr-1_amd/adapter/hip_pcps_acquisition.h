@@ -17,9 +17,7 @@
 #ifndef GNSSCORR_HIP_PCPS_ACQUISITION_H_
 #define GNSSCORR_HIP_PCPS_ACQUISITION_H_
 
-#include "gnss_sdr_types.h"
-#include "gnsscorr.h"
-#include "hip_multicorrelator_real_codes.h"  // gnsscorr::shared_context()
+#include "acquisition_block_base.h"  // engine owner, synchro clearing
 #include "mat5_writer.h"
 #include <cmath>
 #include <cstring>
@@ -75,14 +73,6 @@ public:
             }
     }
 
-    ~hip_pcps_acquisition()
-    {
-        if (d_acq != nullptr) gc_acq_destroy(d_acq);
-    }
-
-    hip_pcps_acquisition(const hip_pcps_acquisition&) = delete;
-    hip_pcps_acquisition& operator=(const hip_pcps_acquisition&) = delete;
-
     inline void set_gnss_synchro(Gnss_Synchro* p_gnss_synchro)
     {
         std::lock_guard<std::mutex> lock(d_setlock);
@@ -95,22 +85,10 @@ public:
      *  (re)creates the engine plan, whose wipe-off table is built like update_local_carrier does. */
     void init()
     {
-        d_gnss_synchro->Flag_valid_acquisition = false;
-        d_gnss_synchro->Flag_valid_symbol_output = false;
-        d_gnss_synchro->Flag_valid_pseudorange = false;
-        d_gnss_synchro->Flag_valid_word = false;
-        d_gnss_synchro->Acq_doppler_step = 0U;
-        d_gnss_synchro->Acq_delay_samples = 0.0;
-        d_gnss_synchro->Acq_doppler_hz = 0.0;
-        d_gnss_synchro->Acq_samplestamp_samples = 0ULL;
+        gnsscorr::clear_synchro_for_init(*d_gnss_synchro);
         d_mag = 0.0;
         d_input_power = 0.0;
         d_num_doppler_bins = static_cast<uint32_t>(std::ceil(static_cast<double>(static_cast<int32_t>(acq_parameters.doppler_max) - static_cast<int32_t>(-acq_parameters.doppler_max)) / static_cast<double>(d_doppler_step)));
-        if (d_acq != nullptr)
-            {
-                gc_acq_destroy(d_acq);
-                d_acq = nullptr;
-            }
         gc_acq_conf c;
         std::memset(&c, 0, sizeof c);
         c.fs_in = acq_parameters.use_automatic_resampler ? acq_parameters.resampled_fs : acq_parameters.fs_in;
@@ -127,10 +105,9 @@ public:
         c.make_2_steps = acq_parameters.make_2_steps ? 1 : 0;
         c.num_doppler_bins_step2 = acq_parameters.num_doppler_bins_step2;
         c.doppler_step2 = acq_parameters.doppler_step2;
-        gc_ctx* ctx = gnsscorr::shared_context();
-        d_status = ctx ? gc_acq_create(ctx, &c, 1, &d_acq) : GC_ERR_NO_DEVICE;
-        if (d_status == GC_OK && d_old_freq != 0) d_status = gc_acq_set_frequency_offset(d_acq, d_old_freq);
-        if (d_status == GC_OK && !d_code.empty()) d_status = gc_acq_set_local_code(d_acq, 0, reinterpret_cast<const float*>(d_code.data()));
+        d_status = gnsscorr::create_engine(d_acq, [&](gc_ctx* ctx, gc_acq** acq) { return gc_acq_create(ctx, &c, 1, acq); });
+        if (d_status == GC_OK && d_old_freq != 0) d_status = gc_acq_set_frequency_offset(d_acq.get(), d_old_freq);
+        if (d_status == GC_OK && !d_code.empty()) d_status = gc_acq_set_local_code(d_acq.get(), 0, reinterpret_cast<const float*>(d_code.data()));
         d_worker_active = false;
         if (d_dump)
             {
@@ -157,11 +134,11 @@ public:
                 const auto it = d_glonass_prn.find(d_gnss_synchro->PRN);
                 if (it != d_glonass_prn.end()) d_old_freq += static_cast<int64_t>(d_gnss_synchro->Signal[0] == '1' ? 562500 : 437500) * it->second;
             }
-        if (d_acq != nullptr) d_status = gc_acq_set_frequency_offset(d_acq, d_old_freq);
+        if (d_acq != nullptr) d_status = gc_acq_set_frequency_offset(d_acq.get(), d_old_freq);
         const size_t n = acq_parameters.bit_transition_flag ? d_fft_size / 2 : d_consumed_samples;
         d_code.assign(code, code + n);
         // (a failed frequency-offset call must stay visible in last_status(): the search would run on the old wipe-off tables)
-        if (d_acq != nullptr && d_status == GC_OK) d_status = gc_acq_set_local_code(d_acq, 0, reinterpret_cast<const float*>(d_code.data()));
+        if (d_acq != nullptr && d_status == GC_OK) d_status = gc_acq_set_local_code(d_acq.get(), 0, reinterpret_cast<const float*>(d_code.data()));
     }
 
     inline void set_active(bool active)
@@ -176,10 +153,7 @@ public:
         d_state = state;
         if (d_state == 1)
             {
-                d_gnss_synchro->Acq_delay_samples = 0.0;
-                d_gnss_synchro->Acq_doppler_hz = 0.0;
-                d_gnss_synchro->Acq_samplestamp_samples = 0ULL;
-                d_gnss_synchro->Acq_doppler_step = 0U;
+                gnsscorr::clear_synchro_for_restart(*d_gnss_synchro);
                 d_mag = 0.0;
                 d_input_power = 0.0;
                 d_test_statistics = 0.0;
@@ -229,7 +203,7 @@ public:
                 if (d_step_two)
                     {
                         d_doppler_center_step_two = static_cast<float>(d_gnss_synchro->Acq_doppler_hz);
-                        if (d_acq != nullptr) d_status = gc_acq_set_step_two(d_acq, 1, d_doppler_center_step_two);
+                        if (d_acq != nullptr) d_status = gc_acq_set_step_two(d_acq.get(), 1, d_doppler_center_step_two);
                         d_state = 0;
                         d_active = true;
                     }
@@ -238,10 +212,7 @@ public:
         switch (d_state)
             {
             case 0:
-                d_gnss_synchro->Acq_delay_samples = 0.0;
-                d_gnss_synchro->Acq_doppler_hz = 0.0;
-                d_gnss_synchro->Acq_samplestamp_samples = 0ULL;
-                d_gnss_synchro->Acq_doppler_step = 0U;
+                gnsscorr::clear_synchro_for_restart(*d_gnss_synchro);
                 d_mag = 0.0;
                 d_input_power = 0.0;
                 d_test_statistics = 0.0;
@@ -288,7 +259,7 @@ public:
         lk.unlock();
         gc_acq_result r;
         std::memset(&r, 0, sizeof r);
-        d_status = d_acq ? gc_acq_dwell(d_acq, reinterpret_cast<const float*>(d_data_buffer.data()), &r) : GC_ERR_STATE;
+        d_status = d_acq ? gc_acq_dwell(d_acq.get(), reinterpret_cast<const float*>(d_data_buffer.data()), &r) : GC_ERR_STATE;
         d_test_statistics = r.test_statistics;
         d_input_power = r.input_power;
         d_last = r;
@@ -300,7 +271,7 @@ public:
                 const uint32_t bins = d_step_two ? d_num_doppler_bins_step2 : d_num_doppler_bins;
                 std::vector<float>& dst = d_step_two ? narrow_grid_ : grid_;
                 d_grid_tmp.resize(static_cast<size_t>(bins) * d_fft_size);
-                if (gc_acq_get_grid(d_acq, 0, d_grid_tmp.data()) == GC_OK)
+                if (gc_acq_get_grid(d_acq.get(), 0, d_grid_tmp.data()) == GC_OK)
                     {
                         for (uint32_t b = 0; b < bins; b++)
                             std::memcpy(&dst[static_cast<size_t>(b) * effective_fft_size], &d_grid_tmp[static_cast<size_t>(b) * d_fft_size], sizeof(float) * effective_fft_size);
@@ -405,8 +376,8 @@ public:
                 d_positive_acq = 0;
                 if (d_acq != nullptr)
                     {
-                        gc_acq_reset(d_acq);  // "Reset grid" (:917-924)
-                        if (!d_step_two) gc_acq_set_step_two(d_acq, 0, 0.0f);
+                        gc_acq_reset(d_acq.get());  // "Reset grid" (:917-924)
+                        if (!d_step_two) gc_acq_set_step_two(d_acq.get(), 0, 0.0f);
                     }
             }
     }
@@ -432,9 +403,9 @@ public:
         std::vector<std::pair<float, uint32_t>> out;
         if (d_acq == nullptr) return out;
         uint32_t fft = 0, cons = 0, bins = 0;
-        if (gc_acq_fft_size(d_acq, &fft, &cons, &bins) != GC_OK) return out;
+        if (gc_acq_fft_size(d_acq.get(), &fft, &cons, &bins) != GC_OK) return out;
         std::vector<float> v(2 * static_cast<size_t>(bins));
-        if (gc_acq_peek(d_acq, GC_ACQ_PEEK_ROW_MAX, 0, v.data()) != GC_OK) return out;
+        if (gc_acq_peek(d_acq.get(), GC_ACQ_PEEK_ROW_MAX, 0, v.data()) != GC_OK) return out;
         for (uint32_t d = 0; d < bins; d++) out.emplace_back(v[2 * d], static_cast<uint32_t>(v[2 * d + 1]));
         return out;
     }
@@ -526,7 +497,7 @@ private:
     std::string d_dump_filename;
     std::string d_last_dump_file;
     std::vector<float> grid_, narrow_grid_, d_grid_tmp;
-    gc_acq* d_acq = nullptr;
+    gnsscorr::AcqEngine d_acq;
     gc_status d_status = GC_OK;
     gc_acq_result d_last{};
     std::mutex d_setlock;

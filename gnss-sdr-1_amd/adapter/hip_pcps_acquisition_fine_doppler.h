@@ -31,9 +31,7 @@
 #ifndef GNSSCORR_HIP_PCPS_ACQUISITION_FINE_DOPPLER_H_
 #define GNSSCORR_HIP_PCPS_ACQUISITION_FINE_DOPPLER_H_
 
-#include "gnss_sdr_types.h"
-#include "gnsscorr.h"
-#include "hip_multicorrelator_real_codes.h"  // gnsscorr::shared_context()
+#include "acquisition_block_base.h"  // engine owners, conf filler, synchro clearing
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -120,15 +118,6 @@ public:
         d_10_ms_buffer.assign(static_cast<size_t>(kBufferMs) * d_fft_size, gr_complex(0.0f, 0.0f));
     }
 
-    ~hip_pcps_acquisition_fine_doppler()
-    {
-        if (d_acq != nullptr) gc_acq_destroy(d_acq);
-        if (d_fine != nullptr) gc_fine_doppler_destroy(d_fine);
-    }
-
-    hip_pcps_acquisition_fine_doppler(const hip_pcps_acquisition_fine_doppler&) = delete;
-    hip_pcps_acquisition_fine_doppler& operator=(const hip_pcps_acquisition_fine_doppler&) = delete;
-
     inline void set_gnss_synchro(Gnss_Synchro* p_gnss_synchro) { d_gnss_synchro = p_gnss_synchro; }
     inline uint32_t mag() const { return static_cast<uint32_t>(d_test_statistics); }
     inline void set_active(bool active) { d_active = active; }
@@ -154,38 +143,15 @@ public:
     /*! init (:208-219), and the engines: the block builds its grid in set_doppler_step and its transforms in the constructor */
     void init()
     {
-        d_gnss_synchro->Flag_valid_acquisition = false;
-        d_gnss_synchro->Flag_valid_symbol_output = false;
-        d_gnss_synchro->Flag_valid_pseudorange = false;
-        d_gnss_synchro->Flag_valid_word = false;
-        d_gnss_synchro->Acq_doppler_step = 0U;
-        d_gnss_synchro->Acq_delay_samples = 0.0;
-        d_gnss_synchro->Acq_doppler_hz = 0.0;
-        d_gnss_synchro->Acq_samplestamp_samples = 0ULL;
+        gnsscorr::clear_synchro_for_init(*d_gnss_synchro);
         d_state = 0;
-        if (d_acq != nullptr) gc_acq_destroy(d_acq);
-        if (d_fine != nullptr) gc_fine_doppler_destroy(d_fine);
-        d_acq = nullptr;
-        d_fine = nullptr;
-        gc_ctx* ctx = gnsscorr::shared_context();
-        if (ctx == nullptr)
-            {
-                d_status = GC_ERR_NO_DEVICE;
-                return;
-            }
-        gc_acq_conf c;
-        std::memset(&c, 0, sizeof c);
-        c.fs_in = d_fs_in;
-        c.sampled_ms = 1;
-        c.ms_per_code = 1;
-        c.samples_per_ms = static_cast<float>(d_samples_per_ms);
-        c.samples_per_code = static_cast<float>(d_samples_per_ms);
-        c.samples_per_chip = gnsscorr::fine_doppler_samples_per_chip(d_fs_in);
-        c.doppler_max = d_config_doppler_max;
-        c.doppler_step = d_doppler_step;
-        c.max_dwells = std::max(1u, d_max_dwells);
+        d_fine.reset();
+        gc_acq_conf c = gnsscorr::acq_conf(d_fs_in, 1, 1, static_cast<float>(d_samples_per_ms), static_cast<float>(d_samples_per_ms), 1.023e6, d_config_doppler_max, d_doppler_step,
+            std::max(1u, d_max_dwells));
+        c.samples_per_chip = gnsscorr::fine_doppler_samples_per_chip(d_fs_in);  // the block's own rounding (:295), through float
         c.num_doppler_bins_override = d_num_doppler_points;
-        d_status = d_num_doppler_points > 0 ? gc_acq_create(ctx, &c, 1, &d_acq) : GC_ERR_INVALID;
+        // without a device GC_ERR_NO_DEVICE, whatever the grid; with one, a grid of no bins is GC_ERR_INVALID
+        d_status = gnsscorr::create_engine(d_acq, [&](gc_ctx* ctx, gc_acq** acq) { return d_num_doppler_points > 0 ? gc_acq_create(ctx, &c, 1, acq) : GC_ERR_INVALID; });
         if (d_status != GC_OK) return;
         gc_fine_doppler_conf f;
         std::memset(&f, 0, sizeof f);
@@ -195,7 +161,7 @@ public:
         f.zero_padding_factor = kZeroPaddingFactor;
         f.window_hz = 1000.0f;
         f.alignment = GC_FINE_ALIGN_REFERENCE;
-        d_status = gc_fine_doppler_create(ctx, &f, 1, &d_fine);
+        d_status = gnsscorr::create_engine(d_fine, [&](gc_ctx* ctx, gc_fine_doppler** fine) { return gc_fine_doppler_create(ctx, &f, 1, fine); });
         if (d_status == GC_OK) install_code();
     }
 
@@ -205,10 +171,7 @@ public:
         d_state = state;
         if (d_state == 1)
             {
-                d_gnss_synchro->Acq_delay_samples = 0.0;
-                d_gnss_synchro->Acq_doppler_hz = 0.0;
-                d_gnss_synchro->Acq_samplestamp_samples = 0ULL;
-                d_gnss_synchro->Acq_doppler_step = 0U;
+                gnsscorr::clear_synchro_for_restart(*d_gnss_synchro);
                 d_test_statistics = 0.0f;
                 d_active = true;
                 reset_grid();
@@ -234,7 +197,7 @@ public:
                 {
                     if (noutput_items < fft) return 0;
                     gc_acq_result r;
-                    d_status = d_acq != nullptr ? gc_acq_dwell(d_acq, reinterpret_cast<const float*>(in), &r) : GC_ERR_STATE;
+                    d_status = d_acq != nullptr ? gc_acq_dwell(d_acq.get(), reinterpret_cast<const float*>(in), &r) : GC_ERR_STATE;
                     if (d_n_samples_in_buffer + d_fft_size <= d_10_ms_buffer.size()) std::memcpy(&d_10_ms_buffer[d_n_samples_in_buffer], in, sizeof(gr_complex) * d_fft_size);
                     d_n_samples_in_buffer += d_fft_size;
                     d_well_count++;
@@ -247,7 +210,7 @@ public:
             case 2:
                 {
                     d_grid.resize(static_cast<size_t>(d_num_doppler_points) * d_fft_size);
-                    d_status = gc_acq_get_grid(d_acq, 0, d_grid.data());
+                    d_status = gc_acq_get_grid(d_acq.get(), 0, d_grid.data());
                     if (d_status != GC_OK)
                         {
                             d_state = 5;
@@ -319,8 +282,8 @@ public:
     const gnsscorr::FineDopplerCaf& caf() const { return d_caf; }
     //! the fine stage's record of the last positive search (status 0: it did not run)
     const gc_fine_doppler_result& fine_result() const { return d_fine_result; }
-    gc_acq* engine() { return d_acq; }
-    gc_fine_doppler* fine_engine() { return d_fine; }
+    gc_acq* engine() { return d_acq.get(); }
+    gc_fine_doppler* fine_engine() { return d_fine.get(); }
 
 private:
     int standby(int n)
@@ -333,15 +296,15 @@ private:
     void install_code()
     {
         if (!d_have_code) return;
-        if (d_acq != nullptr) d_status = gc_acq_set_local_code(d_acq, 0, reinterpret_cast<const float*>(d_code.data()));
-        if (d_fine != nullptr && d_status == GC_OK) d_status = gc_fine_doppler_set_code(d_fine, 0, reinterpret_cast<const float*>(d_code.data()));
+        if (d_acq != nullptr) d_status = gc_acq_set_local_code(d_acq.get(), 0, reinterpret_cast<const float*>(d_code.data()));
+        if (d_fine != nullptr && d_status == GC_OK) d_status = gc_fine_doppler_set_code(d_fine.get(), 0, reinterpret_cast<const float*>(d_code.data()));
     }
 
     // reset_grid (:232-243): the engine's grid reads as zero after gc_acq_reset
     void reset_grid()
     {
         d_well_count = 0;
-        if (d_acq != nullptr) d_status = gc_acq_reset(d_acq);
+        if (d_acq != nullptr) d_status = gc_acq_reset(d_acq.get());
     }
 
     // estimate_Doppler (:400-479) on the buffer's first 10 ms
@@ -353,7 +316,7 @@ private:
         q.slot = 0;
         q.delay_samples = static_cast<uint32_t>(static_cast<int>(d_gnss_synchro->Acq_delay_samples));
         q.coarse_doppler_hz = d_gnss_synchro->Acq_doppler_hz;
-        d_status = gc_fine_doppler_estimate(d_fine, reinterpret_cast<const float*>(d_10_ms_buffer.data()), &q, 1, &d_fine_result);
+        d_status = gc_fine_doppler_estimate(d_fine.get(), reinterpret_cast<const float*>(d_10_ms_buffer.data()), &q, 1, &d_fine_result);
         if (d_status == GC_OK && d_fine_result.status == GC_FINE_REFINED) d_gnss_synchro->Acq_doppler_hz = d_fine_result.doppler_hz;
     }
 
@@ -368,8 +331,8 @@ private:
     int32_t d_state = 0, d_positive_acq = 0;
     bool d_active = false, d_have_code = false;
     float d_threshold = 0.0f, d_test_statistics = 0.0f;
-    gc_acq* d_acq = nullptr;
-    gc_fine_doppler* d_fine = nullptr;
+    gnsscorr::AcqEngine d_acq;
+    gnsscorr::FineDopplerEngine d_fine;
     gc_status d_status = GC_OK;
     gnsscorr::FineDopplerCaf d_caf;
     gc_fine_doppler_result d_fine_result{};

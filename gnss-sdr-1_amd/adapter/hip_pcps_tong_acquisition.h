@@ -26,9 +26,8 @@
 #ifndef GNSSCORR_HIP_PCPS_TONG_ACQUISITION_H_
 #define GNSSCORR_HIP_PCPS_TONG_ACQUISITION_H_
 
-#include "gnss_sdr_types.h"
-#include "gnsscorr.h"
-#include "hip_multicorrelator_real_codes.h"  // gnsscorr::shared_context()
+#include "acquisition_adapter_base.h"
+#include "acquisition_block_base.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -38,45 +37,27 @@
 
 namespace gnsscorr
 {
-//! init() (:198-205): both ends of the range count
-inline uint32_t tong_doppler_bins(uint32_t doppler_max, uint32_t doppler_step)
-{
-    if (doppler_step == 0) doppler_step = 250;
-    uint32_t n = 0;
-    for (int64_t doppler = -static_cast<int64_t>(doppler_max); doppler <= static_cast<int64_t>(doppler_max); doppler += doppler_step) n++;
-    return n;
-}
+//! init() (:198-205): both ends of the range count; a step of 0 means 250
+inline uint32_t tong_doppler_bins(uint32_t doppler_max, uint32_t doppler_step) { return inclusive_doppler_bins(doppler_max, doppler_step ? doppler_step : 250); }
 }  // namespace gnsscorr
 
-class hip_pcps_tong_acquisition
+class hip_pcps_tong_acquisition : public hip_acquisition_item_block
 {
 public:
+    // general_work (:263-489): search state 1 (:303-419), positive 2, negative 3; set_state(1) restarts and leaves d_active alone (:233-251)
     hip_pcps_tong_acquisition(uint32_t sampled_ms, uint32_t doppler_max, int64_t fs_in, int32_t samples_per_ms, int32_t samples_per_code, uint32_t tong_init_val,
         uint32_t tong_max_val, uint32_t tong_max_dwells, bool dump, const std::string& dump_filename)
-        : d_fs_in(fs_in), d_samples_per_ms(samples_per_ms), d_samples_per_code(samples_per_code), d_sampled_ms(sampled_ms), d_doppler_max(doppler_max), d_tong_init_val(tong_init_val), d_tong_max_val(tong_max_val), d_tong_max_dwells(tong_max_dwells), d_tong_count(tong_init_val), d_dump(dump), d_dump_filename(dump_filename)
+        : hip_acquisition_item_block(Policy{1, 1, 2, 3, false}, sampled_ms, tong_max_dwells, doppler_max, fs_in, samples_per_ms, samples_per_code, dump, dump_filename,
+              sampled_ms * static_cast<uint32_t>(samples_per_ms), sampled_ms * static_cast<uint32_t>(samples_per_ms)),
+          d_tong_init_val(tong_init_val), d_tong_max_val(tong_max_val), d_tong_count(tong_init_val)
     {
-        d_fft_size = d_sampled_ms * static_cast<uint32_t>(d_samples_per_ms);
         d_code.assign(d_fft_size, gr_complex(0.0f, 0.0f));
     }
 
-    ~hip_pcps_tong_acquisition()
-    {
-        if (d_acq != nullptr) gc_acq_destroy(d_acq);
-    }
-
-    hip_pcps_tong_acquisition(const hip_pcps_tong_acquisition&) = delete;
-    hip_pcps_tong_acquisition& operator=(const hip_pcps_tong_acquisition&) = delete;
-
-    inline void set_gnss_synchro(Gnss_Synchro* p_gnss_synchro) { d_gnss_synchro = p_gnss_synchro; }
-    inline uint32_t mag() const { return d_mag; }
-    inline void set_active(bool active) { d_active = active; }
-    inline void set_channel(uint32_t channel) { d_channel = channel; }
-    inline void set_doppler_max(uint32_t doppler_max) { d_doppler_max = doppler_max; }
-    inline void set_doppler_step(uint32_t doppler_step) { d_doppler_step = doppler_step; }
-    inline void set_threshold(float threshold)
+    void set_threshold(float threshold) override
     {
         d_threshold = threshold;
-        if (d_acq != nullptr) d_status = gc_acq_tong_set_threshold(d_acq, d_threshold);
+        if (d_acq != nullptr) d_status = gc_acq_tong_set_threshold(d_acq.get(), d_threshold);
     }
 
     /*! set_local_code (:174-182): d_fft_size samples */
@@ -84,119 +65,40 @@ public:
     {
         std::memcpy(d_code.data(), code, sizeof(gr_complex) * d_code.size());
         d_have_code = true;
-        if (d_acq != nullptr) d_status = gc_acq_set_local_code(d_acq, 0, reinterpret_cast<const float*>(d_code.data()));
+        if (d_acq != nullptr) d_status = load_code();
     }
 
-    /*! init (:185-227): clears the synchro fields, counts the bins, (re)creates the engine (wipe-off grid and zeroed data grid) */
-    void init()
-    {
-        d_gnss_synchro->Flag_valid_acquisition = false;
-        d_gnss_synchro->Flag_valid_symbol_output = false;
-        d_gnss_synchro->Flag_valid_pseudorange = false;
-        d_gnss_synchro->Flag_valid_word = false;
-        d_gnss_synchro->Acq_doppler_step = 0U;
-        d_gnss_synchro->Acq_delay_samples = 0.0;
-        d_gnss_synchro->Acq_doppler_hz = 0.0;
-        d_gnss_synchro->Acq_samplestamp_samples = 0ULL;
-        d_mag = 0.0;
-        d_input_power = 0.0;
-        if (d_doppler_step == 0) d_doppler_step = 250;
-        d_num_doppler_bins = gnsscorr::tong_doppler_bins(d_doppler_max, d_doppler_step);
-        if (d_acq != nullptr)
-            {
-                gc_acq_destroy(d_acq);
-                d_acq = nullptr;
-            }
-        gc_acq_conf c;
-        std::memset(&c, 0, sizeof c);
-        c.fs_in = d_fs_in;
-        c.sampled_ms = d_sampled_ms;
-        c.ms_per_code = d_sampled_ms;
-        c.samples_per_ms = static_cast<float>(d_samples_per_ms);
-        c.samples_per_code = static_cast<float>(d_samples_per_code);
-        c.samples_per_chip = static_cast<uint32_t>(std::ceil(static_cast<double>(d_fs_in) / 1.023e6));
-        c.doppler_max = d_doppler_max;
-        c.doppler_step = d_doppler_step;
-        c.max_dwells = d_tong_max_dwells;
-        gc_ctx* ctx = gnsscorr::shared_context();
-        d_status = ctx ? gc_acq_create_tong(ctx, &c, 1, d_tong_init_val, d_tong_max_val, d_tong_max_dwells, &d_acq) : GC_ERR_NO_DEVICE;
-        if (d_status == GC_OK) d_status = gc_acq_tong_set_threshold(d_acq, d_threshold);
-        if (d_status == GC_OK && d_have_code) d_status = gc_acq_set_local_code(d_acq, 0, reinterpret_cast<const float*>(d_code.data()));
-    }
-
-    void set_state(int32_t state)
-    {
-        d_state = state;
-        if (d_state == 1) restart();
-    }
-
-    /*! general_work (:263-489) on host items of item_length() samples.  Returns the number of items consumed. */
-    int work(const gr_complex* in, int ninput_items) { return step(in, nullptr, 0, ninput_items); }
-
-    /*! the same on items that lie in `ring` from absolute sample first_index on (a GC_IQ_F32 ring, or the format given to the engine) */
+    /*! general_work (:263-489) on items that lie in `ring` from absolute sample first_index on (a GC_IQ_F32 ring, or the format given
+     *  to the engine); work(in, n) of the base is the same on host items of item_length() samples */
     int work_ring(gc_stream* ring, uint64_t first_index, int n_items) { return step(nullptr, ring, first_index, n_items); }
 
-    //! messages published on the "events" port: 1 = ACQ_SUCCESS, 2 = ACQ_FAIL
-    const std::vector<int>& events() const { return d_events; }
-    void clear_events() { d_events.clear(); }
-    float test_statistics() const { return d_test_statistics; }
-    float input_power() const { return d_input_power; }
-    float threshold() const { return d_threshold; }
-    const gc_acq_result& last_result() const { return d_last; }
-    uint32_t fft_size() const { return d_fft_size; }
-    uint32_t item_length() const { return d_fft_size; }
-    uint32_t num_doppler_bins() const { return d_num_doppler_bins; }
-    uint32_t dwell_count() const { return d_dwell_count; }
     uint32_t tong_count() const { return d_tong_count; }
-    int32_t state() const { return d_state; }
-    uint64_t sample_counter() const { return d_sample_counter; }
-    gc_status last_status() const { return d_status; }
-    gc_acq* engine() { return d_acq; }
 
 private:
+    // init (:185-227): counts the bins, creates the engine (wipe-off grid and zeroed data grid)
+    gc_status create_engine() override
+    {
+        if (d_doppler_step == 0) d_doppler_step = 250;
+        d_num_doppler_bins = gnsscorr::tong_doppler_bins(d_doppler_max, d_doppler_step);
+        const gc_acq_conf c = conf(1.023e6, d_max_dwells);
+        const gc_status status = make_engine([&](gc_ctx* ctx, gc_acq** acq) { return gc_acq_create_tong(ctx, &c, 1, d_tong_init_val, d_tong_max_val, d_max_dwells, acq); });
+        return status == GC_OK ? gc_acq_tong_set_threshold(d_acq.get(), d_threshold) : status;
+    }
+
+    gc_status load_code() override { return gc_acq_set_local_code(d_acq.get(), 0, reinterpret_cast<const float*>(d_code.data())); }
+
     // "restart acquisition variables" (set_state(1) :233-251 and state 0 :275-292): the engine's grid reads as zero after gc_acq_reset
-    void restart()
+    void on_restart() override
     {
-        d_gnss_synchro->Acq_delay_samples = 0.0;
-        d_gnss_synchro->Acq_doppler_hz = 0.0;
-        d_gnss_synchro->Acq_samplestamp_samples = 0ULL;
-        d_gnss_synchro->Acq_doppler_step = 0U;
-        d_dwell_count = 0;
         d_tong_count = d_tong_init_val;
-        d_mag = 0.0;
-        d_input_power = 0.0;
-        d_test_statistics = 0.0;
-        if (d_acq != nullptr) d_status = gc_acq_reset(d_acq);
+        reset_engine();
     }
 
-    int step(const gr_complex* in, gc_stream* ring, uint64_t first_index, int n_items)
+    // state 1 (:303-419): one dwell on a host item, or all the dwells the ring's items allow in one call.  The counter and the dwell
+    // count advance AFTER the call, by the dwells the device ran
+    int search(const gr_complex* in, gc_stream* ring, uint64_t first_index, int n_items) override
     {
-        switch (d_state)
-            {
-            case 0:
-                if (d_active)
-                    {
-                        restart();
-                        d_state = 1;
-                    }
-                d_sample_counter += static_cast<uint64_t>(d_fft_size) * static_cast<uint64_t>(n_items);
-                return n_items;
-            case 1:
-                return n_items > 0 ? dwells(in, ring, first_index, n_items) : 0;
-            case 2:
-            case 3:
-                d_active = false;
-                d_events.push_back(d_state == 2 ? 1 : 2);
-                d_state = 0;
-                d_sample_counter += static_cast<uint64_t>(d_fft_size) * static_cast<uint64_t>(n_items);
-                return n_items;
-            }
-        return 0;
-    }
-
-    // state 1 (:303-419): one dwell on a host item, or all the dwells the ring's items allow in one call.  Returns the items consumed
-    int dwells(const gr_complex* in, gc_stream* ring, uint64_t first_index, int n_items)
-    {
+        if (n_items <= 0) return 0;
         gc_acq_result r;
         struct gc_acq_tong_status st;
         std::memset(&r, 0, sizeof r);
@@ -205,16 +107,16 @@ private:
         if (d_acq == nullptr)
             d_status = GC_ERR_STATE;
         else if (ring != nullptr)
-            d_status = gc_acq_tong_search_stream(d_acq, ring, first_index, static_cast<uint32_t>(n_items), &r, &st);
+            d_status = gc_acq_tong_search_stream(d_acq.get(), ring, first_index, static_cast<uint32_t>(n_items), &r, &st);
         else
             {
-                d_status = gc_acq_dwell(d_acq, reinterpret_cast<const float*>(in), &r);
-                if (d_status == GC_OK) d_status = gc_acq_tong_status(d_acq, &st);
+                d_status = gc_acq_dwell(d_acq.get(), reinterpret_cast<const float*>(in), &r);
+                if (d_status == GC_OK) d_status = gc_acq_tong_status(d_acq.get(), &st);
             }
         if (d_status != GC_OK)
             {
                 // nothing ran: the item is consumed and the search fails, so that a broken engine cannot hold a channel for ever
-                d_sample_counter += static_cast<uint64_t>(d_fft_size);
+                count_items(1);
                 d_dwell_count++;
                 d_state = 3;
                 return 1;
@@ -240,22 +142,8 @@ private:
         return static_cast<int>(ran);
     }
 
-    int64_t d_fs_in;
-    int32_t d_samples_per_ms, d_samples_per_code;
-    uint32_t d_sampled_ms, d_doppler_max, d_tong_init_val, d_tong_max_val, d_tong_max_dwells, d_tong_count;
-    bool d_dump;
-    std::string d_dump_filename;
-    uint32_t d_fft_size = 0U, d_num_doppler_bins = 0U, d_doppler_step = 0U, d_channel = 0U, d_dwell_count = 0U;
-    uint64_t d_sample_counter = 0ULL;
-    int32_t d_state = 0;
-    bool d_active = false, d_have_code = false;
-    float d_threshold = 0.0f, d_mag = 0.0f, d_input_power = 0.0f, d_test_statistics = 0.0f;
-    gc_acq* d_acq = nullptr;
-    gc_status d_status = GC_OK;
-    gc_acq_result d_last{};
-    Gnss_Synchro* d_gnss_synchro = nullptr;
+    uint32_t d_tong_init_val, d_tong_max_val, d_tong_count;
     std::vector<gr_complex> d_code;
-    std::vector<int> d_events;
 };
 
 /*! GpsL1CaPcpsTongAcquisition (gps_l1_ca_pcps_tong_acquisition.cc:40-290) and GalileoE1PcpsTongAmbiguousAcquisition
@@ -266,15 +154,12 @@ private:
  *  code_length = round(fs / (1.023e6 / 4092)), vector_length = code_length * (sampled_ms / 4), samples_per_ms = code_length / 4
  *  (Galileo).  The local code is the code period tiled over vector_length. */
 template <bool GALILEO>
-class PcpsTongAcquisitionHip : public AcquisitionInterface
+class PcpsTongAcquisitionHip : public AcquisitionAdapterBase<hip_pcps_tong_acquisition>
 {
 public:
     PcpsTongAcquisitionHip(ConfigurationInterface* configuration, const std::string& role, unsigned int in_streams, unsigned int out_streams)
-        : configuration_(configuration), role_(role), in_streams_(in_streams), out_streams_(out_streams)
+        : AcquisitionAdapterBase<hip_pcps_tong_acquisition>(configuration, role, in_streams, out_streams, GALILEO ? 4000000 : 2048000)
     {
-        item_type_ = configuration_->property(role + ".item_type", std::string("gr_complex"));
-        int64_t fs_in_deprecated = configuration_->property("GNSS-SDR.internal_fs_hz", static_cast<int64_t>(GALILEO ? 4000000 : 2048000));
-        fs_in_ = configuration_->property("GNSS-SDR.internal_fs_sps", fs_in_deprecated);
         dump_ = configuration_->property(role + ".dump", false);
         doppler_max_ = configuration_->property(role + ".doppler_max", 5000);
         sampled_ms_ = configuration_->property(role + ".coherent_integration_time_ms", GALILEO ? 4 : 1);
@@ -290,98 +175,38 @@ public:
             tong_max_val_, tong_max_dwells_, dump_, dump_filename_);
     }
 
-    std::string role() override { return role_; }
     std::string implementation() override { return GALILEO ? "Galileo_E1_PCPS_Tong_Ambiguous_Acquisition_HIP" : "GPS_L1_CA_PCPS_Tong_Acquisition_HIP"; }
-    size_t item_size() override { return sizeof(gr_complex); }
-
-    void set_gnss_synchro(Gnss_Synchro* p_gnss_synchro) override
-    {
-        gnss_synchro_ = p_gnss_synchro;
-        acquisition_->set_gnss_synchro(gnss_synchro_);
-    }
-
-    void set_channel(unsigned int channel) override
-    {
-        channel_ = channel;
-        acquisition_->set_channel(channel_);
-    }
-
-    void set_channel_fsm(std::shared_ptr<ChannelFsm> channel_fsm) override { channel_fsm_ = channel_fsm; }
 
     void set_threshold(float threshold) override
     {
-        float pfa = configuration_->property(role_ + std::to_string(channel_) + ".pfa", 0.0f);
-        if (pfa == 0.0f) pfa = configuration_->property(role_ + ".pfa", 0.0f);
+        const float pfa = pfa_for_channel();
         threshold_ = threshold;
         if (pfa != 0.0f) gc_tong_threshold(pfa, vector_length_, doppler_max_, doppler_step_ ? doppler_step_ : 250, &threshold_);
         acquisition_->set_threshold(threshold_);
     }
 
-    void set_doppler_max(unsigned int doppler_max) override
-    {
-        doppler_max_ = doppler_max;
-        acquisition_->set_doppler_max(doppler_max_);
-    }
-
-    void set_doppler_step(unsigned int doppler_step) override
-    {
-        doppler_step_ = doppler_step;
-        acquisition_->set_doppler_step(doppler_step_);
-    }
-
-    void init() override { acquisition_->init(); }
-
     void set_local_code() override
     {
         std::vector<gr_complex> code(code_length_ + 8), tiled(vector_length_);
         if (GALILEO)
-            {
-                const bool cboc = configuration_->property("Acquisition" + std::to_string(channel_) + ".cboc", false);
-                const char* sig = (gnss_synchro_->Signal[0] == '1' && gnss_synchro_->Signal[1] == 'C') ? "1C" : "1B";
-                gc_galileo_e1_code_gen_complex_sampled(reinterpret_cast<float*>(code.data()), sig, cboc ? 1 : 0, gnss_synchro_->PRN, static_cast<int32_t>(fs_in_), 0, nullptr);
-            }
+            gnsscorr::e1_code_sampled(configuration_, channel_, gnss_synchro_, fs_in_, code.data());
         else
             gc_gps_l1_ca_code_gen_complex_sampled(reinterpret_cast<float*>(code.data()), gnss_synchro_->PRN, static_cast<int32_t>(fs_in_), 0, nullptr);
-        for (unsigned int i = 0; i < vector_length_ / code_length_; i++) std::memcpy(&tiled[static_cast<size_t>(i) * code_length_], code.data(), sizeof(gr_complex) * code_length_);
+        gnsscorr::tile_code(code.data(), code_length_, vector_length_ / code_length_, tiled.data());
         if (!tiled.empty()) acquisition_->set_local_code(tiled.data());
     }
 
-    void set_state(int state) override { acquisition_->set_state(state); }
-    signed int mag() override { return acquisition_->mag(); }
-    void reset() override { acquisition_->set_active(true); }
-    void stop_acquisition() override {}
-    void set_resampler_latency(uint32_t) override {}
-
-    //! the block (get_left_block() is a stream_to_vector in front of it in the reference)
-    std::shared_ptr<hip_pcps_tong_acquisition> block() { return acquisition_; }
-    unsigned int vector_length() const { return vector_length_; }
     unsigned int code_length() const { return code_length_; }
     unsigned int sampled_ms() const { return sampled_ms_; }
     unsigned int tong_init_val() const { return tong_init_val_; }
     unsigned int tong_max_val() const { return tong_max_val_; }
     unsigned int tong_max_dwells() const { return tong_max_dwells_; }
-    float threshold() const { return threshold_; }
 
 private:
-    ConfigurationInterface* configuration_;
-    std::shared_ptr<hip_pcps_tong_acquisition> acquisition_;
-    std::string item_type_;
-    std::string role_;
     std::string dump_filename_;
-    unsigned int in_streams_;
-    unsigned int out_streams_;
-    unsigned int vector_length_ = 0;
-    unsigned int code_length_ = 0;
-    unsigned int channel_ = 0;
-    unsigned int doppler_max_ = 0;
-    unsigned int doppler_step_ = 0;
     unsigned int sampled_ms_ = 1;
     unsigned int tong_init_val_ = 1, tong_max_val_ = 2, tong_max_dwells_ = 3;
     bool dump_ = false;
-    float threshold_ = 0.0f;
-    int64_t fs_in_ = 0;
-    std::shared_ptr<ChannelFsm> channel_fsm_;
-    Gnss_Synchro* gnss_synchro_ = nullptr;
 };
 
 using GpsL1CaPcpsTongAcquisitionHip = PcpsTongAcquisitionHip<false>;

@@ -6,6 +6,8 @@
 //   - CCCWSR on data + pilot gives a larger statistic than the one-replica adapter on E1-B for the same block;
 //   - the bank with CCCWSR combining finds the PRN the one-replica bank finds.
 // Usage: paired_acquisition_selftest <tests/golden directory>.  Needs a GPU (run by pytest -m gpu).
+//        paired_acquisition_selftest --host: the bin count and what a Doppler step of 0 does in the block's init() and in the 8 ms
+//        adapter's Pfa rule.  Creates no GPU context.
 #include "hip_acquisition_bank.h"
 #include "pcps_acquisition_adapters.h"
 #include <cmath>
@@ -199,12 +201,54 @@ static void test_bank(const std::vector<gr_complex>& x)
     if (ctx) gc_ctx_destroy(ctx);
 }
 
+// the pieces that need no GPU: the bin count and what a Doppler step of 0 does.  Creates no GPU context
+static void host_tests()
+{
+    EXPECT(gnsscorr::inclusive_doppler_bins(10000, 250) == 81 && gnsscorr::inclusive_doppler_bins(10000, 125) == 161, "both ends of the Doppler range count");
+    // init() before set_doppler_step: no bins, no engine, GC_ERR_INVALID; the search fails through the "no engine" path after max_dwells items
+    Gnss_Synchro g;
+    hip_pcps_paired_acquisition blk(hip_pcps_paired_acquisition::CCCWSR, 4, 2, 10000, 4000000, 4000, 16000, false, "");
+    blk.set_gnss_synchro(&g);
+    blk.init();
+    EXPECT(blk.last_status() == GC_ERR_INVALID && blk.num_doppler_bins() == 0, "step 0: status %d, %u bins", blk.last_status(), blk.num_doppler_bins());
+    blk.set_state(1);
+    std::vector<gr_complex> item(16000);
+    EXPECT(blk.work(item.data(), 1) == 1 && blk.state() == 1 && blk.work(item.data(), 1) == 1 && blk.state() == 3 && blk.dwell_count() == 2, "step 0: state %d after %u dwells",
+        blk.state(), blk.dwell_count());
+    EXPECT(blk.work(item.data(), 1) == 1 && blk.events().size() == 1 && blk.events()[0] == 2 && blk.sample_counter() == 48000, "step 0: ACQ_FAIL published");
+    // a Pfa before set_doppler_step: the 8 ms adapter leaves the given threshold installed; with a step it applies its rule
+    InMemoryConfiguration config;
+    config.set_property("GNSS-SDR.internal_fs_sps", "4000000");
+    config.set_property("Acquisition_1B.coherent_integration_time_ms", "8");
+    config.set_property("Acquisition_1B.pfa", "0.001");
+    GalileoE1Pcps8msAmbiguousAcquisitionHip acq(&config, "Acquisition_1B", 1, 0);
+    acq.set_doppler_max(10000);
+    acq.set_threshold(0.25f);
+    EXPECT(acq.threshold() == 0.25f && acq.block()->threshold() == 0.25f, "Pfa with a step of 0: threshold %g", acq.threshold());
+    acq.set_doppler_step(125);
+    acq.set_threshold(0.25f);
+    const double val = std::pow(1.0 - 0.001, 1.0 / (32000.0 * 161.0));
+    const float want = static_cast<float>(-std::log(1.0 - val) / 32000.0);
+    EXPECT(std::abs(acq.threshold() - want) <= 1e-5f * want, "Pfa threshold %g, expected %g", acq.threshold(), want);
+    // the CCCWSR adapter installs what it is given, Pfa or not
+    GalileoE1PcpsCccwsrAmbiguousAcquisitionHip cccwsr(&config, "Acquisition_1B", 1, 0);
+    cccwsr.set_doppler_step(250);
+    cccwsr.set_threshold(0.25f);
+    EXPECT(cccwsr.threshold() == 0.25f, "CCCWSR threshold %g", cccwsr.threshold());
+}
+
 int main(int argc, char** argv)
 {
     if (argc < 2)
         {
-            std::printf("usage: %s <golden dir>\n", argv[0]);
+            std::printf("usage: %s --host | <golden dir>\n", argv[0]);
             return 2;
+        }
+    if (std::string(argv[1]) == "--host")
+        {
+            host_tests();
+            if (g_fail == 0) std::printf("paired acquisition host self-test passed\n");
+            return g_fail == 0 ? 0 : 1;
         }
     const auto x = read_iq(std::string(argv[1]) + "/kat_galileo_e1_id1_fs4msps_8ms.dat");
     EXPECT(x.size() == 32000, "capture size %zu", x.size());

@@ -13,6 +13,9 @@
  *   hypotheses of an 8 ms replica, in one search -- backed by hip_pcps_paired_acquisition (at the end of this file)
  *   GpsL1CaPcpsAcquisitionFineDoppler (same directory): the search that ends in a 12.5 Hz Doppler estimate -- backed by
  *   hip_pcps_acquisition_fine_doppler (at the end of this file)
+ * The members and the overrides that only forward to the block are AcquisitionAdapterBase<Block> (acquisition_adapter_base.h); each
+ * adapter here holds its constructor, implementation(), set_threshold(), set_local_code() and the forwarders in which its reference
+ * adapter differs.
  * (item_type gr_complex only; `dump` / `dump_filename` / `dump_channel` write the reference's .mat
  * variables, see hip_pcps_acquisition::dump_results; the acquisition resampler and the GNU Radio
  * connect()/get_left_block() plumbing are outside this path).  Registration in a GNSS-SDR tree is one
@@ -22,6 +25,7 @@
 #ifndef GNSSCORR_PCPS_ACQUISITION_ADAPTERS_H_
 #define GNSSCORR_PCPS_ACQUISITION_ADAPTERS_H_
 
+#include "acquisition_adapter_base.h"
 #include "hip_pcps_acquisition.h"
 #include "hip_pcps_paired_acquisition.h"
 #include "hip_pcps_acquisition_fine_doppler.h"
@@ -81,17 +85,14 @@ inline AcqSignalTraits acq_traits(AcqSignal s)
 
 
 template <gnsscorr::AcqSignal SIG>
-class PcpsAcquisitionHip : public AcquisitionInterface
+class PcpsAcquisitionHip : public AcquisitionAdapterBase<hip_pcps_acquisition>
 {
 public:
     PcpsAcquisitionHip(ConfigurationInterface* configuration, const std::string& role, unsigned int in_streams, unsigned int out_streams)
-        : configuration_(configuration), role_(role), in_streams_(in_streams), out_streams_(out_streams)
+        : AcquisitionAdapterBase<hip_pcps_acquisition>(configuration, role, in_streams, out_streams, 2048000)
     {
         using gnsscorr::AcqSignal;
         const gnsscorr::AcqSignalTraits t = gnsscorr::acq_traits(SIG);
-        item_type_ = configuration_->property(role + ".item_type", std::string("gr_complex"));
-        int64_t fs_in_deprecated = configuration_->property("GNSS-SDR.internal_fs_hz", static_cast<int64_t>(2048000));
-        fs_in_ = configuration_->property("GNSS-SDR.internal_fs_sps", fs_in_deprecated);
         acq_parameters_.fs_in = fs_in_;
         acq_parameters_.resampled_fs = fs_in_;
         acq_parameters_.blocking = configuration_->property(role + ".blocking", true);
@@ -209,48 +210,24 @@ public:
         acquisition_ = std::make_shared<hip_pcps_acquisition>(acq_parameters_);
     }
 
-    std::string role() override { return role_; }
     std::string implementation() override { return gnsscorr::acq_traits(SIG).implementation; }
-    size_t item_size() override { return sizeof(gr_complex); }
 
-    void set_gnss_synchro(Gnss_Synchro* p_gnss_synchro) override
-    {
-        gnss_synchro_ = p_gnss_synchro;
-        acquisition_->set_gnss_synchro(gnss_synchro_);
-    }
-
-    void set_channel(unsigned int channel) override
-    {
-        channel_ = channel;
-        acquisition_->set_channel(channel_);
-    }
-
+    //! this block notifies the channel state machine itself (pcps_acquisition.cc:432-436)
     void set_channel_fsm(std::shared_ptr<ChannelFsm> channel_fsm) override
     {
         channel_fsm_ = channel_fsm;
         acquisition_->set_channel_fsm(channel_fsm);
     }
 
+    //! <role>.pfa only, no per-channel key (gps_l1_ca_pcps_acquisition.cc:262-279, same rule in the Galileo and BeiDou adapters).
+    //! Departure: with a doppler_step of 0 (set_threshold before set_doppler_step) the reference's bin loop would not end; the given
+    //! threshold stays installed
     void set_threshold(float threshold) override
     {
         float pfa = configuration_->property(role_ + ".pfa", 0.0f);
-        threshold_ = (pfa == 0.0f) ? threshold : calculate_threshold(pfa);
+        threshold_ = (pfa == 0.0f || doppler_step_ == 0) ? threshold : gnsscorr::exponential_quantile_threshold(pfa, vector_length_, doppler_max_, doppler_step_);
         acquisition_->set_threshold(threshold_);
     }
-
-    void set_doppler_max(unsigned int doppler_max) override
-    {
-        doppler_max_ = doppler_max;
-        acquisition_->set_doppler_max(doppler_max_);
-    }
-
-    void set_doppler_step(unsigned int doppler_step) override
-    {
-        doppler_step_ = doppler_step;
-        acquisition_->set_doppler_step(doppler_step_);
-    }
-
-    void init() override { acquisition_->init(); }
 
     void set_local_code() override
     {
@@ -281,63 +258,24 @@ public:
             }
         else
             {
-                // galileo_e1_pcps_ambiguous_acquisition.cc:240-284: the cboc flag is looked up per channel
-                bool cboc = configuration_->property("Acquisition" + std::to_string(channel_) + ".cboc", false);
-                char pilot_signal[3] = "1C";
-                const char* sig = acquire_pilot_ ? pilot_signal : gnss_synchro_->Signal;
-                char sig3[3] = {sig[0], sig[1], 0};
-                gc_galileo_e1_code_gen_complex_sampled(dst, sig3, cboc ? 1 : 0, gnss_synchro_->PRN, static_cast<int32_t>(fs_in_), 0, nullptr);
+                // galileo_e1_pcps_ambiguous_acquisition.cc:240-284: the pilot if asked for, else whatever signal the synchro names
+                const char sig[3] = {acquire_pilot_ ? '1' : gnss_synchro_->Signal[0], acquire_pilot_ ? 'C' : gnss_synchro_->Signal[1], 0};
+                gnsscorr::e1_code_sampled(configuration_, channel_, gnss_synchro_, fs_in_, code.data(), sig);
                 reps = sampled_ms_ / 4;
             }
-        for (unsigned int i = 0; i < reps; i++) std::memcpy(&code_[i * code_length_], code.data(), sizeof(gr_complex) * code_length_);
+        gnsscorr::tile_code(code.data(), code_length_, reps, code_.data());
         acquisition_->set_local_code(code_.data());
     }
 
-    void set_state(int state) override { acquisition_->set_state(state); }
-    signed int mag() override { return acquisition_->mag(); }
-    void reset() override { acquisition_->set_active(true); }
-    void stop_acquisition() override {}
+    //! this block takes the resampler's latency into its sample stamps
     void set_resampler_latency(uint32_t latency_samples) override { acquisition_->set_resampler_latency(latency_samples); }
 
-    //! the block (get_left_block()/get_right_block() in the reference)
-    std::shared_ptr<hip_pcps_acquisition> block() { return acquisition_; }
-    unsigned int vector_length() const { return vector_length_; }
-    float threshold() const { return threshold_; }
-
 private:
-    //! gps_l1_ca_pcps_acquisition.cc:262-279 (same rule in the Galileo and BeiDou adapters); the quantile
-    //! of an exponential distribution of rate lambda is -ln(1 - p) / lambda
-    float calculate_threshold(float pfa)
-    {
-        unsigned int frequency_bins = 0;
-        for (int doppler = static_cast<int>(-doppler_max_); doppler <= static_cast<int>(doppler_max_); doppler += doppler_step_) frequency_bins++;
-        unsigned int ncells = vector_length_ * frequency_bins;
-        double exponent = 1 / static_cast<double>(ncells);
-        double val = std::pow(1.0 - pfa, exponent);
-        auto lambda = double(vector_length_);
-        return static_cast<float>(-std::log(1.0 - val) / lambda);
-    }
-
-    ConfigurationInterface* configuration_;
-    std::shared_ptr<hip_pcps_acquisition> acquisition_;
     Acq_Conf acq_parameters_;
-    std::string item_type_;
-    std::string role_;
-    unsigned int in_streams_;
-    unsigned int out_streams_;
-    unsigned int vector_length_ = 0;
-    unsigned int code_length_ = 0;
-    unsigned int channel_ = 0;
-    unsigned int doppler_max_ = 0;
-    unsigned int doppler_step_ = 0;
     unsigned int sampled_ms_ = 1;
     bool acquire_pilot_ = false;
     bool acquire_iq_ = false;
-    float threshold_ = 0.0f;
-    int64_t fs_in_ = 0;
-    std::shared_ptr<ChannelFsm> channel_fsm_;
     std::vector<gr_complex> code_;
-    Gnss_Synchro* gnss_synchro_ = nullptr;
 };
 
 using GpsL1CaPcpsAcquisitionHip = PcpsAcquisitionHip<gnsscorr::AcqSignal::GPS_L1_CA>;
@@ -359,17 +297,16 @@ using GlonassL1CaPcpsAcquisitionHip = PcpsAcquisitionHip<gnsscorr::AcqSignal::GL
  *  (its Pfa rule is "not implemented", :237-243); the 8 ms adapter looks up <role><ch>.pfa, then <role>.pfa, and applies the
  *  exponential-quantile rule (:136-160, :245-263).  The E1-B and E1-C replicas come from gc_galileo_e1_code_gen_complex_sampled;
  *  the CCCWSR adapter of the reference generates ONE code period whatever the coherent time and hands the block a buffer it reads
- *  vector_length samples of (:199-220) -- here the period is tiled over the coherent time, as its 8 ms sibling does (:224-228). */
+ *  vector_length samples of (:199-220) -- here the period is tiled over the coherent time, as its 8 ms sibling does (:224-228).
+ *  Departure: with a doppler_step of 0 (set_threshold before set_doppler_step) the bin loop of the 8 ms adapter's rule would not
+ *  end; the given threshold stays installed. */
 template <hip_pcps_paired_acquisition::Kind KIND>
-class GalileoE1PairedAcquisitionHip : public AcquisitionInterface
+class GalileoE1PairedAcquisitionHip : public AcquisitionAdapterBase<hip_pcps_paired_acquisition>
 {
 public:
     GalileoE1PairedAcquisitionHip(ConfigurationInterface* configuration, const std::string& role, unsigned int in_streams, unsigned int out_streams)
-        : configuration_(configuration), role_(role), in_streams_(in_streams), out_streams_(out_streams)
+        : AcquisitionAdapterBase<hip_pcps_paired_acquisition>(configuration, role, in_streams, out_streams, 4000000)
     {
-        item_type_ = configuration_->property(role + ".item_type", std::string("gr_complex"));
-        int64_t fs_in_deprecated = configuration_->property("GNSS-SDR.internal_fs_hz", static_cast<int64_t>(4000000));
-        fs_in_ = configuration_->property("GNSS-SDR.internal_fs_sps", fs_in_deprecated);
         dump_ = configuration_->property(role + ".dump", false);
         doppler_max_ = configuration_->property(role + ".doppler_max", 5000);
         sampled_ms_ = configuration_->property(role + ".coherent_integration_time_ms", 4);
@@ -382,116 +319,44 @@ public:
         acquisition_ = std::make_shared<hip_pcps_paired_acquisition>(KIND, sampled_ms_, max_dwells_, doppler_max_, fs_in_, samples_per_ms, code_length_, dump_, dump_filename_);
     }
 
-    std::string role() override { return role_; }
     std::string implementation() override
     {
         return KIND == hip_pcps_paired_acquisition::CCCWSR ? "Galileo_E1_PCPS_CCCWSR_Ambiguous_Acquisition_HIP" : "Galileo_E1_PCPS_8ms_Ambiguous_Acquisition_HIP";
     }
-    size_t item_size() override { return sizeof(gr_complex); }
 
-    void set_gnss_synchro(Gnss_Synchro* p_gnss_synchro) override
-    {
-        gnss_synchro_ = p_gnss_synchro;
-        acquisition_->set_gnss_synchro(gnss_synchro_);
-    }
-
-    void set_channel(unsigned int channel) override
-    {
-        channel_ = channel;
-        acquisition_->set_channel(channel_);
-    }
-
-    void set_channel_fsm(std::shared_ptr<ChannelFsm> channel_fsm) override { channel_fsm_ = channel_fsm; }
-
+    //! CCCWSR installs the threshold it is given; the 8 ms kind applies the Pfa rule (galileo_e1_pcps_8ms_ambiguous_acquisition.cc:245-263)
     void set_threshold(float threshold) override
     {
         threshold_ = threshold;
         if (KIND == hip_pcps_paired_acquisition::E1_8MS)
             {
-                float pfa = configuration_->property(role_ + std::to_string(channel_) + ".pfa", 0.0f);
-                if (pfa == 0.0f) pfa = configuration_->property(role_ + ".pfa", 0.0f);
-                if (pfa != 0.0f) threshold_ = calculate_threshold(pfa);
+                const float pfa = pfa_for_channel();
+                if (pfa != 0.0f && doppler_step_ != 0) threshold_ = gnsscorr::exponential_quantile_threshold(pfa, vector_length_, doppler_max_, doppler_step_);
             }
         acquisition_->set_threshold(threshold_);
     }
 
-    void set_doppler_max(unsigned int doppler_max) override
-    {
-        doppler_max_ = doppler_max;
-        acquisition_->set_doppler_max(doppler_max_);
-    }
-
-    void set_doppler_step(unsigned int doppler_step) override
-    {
-        doppler_step_ = doppler_step;
-        acquisition_->set_doppler_step(doppler_step_);
-    }
-
-    void init() override { acquisition_->init(); }
-
     void set_local_code() override
     {
-        const bool cboc = configuration_->property("Acquisition" + std::to_string(channel_) + ".cboc", false);
-        const unsigned int reps = sampled_ms_ / 4;
         std::vector<gr_complex> one(code_length_ + 8), data(vector_length_), pilot(vector_length_);
-        // without a synchro signal the data component is searched, as "1B" selects it in the reference's generator
-        const char* sig_8ms = (gnss_synchro_->Signal[0] == '1' && gnss_synchro_->Signal[1] == 'C') ? "1C" : "1B";
-        gc_galileo_e1_code_gen_complex_sampled(reinterpret_cast<float*>(one.data()), KIND == hip_pcps_paired_acquisition::CCCWSR ? "1B" : sig_8ms, cboc ? 1 : 0,
-            gnss_synchro_->PRN, static_cast<int32_t>(fs_in_), 0, nullptr);
-        for (unsigned int i = 0; i < reps; i++) std::memcpy(&data[i * code_length_], one.data(), sizeof(gr_complex) * code_length_);
+        // CCCWSR: E1-B and E1-C; 8 ms: the synchro's component
+        gnsscorr::e1_code_sampled(configuration_, channel_, gnss_synchro_, fs_in_, one.data(), KIND == hip_pcps_paired_acquisition::CCCWSR ? "1B" : nullptr);
+        gnsscorr::tile_code(one.data(), code_length_, sampled_ms_ / 4, data.data());
         if (KIND == hip_pcps_paired_acquisition::CCCWSR)
             {
-                gc_galileo_e1_code_gen_complex_sampled(reinterpret_cast<float*>(one.data()), "1C", cboc ? 1 : 0, gnss_synchro_->PRN, static_cast<int32_t>(fs_in_), 0, nullptr);
-                for (unsigned int i = 0; i < reps; i++) std::memcpy(&pilot[i * code_length_], one.data(), sizeof(gr_complex) * code_length_);
+                gnsscorr::e1_code_sampled(configuration_, channel_, gnss_synchro_, fs_in_, one.data(), "1C");
+                gnsscorr::tile_code(one.data(), code_length_, sampled_ms_ / 4, pilot.data());
                 acquisition_->set_local_code(data.data(), pilot.data());
             }
         else
             acquisition_->set_local_code(data.data());
     }
 
-    void set_state(int state) override { acquisition_->set_state(state); }
-    signed int mag() override { return acquisition_->mag(); }
-    void reset() override { acquisition_->set_active(true); }
-    void stop_acquisition() override {}
-    void set_resampler_latency(uint32_t) override {}
-
-    //! the block (get_left_block() is a stream_to_vector of vector_length() samples in front of it in the reference)
-    std::shared_ptr<hip_pcps_paired_acquisition> block() { return acquisition_; }
-    unsigned int vector_length() const { return vector_length_; }
-    float threshold() const { return threshold_; }
-
 private:
-    //! galileo_e1_pcps_8ms_ambiguous_acquisition.cc:245-263
-    float calculate_threshold(float pfa)
-    {
-        unsigned int frequency_bins = 0;
-        for (int doppler = static_cast<int>(-doppler_max_); doppler <= static_cast<int>(doppler_max_); doppler += doppler_step_) frequency_bins++;
-        unsigned int ncells = vector_length_ * frequency_bins;
-        double exponent = 1 / static_cast<double>(ncells);
-        double val = std::pow(1.0 - pfa, exponent);
-        auto lambda = double(vector_length_);
-        return static_cast<float>(-std::log(1.0 - val) / lambda);
-    }
-
-    ConfigurationInterface* configuration_;
-    std::shared_ptr<hip_pcps_paired_acquisition> acquisition_;
-    std::string item_type_;
-    std::string role_;
     std::string dump_filename_;
-    unsigned int in_streams_;
-    unsigned int out_streams_;
-    unsigned int vector_length_ = 0;
-    unsigned int code_length_ = 0;
-    unsigned int channel_ = 0;
-    unsigned int doppler_max_ = 0;
-    unsigned int doppler_step_ = 0;
     unsigned int sampled_ms_ = 4;
     unsigned int max_dwells_ = 1;
     bool dump_ = false;
-    float threshold_ = 0.0f;
-    int64_t fs_in_ = 0;
-    std::shared_ptr<ChannelFsm> channel_fsm_;
-    Gnss_Synchro* gnss_synchro_ = nullptr;
 };
 
 using GalileoE1PcpsCccwsrAmbiguousAcquisitionHip = GalileoE1PairedAcquisitionHip<hip_pcps_paired_acquisition::CCCWSR>;
@@ -501,15 +366,12 @@ using GalileoE1Pcps8msAmbiguousAcquisitionHip = GalileoE1PairedAcquisitionHip<hi
  *  doppler_max (5000), coherent_integration_time_ms (1; read and, as in the reference, not used by the block), max_dwells (1), dump,
  *  dump_filename ("./acquisition.mat"), blocking_on_standby (false); doppler_step and threshold come through the interface.
  *  vector_length = round(fs / (1.023e6 / 1023)) = samples_per_ms; the local code is one sampled code period. */
-class GpsL1CaPcpsAcquisitionFineDopplerHip : public AcquisitionInterface
+class GpsL1CaPcpsAcquisitionFineDopplerHip : public AcquisitionAdapterBase<hip_pcps_acquisition_fine_doppler>
 {
 public:
     GpsL1CaPcpsAcquisitionFineDopplerHip(ConfigurationInterface* configuration, const std::string& role, unsigned int in_streams, unsigned int out_streams)
-        : role_(role), in_streams_(in_streams), out_streams_(out_streams)
+        : AcquisitionAdapterBase<hip_pcps_acquisition_fine_doppler>(configuration, role, in_streams, out_streams, 2048000)
     {
-        item_type_ = configuration->property(role + ".item_type", std::string("gr_complex"));
-        int64_t fs_in_deprecated = configuration->property("GNSS-SDR.internal_fs_hz", static_cast<int64_t>(2048000));
-        fs_in_ = configuration->property("GNSS-SDR.internal_fs_sps", fs_in_deprecated);
         dump_ = configuration->property(role + ".dump", false);
         dump_filename_ = configuration->property(role + ".dump_filename", std::string("./acquisition.mat"));
         doppler_max_ = configuration->property(role + ".doppler_max", 5000);
@@ -521,77 +383,36 @@ public:
             dump_filename_);
     }
 
-    std::string role() override { return role_; }
     std::string implementation() override { return "GPS_L1_CA_PCPS_Acquisition_Fine_Doppler_HIP"; }
-    size_t item_size() override { return sizeof(gr_complex); }
 
-    void set_gnss_synchro(Gnss_Synchro* p_gnss_synchro) override
-    {
-        gnss_synchro_ = p_gnss_synchro;
-        acquisition_->set_gnss_synchro(gnss_synchro_);
-    }
-    void set_channel(unsigned int channel) override
-    {
-        channel_ = channel;
-        acquisition_->set_channel(channel_);
-    }
-    void set_channel_fsm(std::shared_ptr<ChannelFsm> channel_fsm) override { channel_fsm_ = channel_fsm; }
     void set_threshold(float threshold) override
     {
         threshold_ = threshold;
         acquisition_->set_threshold(threshold_);
     }
-    void set_doppler_max(unsigned int doppler_max) override
-    {
-        doppler_max_ = doppler_max;
-        acquisition_->set_doppler_max(doppler_max_);
-    }
-    void set_doppler_step(unsigned int doppler_step) override
-    {
-        doppler_step_ = doppler_step;
-        acquisition_->set_doppler_step(doppler_step_);
-    }
-    void init() override { acquisition_->init(); }
+
     void set_local_code() override
     {
         std::vector<gr_complex> code(vector_length_ + 8);
         gc_gps_l1_ca_code_gen_complex_sampled(reinterpret_cast<float*>(code.data()), gnss_synchro_->PRN, static_cast<int32_t>(fs_in_), 0, nullptr);
         acquisition_->set_local_code(code.data());
     }
-    void set_state(int state) override { acquisition_->set_state(state); }
-    signed int mag() override { return static_cast<signed int>(acquisition_->mag()); }
-    void reset() override { acquisition_->set_active(true); }
-    void stop_acquisition() override {}
-    void set_resampler_latency(uint32_t) override {}
 
-    std::shared_ptr<hip_pcps_acquisition_fine_doppler> block() { return acquisition_; }
-    unsigned int vector_length() const { return vector_length_; }
+    //! the block's mag() is its statistic, cut to an integer
+    signed int mag() override { return static_cast<signed int>(acquisition_->mag()); }
+
     unsigned int doppler_max() const { return doppler_max_; }
     unsigned int sampled_ms() const { return sampled_ms_; }
     unsigned int max_dwells() const { return max_dwells_; }
     bool blocking_on_standby() const { return blocking_on_standby_; }
     bool dump() const { return dump_; }
     const std::string& dump_filename() const { return dump_filename_; }
-    float threshold() const { return threshold_; }
 
 private:
-    std::shared_ptr<hip_pcps_acquisition_fine_doppler> acquisition_;
-    std::string item_type_;
-    std::string role_;
     std::string dump_filename_;
-    unsigned int in_streams_;
-    unsigned int out_streams_;
-    unsigned int vector_length_ = 0;
-    unsigned int channel_ = 0;
-    unsigned int doppler_max_ = 0;
-    unsigned int doppler_step_ = 0;
     unsigned int sampled_ms_ = 1;
     unsigned int max_dwells_ = 1;
     bool dump_ = false, blocking_on_standby_ = false;
-    float threshold_ = 0.0f;
-    int64_t fs_in_ = 0;
-    std::shared_ptr<ChannelFsm> channel_fsm_;
-    Gnss_Synchro* gnss_synchro_ = nullptr;
 };
 
 #endif  // GNSSCORR_PCPS_ACQUISITION_ADAPTERS_H_
