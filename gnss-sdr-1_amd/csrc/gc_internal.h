@@ -91,10 +91,12 @@ struct gc_device_guard
     }
 };
 
-// Move-only owners of hipMalloc (gc_dev_buf<T>) and hipHostMalloc (gc_host_buf<T>) memory, as members of a handle struct: the
-// handle's destructor frees them, so a create function that fails half way and a destroy function need no list of frees.  Declare
-// the handle's gc_ctx_ref BEFORE its buffers (members are destroyed in reverse order: the context outlives the frees) and delete the
-// handle under a gc_device_guard of its device.  A buffer converts to T*, so launch sites read as they would with a plain pointer.
+// Move-only owners of hipMalloc (gc_dev_buf<T>), hipHostMalloc (gc_host_buf<T>) and page-locked, device-mapped memory with its device
+// view (gc_mapped_buf<T>), as members of a handle struct: the handle's destructor frees them, so a create function that fails half
+// way and a destroy function need no list of frees.  Declare the handle's gc_ctx_ref BEFORE its buffers (members are destroyed in
+// reverse order: the context outlives the frees) and delete the handle under a gc_device_guard of its device.  A buffer converts to
+// T*, so launch sites read as they would with a plain pointer.  The Mem policy is a template argument so that a stub can stand in for
+// the HIP runtime on the CPU (tests/owned_buf_selftest.cpp).
 struct gc_device_mem
 {
     static hipError_t alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
@@ -109,6 +111,14 @@ struct gc_pinned_mem
     static void release(void* p) { (void)hipHostFree(p); }
 };
 
+struct gc_mapped_mem
+{
+    static hipError_t alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocMapped); }
+    static hipError_t zero(void* p, size_t bytes) { return std::memset(p, 0, bytes), hipSuccess; }
+    static void release(void* p) { (void)hipHostFree(p); }
+    static hipError_t device_view(void** dv, void* p) { return hipHostGetDevicePointer(dv, p, 0); }
+};
+
 template <typename T, typename Mem>
 struct gc_owned_buf
 {
@@ -117,17 +127,34 @@ struct gc_owned_buf
         void operator()(T* q) const { Mem::release(q); }
     };
     std::unique_ptr<T, Release> p;
+    size_t cap = 0;  // elements held
+    gc_owned_buf() = default;
+    gc_owned_buf(gc_owned_buf&& o) noexcept : p(std::move(o.p)), cap(o.cap) { o.cap = 0; }
+    gc_owned_buf& operator=(gc_owned_buf&& o) noexcept
+    {
+        p = std::move(o.p);
+        cap = o.cap;
+        o.cap = 0;
+        return *this;
+    }
     // n elements, uninitialised or zero-filled (synchronously); what was held before is freed first
     hipError_t alloc(size_t n, bool zero_fill = false)
     {
-        p.reset();
+        reset();
         void* q = nullptr;
         const hipError_t e = Mem::alloc(&q, n * sizeof(T));
         if (e != hipSuccess) return e;
         p.reset(static_cast<T*>(q));
+        cap = n;
         return zero_fill ? Mem::zero(q, n * sizeof(T)) : hipSuccess;
     }
-    void reset() { p.reset(); }
+    // room for n elements: grows only and keeps no contents (alloc); empty, with cap 0, when the allocation fails
+    hipError_t reserve(size_t n) { return n <= cap ? hipSuccess : alloc(n); }
+    void reset()
+    {
+        p.reset();
+        cap = 0;
+    }
     T* get() const { return p.get(); }
     operator T*() const { return p.get(); }
 };
@@ -136,6 +163,48 @@ template <typename T>
 using gc_dev_buf = gc_owned_buf<T, gc_device_mem>;
 template <typename T>
 using gc_host_buf = gc_owned_buf<T, gc_pinned_mem>;
+
+// page-locked memory the device reads and writes in place: host pointer (the buffer itself) + device view `dev`
+template <typename T, typename Mem = gc_mapped_mem>
+struct gc_mapped_buf : gc_owned_buf<T, Mem>
+{
+    T* dev = nullptr;
+    gc_mapped_buf() = default;
+    gc_mapped_buf(gc_mapped_buf&& o) noexcept : gc_owned_buf<T, Mem>(std::move(o)), dev(o.dev) { o.dev = nullptr; }
+    gc_mapped_buf& operator=(gc_mapped_buf&& o) noexcept
+    {
+        gc_owned_buf<T, Mem>::operator=(std::move(o));
+        dev = o.dev;
+        o.dev = nullptr;
+        return *this;
+    }
+    // the memory alone; map() asks for the device view later (a caller that can do without the view when mapping fails)
+    hipError_t alloc_host(size_t n)
+    {
+        dev = nullptr;
+        return gc_owned_buf<T, Mem>::alloc(n);
+    }
+    hipError_t map()
+    {
+        void* dv = nullptr;
+        const hipError_t e = Mem::device_view(&dv, this->get());
+        dev = e == hipSuccess ? static_cast<T*>(dv) : nullptr;
+        return e;
+    }
+    // memory and view, or nothing
+    hipError_t alloc(size_t n)
+    {
+        hipError_t e = alloc_host(n);
+        if (e == hipSuccess && (e = map()) != hipSuccess) reset();
+        return e;
+    }
+    hipError_t reserve(size_t n) { return n <= this->cap ? hipSuccess : alloc(n); }
+    void reset()
+    {
+        gc_owned_buf<T, Mem>::reset();
+        dev = nullptr;
+    }
+};
 
 static inline hipStream_t gc_pick_stream(gc_ctx* ctx, void* stream)
 {

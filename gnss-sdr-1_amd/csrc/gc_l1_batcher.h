@@ -19,10 +19,11 @@
 // Backend concept:
 //   typedef Chan;    channel descriptor copied into the lane's array; has a member `const void* iq`
 //   typedef Params;  per-call parameter record
-//   struct Lane { Chan* h_chans; Params* h_params; char* h_out;            page-locked arrays of MAXB entries
-//                 char* d_span; size_t span_cap;                           device buffer for shared windows
-//                 char* h_span; const char* dv_span; size_t hspan_cap;     page-locked staging for unions + its device view
-//                 ... };
+//   struct Lane { h_chans; h_params; h_out;                                 page-locked arrays of MAXB Chan / Params / result bytes
+//                 d_span; size_t span_cap;                                 device buffer for shared windows
+//                 h_span; const char* dv_span;                             page-locked staging for unions + its device view
+//                 ... };                                                   h_* and d_span: pointers, or owners that convert to one
+//                                                                          (indexed and offset here, never assigned)
 //   struct Guard { explicit Guard(Backend&); };                            RAII "this thread talks to the batcher's device"
 //   bool lane_init(Lane&, int maxb, int max_out_bytes); void lane_free(Lane&);
 //   bool span_reserve(Lane&, size_t); bool hspan_reserve(Lane&, size_t);

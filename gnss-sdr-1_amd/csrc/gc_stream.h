@@ -15,6 +15,9 @@ struct gc_hip_event_policy
     static bool record(hipEvent_t e, hipStream_t st) { return hipEventRecord(e, st) == hipSuccess; }
 };
 
+// bytes of one complex sample of a gc_iq_format
+static inline size_t gc_iq_sample_bytes(int iq_format) { return iq_format == GC_IQ_F32 ? 8 : iq_format == GC_IQ_I16 ? 4 : 2; }
+
 // samples behind the mirror that belong to the ring's storage and stay zero, samples each guard band holds at least, and the
 // byte the bands are filled with (gc_stream.hip has the layout and what each is for)
 static const uint64_t GC_STREAM_SLACK = 2;

@@ -112,7 +112,7 @@ gc_status gc_stream_create(gc_ctx* ctx, int iq_format, uint64_t capacity_samples
     s->ctx = ctx;
     s->ctx_ref.bind(ctx);
     s->iq_format = iq_format;
-    s->elem = iq_format == GC_IQ_F32 ? 8 : iq_format == GC_IQ_I16 ? 4 : 2;
+    s->elem = gc_iq_sample_bytes(iq_format);
     s->capacity = capacity_samples;
     s->mirror = max_window_samples;
     s->slot_bytes = (size_t)4 << 20;

@@ -20,6 +20,7 @@
 #include <cstddef>
 #include <cstdlib>
 #include "gc_stream.h"
+#include "trk_batch_plan.h"
 #include "trk_loop_device.hpp"
 #include <cstring>
 #include <vector>
@@ -249,14 +250,23 @@ __global__ void trk_loop_start_kernel(LoopChan* chans, int ch)
 // -----------------------------------------------------------------------------
 // host API
 // -----------------------------------------------------------------------------
+// an event made without timing, destroyed with the engine
+struct LoopEvent
+{
+    hipEvent_t e = nullptr;
+    hipError_t create() { return hipEventCreateWithFlags(&e, hipEventDisableTiming); }
+    ~LoopEvent() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+};
+
 struct gc_trk_loop
 {
     gc_ctx* ctx = nullptr;
     gc_ctx_ref ctx_ref;
     int n_channels = 0, max_code_len = 0, n_taps = 0;
-    LoopChan* d_chans = nullptr;
-    float* d_codes = nullptr;
-    float* d_data_codes = nullptr;            // pilot tracking: data-component replicas, allocated on first use
+    gc_dev_buf<LoopChan> d_chans;
+    gc_dev_buf<float> d_codes;
+    gc_dev_buf<float> d_data_codes;           // pilot tracking: data-component replicas, allocated on first use
     std::vector<LoopSync> sync;               // per channel (gc_trk_loop_set_sync); extend_symbols == 0: none installed
     std::vector<int> data_code_len;           // samples of the data replica uploaded for the channel (0: none)
     int pilot = -1;                           // pilot mode of the started channels (-1: none started yet)
@@ -264,14 +274,12 @@ struct gc_trk_loop
     int mixed = 0;                            // gc_trk_loop_set_mixed: tap count and pilot mode per channel (the mixed kernel)
     std::vector<int> code_len;                // per channel: samples of the replica it was started with
     std::vector<char> track_pilot;            // per channel: pilot mode it was started with
-    gc_loop_record* d_recs = nullptr;
-    size_t recs_cap = 0;
+    gc_dev_buf<gc_loop_record> d_recs;
     int forced_threads = 0;  // gc_trk_loop_set_geometry: threads per workgroup of the persistent kernel (0: by channel count)
     int forced_slices = 0;   // gc_trk_loop_set_geometry: workgroups per channel-period (0: by channel count; 1: persistent kernel)
-    LoopPrep* d_prep = nullptr;      // sliced launches: next period's correlator scalars per channel
-    float2* d_slice_partial = nullptr;
-    unsigned* d_tickets = nullptr;
-    int slice_cap = 0;               // slices the partial buffer was allocated for
+    gc_dev_buf<LoopPrep> d_prep;     // sliced launches: next period's correlator scalars per channel
+    gc_dev_buf<float2> d_slice_partial;
+    gc_dev_buf<unsigned> d_tickets;
     int iq_format = GC_IQ_F32;  // sample format of every channel's input (gc_trk_loop_set_input_format)
     std::vector<char> started;
     std::vector<const void*> iq;
@@ -285,13 +293,16 @@ struct gc_trk_loop
     // launch that reads the device copy): an asynchronous launch keeps its slot until it has finished, so back-to-back
     // push -> run_dev -> push -> run_dev never rewrites limits an earlier, still queued launch will read.
     static constexpr int LIMIT_SLOTS = 8;
-    unsigned long long* d_limits[LIMIT_SLOTS] = {};
-    unsigned long long* h_limits[LIMIT_SLOTS] = {};   // pinned
-    hipEvent_t limit_done[LIMIT_SLOTS] = {};
-    bool limit_used[LIMIT_SLOTS] = {};
+    struct LimitSlot
+    {
+        gc_dev_buf<unsigned long long> d;
+        gc_host_buf<unsigned long long> h;  // pinned
+        LoopEvent done;
+        bool used = false;
+    } limits[LIMIT_SLOTS];
     int limit_next = 0;
     // the last launch of the engine, on whatever stream the caller chose: entry points that rewrite device state wait for it
-    hipEvent_t last_launch = nullptr;
+    LoopEvent last_launch;
     bool launched = false;
 };
 
@@ -303,17 +314,6 @@ static hipError_t loop_quiesce(gc_trk_loop* l)
     return e;
 }
 
-static void loop_free_limits(gc_trk_loop* l)
-{
-    for (int k = 0; k < gc_trk_loop::LIMIT_SLOTS; k++)
-        {
-            (void)hipFree(l->d_limits[k]);
-            if (l->h_limits[k]) (void)hipHostFree(l->h_limits[k]);
-            if (l->limit_done[k]) (void)hipEventDestroy(l->limit_done[k]);
-        }
-    if (l->last_launch) (void)hipEventDestroy(l->last_launch);
-}
-
 extern "C" {
 
 gc_status gc_trk_loop_create(gc_ctx* ctx, int n_channels, int max_code_length, gc_trk_loop** out)
@@ -321,22 +321,16 @@ gc_status gc_trk_loop_create(gc_ctx* ctx, int n_channels, int max_code_length, g
     GC_REQUIRE(ctx && out, "gc_trk_loop_create: NULL argument");
     *out = nullptr;
     GC_REQUIRE(n_channels > 0, "gc_trk_loop_create: n_channels must be > 0");
-    GC_REQUIRE(max_code_length > 0 && max_code_length + 64 <= 16000, "gc_trk_loop_create: max_code_length must be in 1..%d", 16000 - 64);
+    GC_REQUIRE(max_code_length > 0 && max_code_length + TRK_LDS_MARGIN_FLOATS <= TRK_LDS_TABLE_FLOATS, "gc_trk_loop_create: max_code_length must be in 1..%d",
+        TRK_LDS_TABLE_FLOATS - TRK_LDS_MARGIN_FLOATS);
     gc_device_guard g(ctx->device);
-    gc_trk_loop* l = new gc_trk_loop();
+    std::unique_ptr<gc_trk_loop> l(new gc_trk_loop());
     l->ctx = ctx;
     l->ctx_ref.bind(ctx);
     l->n_channels = n_channels;
     l->max_code_len = max_code_length;
-    hipError_t e1 = hipMalloc(&l->d_chans, sizeof(LoopChan) * n_channels);
-    hipError_t e2 = hipMalloc(&l->d_codes, sizeof(float) * (size_t)n_channels * max_code_length);
-    if (e1 != hipSuccess || e2 != hipSuccess)
-        {
-            (void)hipFree(l->d_chans);
-            (void)hipFree(l->d_codes);
-            delete l;
-            return gc_fail(GC_ERR_HIP, "gc_trk_loop_create: hipMalloc failed");
-        }
+    if (l->d_chans.alloc(n_channels) != hipSuccess || l->d_codes.alloc((size_t)n_channels * max_code_length) != hipSuccess)
+        return gc_fail(GC_ERR_HIP, "gc_trk_loop_create: hipMalloc failed");
     (void)hipMemset(l->d_chans, 0, sizeof(LoopChan) * n_channels);
     l->started.assign(n_channels, 0);
     l->sync.assign(n_channels, LoopSync());
@@ -349,20 +343,11 @@ gc_status gc_trk_loop_create(gc_ctx* ctx, int n_channels, int max_code_length, g
     l->pos_host.assign(n_channels, 0);
     l->pos_known.assign(n_channels, 0);
     l->idle.assign(n_channels, 0);
-    bool ok = hipEventCreateWithFlags(&l->last_launch, hipEventDisableTiming) == hipSuccess;
-    for (int k = 0; k < gc_trk_loop::LIMIT_SLOTS && ok; k++)
-        ok = hipMalloc(&l->d_limits[k], sizeof(unsigned long long) * n_channels) == hipSuccess &&
-             hipHostMalloc(reinterpret_cast<void**>(&l->h_limits[k]), sizeof(unsigned long long) * n_channels, hipHostMallocDefault) == hipSuccess &&
-             hipEventCreateWithFlags(&l->limit_done[k], hipEventDisableTiming) == hipSuccess;
-    if (!ok)
-        {
-            loop_free_limits(l);
-            (void)hipFree(l->d_chans);
-            (void)hipFree(l->d_codes);
-            delete l;
-            return gc_fail(GC_ERR_HIP, "gc_trk_loop_create: allocation failed");
-        }
-    *out = l;
+    bool ok = l->last_launch.create() == hipSuccess;
+    for (gc_trk_loop::LimitSlot& s : l->limits)
+        ok = ok && s.d.alloc(n_channels) == hipSuccess && s.h.alloc(n_channels) == hipSuccess && s.done.create() == hipSuccess;
+    if (!ok) return gc_fail(GC_ERR_HIP, "gc_trk_loop_create: allocation failed");
+    *out = l.release();
     return GC_OK;
 }
 
@@ -371,14 +356,6 @@ gc_status gc_trk_loop_destroy(gc_trk_loop* l)
     if (!l) return GC_OK;
     gc_device_guard g(l->ctx->device);
     (void)loop_quiesce(l);
-    (void)hipFree(l->d_chans);
-    (void)hipFree(l->d_codes);
-    (void)hipFree(l->d_data_codes);
-    (void)hipFree(l->d_recs);
-    (void)hipFree(l->d_prep);
-    (void)hipFree(l->d_slice_partial);
-    (void)hipFree(l->d_tickets);
-    loop_free_limits(l);
     for (gc_stream* r : l->streams)
         if (r) gc_stream_drop(r);
     delete l;
@@ -418,7 +395,7 @@ gc_status gc_trk_loop_set_input_dev(gc_trk_loop* l, int ch, const void* dev_iq, 
 {
     GC_REQUIRE(l && dev_iq, "gc_trk_loop_set_input_dev: NULL argument");
     GC_REQUIRE(ch >= 0 && ch < l->n_channels, "gc_trk_loop_set_input_dev: channel %d out of range", ch);
-    const uintptr_t es = l->iq_format == GC_IQ_F32 ? 8 : l->iq_format == GC_IQ_I16 ? 4 : 2;
+    const uintptr_t es = gc_iq_sample_bytes(l->iq_format);
     GC_REQUIRE((reinterpret_cast<uintptr_t>(dev_iq) % es) == 0, "gc_trk_loop_set_input_dev: IQ pointer must be aligned to one sample (%d bytes)", (int)es);
     gc_device_guard g(l->ctx->device);
     std::lock_guard<std::mutex> lk(l->ctx->mtx);
@@ -518,7 +495,7 @@ gc_status gc_trk_loop_set_sync(gc_trk_loop* l, int ch, const gc_loop_sync_conf* 
             GC_REQUIRE(data_code, "gc_trk_loop_set_sync: track_pilot needs the data component's replica");
             GC_REQUIRE(data_code_length > 0 && data_code_length <= l->max_code_len, "gc_trk_loop_set_sync: data_code_length %d not in 1..%d", data_code_length,
                 l->max_code_len);
-            if (!l->d_data_codes) GC_HIP(hipMalloc(&l->d_data_codes, sizeof(float) * (size_t)l->n_channels * l->max_code_len));
+            if (!l->d_data_codes) GC_HIP(l->d_data_codes.alloc((size_t)l->n_channels * l->max_code_len));
             GC_HIP(loop_quiesce(l));
             GC_HIP(hipMemcpy(l->d_data_codes + (size_t)ch * l->max_code_len, data_code, sizeof(float) * data_code_length, hipMemcpyHostToDevice));
             l->data_code_len[ch] = data_code_length;  // must equal the tracking replica's length: checked at start
@@ -687,18 +664,13 @@ static hipError_t loop_launch_slices(gc_trk_loop* l, bool pilot, int n_epochs, g
 // slice buffers of the engine, grown on demand
 static hipError_t loop_slices_reserve(gc_trk_loop* l, int n_slices, hipStream_t st)
 {
-    if (l->d_prep && n_slices <= l->slice_cap) return hipSuccess;
-    hipError_t e = hipSuccess;
-    (void)hipFree(l->d_slice_partial);
-    l->d_slice_partial = nullptr;
-    if (!l->d_prep) e = hipMalloc(&l->d_prep, sizeof(LoopPrep) * l->n_channels);
+    hipError_t e = l->d_prep ? hipSuccess : l->d_prep.alloc(l->n_channels);
     if (e == hipSuccess && !l->d_tickets)
         {
-            e = hipMalloc(&l->d_tickets, sizeof(unsigned) * l->n_channels);
+            e = l->d_tickets.alloc(l->n_channels);
             if (e == hipSuccess) e = hipMemsetAsync(l->d_tickets, 0, sizeof(unsigned) * l->n_channels, st);
         }
-    if (e == hipSuccess) e = hipMalloc(&l->d_slice_partial, sizeof(float2) * GC_MAX_TAPS * (size_t)l->n_channels * n_slices);
-    if (e == hipSuccess) l->slice_cap = n_slices;
+    if (e == hipSuccess) e = l->d_slice_partial.reserve((size_t)GC_MAX_TAPS * l->n_channels * n_slices);
     return e;
 }
 
@@ -800,8 +772,9 @@ static gc_status loop_launch(gc_trk_loop* l, int n_epochs, gc_loop_record* dev_r
         return gc_fail(GC_ERR_STATE, "gc_trk_loop_run: no channel has been started (gc_trk_loop_start)");
     // this launch's slot of the limits ring: free once the launch that used it last has finished
     const int slot = l->limit_next;
-    if (l->limit_used[slot]) GC_HIP(hipEventSynchronize(l->limit_done[slot]));
-    unsigned long long* h_limits = l->h_limits[slot];
+    gc_trk_loop::LimitSlot& lim = l->limits[slot];
+    if (lim.used) GC_HIP(hipEventSynchronize(lim.done));
+    unsigned long long* h_limits = lim.h;
     // ring inputs: this launch may use what has been pushed so far, and must not be overtaken by later pushes.  One reservation per
     // ring, taken before the residency check and the enqueue; the limits are the heads seen by those reservations.
     LoopRings rings;
@@ -819,10 +792,10 @@ static gc_status loop_launch(gc_trk_loop* l, int n_epochs, gc_loop_record* dev_r
         {
             for (int i = 0; i < l->n_channels; i++)
                 if (l->streams[i] && l->started[i] && !l->idle[i]) h_limits[i] = reads.ticket(l->streams[i]).head;
-            hipError_t ce = hipMemcpyAsync(l->d_limits[slot], h_limits, sizeof(unsigned long long) * l->n_channels, hipMemcpyHostToDevice, st);
+            hipError_t ce = hipMemcpyAsync(lim.d, h_limits, sizeof(unsigned long long) * l->n_channels, hipMemcpyHostToDevice, st);
             if (ce != hipSuccess) return gc_fail(GC_ERR_HIP, "gc_trk_loop_run: %s", hipGetErrorString(ce));
         }
-    const unsigned long long* limits = rings.any ? l->d_limits[slot] : nullptr;
+    const unsigned long long* limits = rings.any ? lim.d.get() : nullptr;
     const bool pilot = l->pilot > 0;
     const TrkLoopPlan plan = trk_loop_plan(l->n_channels, l->ctx->n_cus, l->high_dyn != 0, l->forced_threads, l->mixed != 0, l->started.data(),
         l->code_len.data(), l->track_pilot.data(), l->max_code_len, pilot);
@@ -848,10 +821,10 @@ static gc_status loop_launch(gc_trk_loop* l, int n_epochs, gc_loop_record* dev_r
     l->launched = true;
     if (ee == hipSuccess && rings.any)
         {
-            ee = hipEventRecord(l->limit_done[slot], st);
+            ee = hipEventRecord(lim.done, st);
             if (ee == hipSuccess)
                 {
-                    l->limit_used[slot] = true;
+                    lim.used = true;
                     l->limit_next = (slot + 1) % gc_trk_loop::LIMIT_SLOTS;
                 }
         }
@@ -884,14 +857,7 @@ gc_status gc_trk_loop_run(gc_trk_loop* l, int n_epochs, gc_loop_record* host_rec
     std::lock_guard<std::mutex> lk(l->ctx->mtx);
     hipStream_t st = l->ctx->stream;
     const size_t n = (size_t)l->n_channels * n_epochs;
-    if (n > l->recs_cap)
-        {
-            (void)hipFree(l->d_recs);
-            l->d_recs = nullptr;
-            l->recs_cap = 0;
-            GC_HIP(hipMalloc(&l->d_recs, n * sizeof(gc_loop_record)));
-            l->recs_cap = n;
-        }
+    GC_HIP(l->d_recs.reserve(n));
     gc_status s = loop_launch(l, n_epochs, l->d_recs, st, true);
     if (s != GC_OK) return s;
     GC_HIP(hipMemcpyAsync(host_records, l->d_recs, n * sizeof(gc_loop_record), hipMemcpyDeviceToHost, st));
