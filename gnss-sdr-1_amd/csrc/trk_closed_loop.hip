@@ -17,11 +17,13 @@
 // gc_trk_loop_set_mixed in trk_closed_loop_mixed.hip.
 #include "gc_internal.h"
 #include <algorithm>
+#include <cmath>
 #include <cstddef>
 #include <cstdlib>
 #include "gc_stream.h"
 #include "trk_batch_plan.h"
 #include "trk_loop_device.hpp"
+#include "trk_glonass_loop_device.hpp"
 #include <cstring>
 #include <vector>
 
@@ -272,6 +274,8 @@ struct gc_trk_loop
     int pilot = -1;                           // pilot mode of the started channels (-1: none started yet)
     int high_dyn = 0;                         // high-dynamics mode of the started channels
     int mixed = 0;                            // gc_trk_loop_set_mixed: tap count and pilot mode per channel (the mixed kernel)
+    int glonass = 0;                          // the running channels are GLONASS channels (gc_trk_loop_start_glonass): their kernel, their state
+    gc_dev_buf<GloChan> d_glo;                // the GLONASS channels' state, allocated on first use
     std::vector<int> code_len;                // per channel: samples of the replica it was started with
     std::vector<char> track_pilot;            // per channel: pilot mode it was started with
     gc_dev_buf<gc_loop_record> d_recs;
@@ -407,6 +411,17 @@ gc_status gc_trk_loop_set_input_dev(gc_trk_loop* l, int ch, const void* dev_iq, 
         {
             // a running channel keeps its state; only the input block changes (stream position restarts at 0)
             GC_HIP(loop_quiesce(l));
+            if (l->glonass)
+                {
+                    GloChan h;
+                    GC_HIP(hipMemcpy(&h, l->d_glo + ch, sizeof h, hipMemcpyDeviceToHost));
+                    h.chan.iq = dev_iq;
+                    h.chan.n_iq = n_samples;
+                    h.chan.ring_len = 0;
+                    h.pos = 0;
+                    GC_HIP(hipMemcpy(l->d_glo + ch, &h, sizeof h, hipMemcpyHostToDevice));
+                    return GC_OK;
+                }
             LoopChan h;
             GC_HIP(hipMemcpy(&h, l->d_chans + ch, sizeof h, hipMemcpyDeviceToHost));
             h.chan.iq = dev_iq;
@@ -518,6 +533,13 @@ gc_status gc_trk_loop_start(gc_trk_loop* l, int ch, const gc_loop_conf* conf, co
     const int n_taps = conf->veml ? 5 : 3;
     gc_device_guard g(l->ctx->device);
     std::lock_guard<std::mutex> lk(l->ctx->mtx);
+    if (l->glonass)
+        {
+            // the running channels of an engine are all of one kind: free again once every GLONASS channel has been stopped
+            for (int i = 0; i < l->n_channels; i++)
+                if (l->started[i]) return gc_fail(GC_ERR_STATE, "gc_trk_loop_start: channel %d runs as a GLONASS channel (gc_trk_loop_start_glonass); stop it first", i);
+            l->glonass = 0;
+        }
     if (!l->mixed)
         {
             // the engine's tap count is that of its running channels: it is free again once every channel has been stopped
@@ -612,8 +634,102 @@ extern "C" gc_status gc_trk_loop_stop(gc_trk_loop* l, int ch)
     GC_HIP(loop_quiesce(l));
     // n_taps = 0 marks the slot as standby for the kernel; the rest of the state is rewritten by the next start
     int zero = 0;
-    GC_HIP(hipMemcpy(reinterpret_cast<char*>(l->d_chans + ch) + offsetof(LoopChan, n_taps), &zero, sizeof zero, hipMemcpyHostToDevice));
+    if (l->glonass)
+        GC_HIP(hipMemcpy(reinterpret_cast<char*>(l->d_glo + ch) + offsetof(GloChan, n_taps), &zero, sizeof zero, hipMemcpyHostToDevice));
+    else
+        GC_HIP(hipMemcpy(reinterpret_cast<char*>(l->d_chans + ch) + offsetof(LoopChan, n_taps), &zero, sizeof zero, hipMemcpyHostToDevice));
     l->started[ch] = 0;
+    return GC_OK;
+}
+
+extern "C" size_t gc_glonass_loop_conf_size(void) { return sizeof(gc_glonass_loop_conf); }
+
+// glonass_l1_ca_dll_pll_tracking_cc::start_tracking (:160-243) for channel `ch`: every argument is checked before anything touches
+// a device -- the configuration first (it needs no handle), then the handle and the engine's state
+extern "C" gc_status gc_trk_loop_start_glonass(gc_trk_loop* l, int ch, const gc_glonass_loop_conf* conf)
+{
+    GC_REQUIRE(conf, "gc_trk_loop_start_glonass: NULL configuration");
+    GC_REQUIRE(conf->fs_in >= 1000.0 && conf->fs_in <= 1e9 && conf->fs_in == std::floor(conf->fs_in), "gc_trk_loop_start_glonass: fs_in must be a whole number of samples per second in 1e3..1e9");
+    GC_REQUIRE(conf->vector_length >= 1 && conf->vector_length <= (1u << 24), "gc_trk_loop_start_glonass: vector_length must be in 1..2^24");
+    GC_REQUIRE(conf->band_carrier_freq_hz > 0 && conf->band_carrier_freq_hz + conf->channel_offset_hz > 0, "gc_trk_loop_start_glonass: bad carrier frequency");
+    GC_REQUIRE(conf->cn0_samples >= 1 && conf->cn0_samples <= LOOP_MAX_CN0, "gc_trk_loop_start_glonass: cn0_samples must be in 1..%d", LOOP_MAX_CN0);
+    GC_REQUIRE(conf->pll_bw_hz > 0 && conf->dll_bw_hz > 0, "gc_trk_loop_start_glonass: loop bandwidths must be > 0");
+    GC_REQUIRE(conf->early_late_space_chips > 0 && conf->early_late_space_chips <= 16.0f, "gc_trk_loop_start_glonass: early_late_space_chips must be in (0, 16]");
+    GC_REQUIRE(std::isfinite(conf->acq_delay_samples) && std::isfinite(conf->acq_doppler_hz) && std::fabs(conf->acq_delay_samples) <= 1e9 && std::fabs(conf->acq_doppler_hz) <= 1e6,
+        "gc_trk_loop_start_glonass: bad acquisition hand-over");
+    GC_REQUIRE(conf->sample_counter >= conf->acq_samplestamp_samples, "gc_trk_loop_start_glonass: sample_counter lies before acq_samplestamp_samples");
+    GloChan h;
+    std::memset(&h, 0, sizeof h);
+    h.conf = *conf;
+    glo_loop_start(h);
+    GC_REQUIRE(h.current_prn_length_samples >= 1 && (unsigned)h.current_prn_length_samples <= 2u * conf->vector_length,
+        "gc_trk_loop_start_glonass: the code period is %d samples, outside 1..2 * vector_length (%u)", h.current_prn_length_samples, conf->vector_length);
+    GC_REQUIRE(l, "gc_trk_loop_start_glonass: NULL handle");
+    GC_REQUIRE(ch >= 0 && ch < l->n_channels, "gc_trk_loop_start_glonass: channel %d out of range", ch);
+    GC_REQUIRE(l->max_code_len >= GLO_CODE_LENGTH, "gc_trk_loop_start_glonass: the engine's max_code_length %d is below the %d chips of the replica", l->max_code_len,
+        GLO_CODE_LENGTH);
+    GC_REQUIRE(l->iq[ch] != nullptr, "gc_trk_loop_start_glonass: channel %d has no input (gc_trk_loop_set_input_dev)", ch);
+    gc_device_guard g(l->ctx->device);
+    std::lock_guard<std::mutex> lk(l->ctx->mtx);
+    if (l->mixed) return gc_fail(GC_ERR_STATE, "gc_trk_loop_start_glonass: a mixed engine (gc_trk_loop_set_mixed) has no GLONASS slots; run a GLONASS engine beside it");
+    if (!l->glonass)
+        for (int i = 0; i < l->n_channels; i++)
+            if (l->started[i]) return gc_fail(GC_ERR_STATE, "gc_trk_loop_start_glonass: channel %d runs as a veml channel (gc_trk_loop_start); stop it first", i);
+    if (gc_stream* r = l->streams[ch])
+        {
+            GC_REQUIRE(2ull * conf->vector_length <= r->mirror, "gc_trk_loop_start_glonass: 2 * vector_length (%u) exceeds the stream's max_window %llu", conf->vector_length,
+                (unsigned long long)r->mirror);
+            h.chan.ring_len = (unsigned)r->capacity;
+        }
+    float chips[GLO_CODE_LENGTH];
+    const gc_status cs = gc_glonass_l1_ca_code_gen_float(chips, 0);
+    if (cs != GC_OK) return cs;
+    GC_HIP(loop_quiesce(l));
+    if (!l->d_glo)
+        {
+            GC_HIP(l->d_glo.alloc(l->n_channels));
+            GC_HIP(hipMemset(l->d_glo, 0, sizeof(GloChan) * l->n_channels));
+        }
+    l->code_len[ch] = GLO_CODE_LENGTH;
+    l->track_pilot[ch] = 0;
+    GC_HIP(hipMemcpy(l->d_codes + (size_t)ch * l->max_code_len, chips, sizeof chips, hipMemcpyHostToDevice));
+    h.chan.iq = l->iq[ch];
+    h.chan.n_iq = l->n_iq[ch];
+    h.chan.code = l->d_codes + (size_t)ch * l->max_code_len;
+    h.chan.code_len = GLO_CODE_LENGTH;
+    h.chan.shifts[0] = -conf->early_late_space_chips;
+    h.chan.shifts[1] = 0.0f;
+    h.chan.shifts[2] = conf->early_late_space_chips;
+    h.n_taps = 3;
+    // ring input is addressed with absolute stream sample numbers: the channel starts where its counter says
+    h.pos = l->streams[ch] ? conf->sample_counter : 0;
+    l->pos_host[ch] = h.pos;
+    l->pos_known[ch] = 1;
+    l->idle[ch] = 0;
+    GC_HIP(hipMemcpy(l->d_glo + ch, &h, sizeof h, hipMemcpyHostToDevice));
+    l->glonass = 1;  // nothing can fail any more: the engine's kind changes together with its first running channel
+    l->started[ch] = 1;
+    return GC_OK;
+}
+
+// the pull-in alignment of a start with `conf`, on the host: glo_loop_start and glo_loop_pull_in, the statements the kernel runs
+extern "C" gc_status gc_glonass_loop_pull_in(const gc_glonass_loop_conf* conf, int32_t* samples_offset, uint64_t* sample_counter, double* acc_carrier_phase_rad)
+{
+    GC_REQUIRE(conf, "gc_glonass_loop_pull_in: NULL configuration");
+    GC_REQUIRE(conf->fs_in >= 1000.0 && conf->fs_in <= 1e9 && conf->fs_in == std::floor(conf->fs_in), "gc_glonass_loop_pull_in: fs_in must be a whole number of samples per second in 1e3..1e9");
+    GC_REQUIRE(conf->band_carrier_freq_hz > 0 && conf->band_carrier_freq_hz + conf->channel_offset_hz > 0, "gc_glonass_loop_pull_in: bad carrier frequency");
+    GC_REQUIRE(std::isfinite(conf->acq_delay_samples) && std::isfinite(conf->acq_doppler_hz) && std::fabs(conf->acq_delay_samples) <= 1e9 && std::fabs(conf->acq_doppler_hz) <= 1e6,
+        "gc_glonass_loop_pull_in: bad acquisition hand-over");
+    GC_REQUIRE(conf->sample_counter >= conf->acq_samplestamp_samples, "gc_glonass_loop_pull_in: sample_counter lies before acq_samplestamp_samples");
+    GloChan h;
+    std::memset(&h, 0, sizeof h);
+    h.conf = *conf;
+    glo_loop_start(h);
+    GC_REQUIRE(h.current_prn_length_samples >= 1, "gc_glonass_loop_pull_in: the code period is %d samples", h.current_prn_length_samples);
+    const int offset = glo_loop_pull_in(h);
+    if (samples_offset) *samples_offset = offset;
+    if (sample_counter) *sample_counter = h.sample_counter;
+    if (acc_carrier_phase_rad) *acc_carrier_phase_rad = h.acc_carrier_phase_rad;
     return GC_OK;
 }
 
@@ -796,25 +912,34 @@ static gc_status loop_launch(gc_trk_loop* l, int n_epochs, gc_loop_record* dev_r
             if (ce != hipSuccess) return gc_fail(GC_ERR_HIP, "gc_trk_loop_run: %s", hipGetErrorString(ce));
         }
     const unsigned long long* limits = rings.any ? lim.d.get() : nullptr;
-    const bool pilot = l->pilot > 0;
-    const TrkLoopPlan plan = trk_loop_plan(l->n_channels, l->ctx->n_cus, l->high_dyn != 0, l->forced_threads, l->mixed != 0, l->started.data(),
-        l->code_len.data(), l->track_pilot.data(), l->max_code_len, pilot);
-    const LoopLaunch a = {l->d_chans, l->n_channels, n_epochs, dev_records, st, plan, limits};
-    // workgroups per channel-period: 1 = the persistent one-workgroup-per-channel kernel (always, in the product library); an
-    // experiments build cuts the period into slices on request (gc_trk_loop_set_geometry), one launch per period: measured slower
     hipError_t le;
-#ifdef GNSSCORR_EXPERIMENTS
-    if (!l->mixed && l->forced_slices > 1)
+    if (l->glonass)
         {
-            GC_HIP(loop_slices_reserve(l, l->forced_slices, st));
-            le = loop_launch_slices(l, pilot, n_epochs, dev_records, st, l->forced_slices, (l->max_code_len + 64) * (pilot ? 2 : 1), limits);
+            // a GLONASS engine: its own kernel; the 511-chip replica always sits in LDS as the doubled resident image
+            const TrkLoopPlan gp = trk_loop_plan(l->n_channels, l->ctx->n_cus, false, l->forced_threads, false, nullptr, nullptr, nullptr, GLO_CODE_LENGTH, false);
+            le = glo_loop_launch(l->d_glo, l->n_channels, l->iq_format, gp.threads, n_epochs, dev_records, st, gp.lds_table_floats, gp.lds_bytes, limits);
         }
     else
+        {
+            const bool pilot = l->pilot > 0;
+            const TrkLoopPlan plan = trk_loop_plan(l->n_channels, l->ctx->n_cus, l->high_dyn != 0, l->forced_threads, l->mixed != 0, l->started.data(),
+                l->code_len.data(), l->track_pilot.data(), l->max_code_len, pilot);
+            const LoopLaunch a = {l->d_chans, l->n_channels, n_epochs, dev_records, st, plan, limits};
+            // workgroups per channel-period: 1 = the persistent one-workgroup-per-channel kernel (always, in the product library); an
+            // experiments build cuts the period into slices on request (gc_trk_loop_set_geometry), one launch per period: measured slower
+#ifdef GNSSCORR_EXPERIMENTS
+            if (!l->mixed && l->forced_slices > 1)
+                {
+                    GC_HIP(loop_slices_reserve(l, l->forced_slices, st));
+                    le = loop_launch_slices(l, pilot, n_epochs, dev_records, st, l->forced_slices, (l->max_code_len + 64) * (pilot ? 2 : 1), limits);
+                }
+            else
 #endif
-    if (l->mixed)
-        le = loop_launch_mixed(l->d_chans, l->n_channels, l->iq_format, l->high_dyn, plan.threads, n_epochs, dev_records, st, plan.lds_table_floats, limits, plan.resident);
-    else
-        le = loop_launch_plain(a, l->n_taps, l->iq_format, pilot, l->high_dyn != 0);
+            if (l->mixed)
+                le = loop_launch_mixed(l->d_chans, l->n_channels, l->iq_format, l->high_dyn, plan.threads, n_epochs, dev_records, st, plan.lds_table_floats, limits, plan.resident);
+            else
+                le = loop_launch_plain(a, l->n_taps, l->iq_format, pilot, l->high_dyn != 0);
+        }
     if (le != hipSuccess) return gc_fail(GC_ERR_HIP, "gc_trk_loop_run: kernel launch failed: %s", hipGetErrorString(le));
     gc_status out = GC_OK;
     hipError_t ee = hipEventRecord(l->last_launch, st);

@@ -255,6 +255,36 @@ static __device__ void loop_start(LoopChan& s)
     s.carr_hist_n = s.code_hist_n = 0;
 }
 
+// cn0_svn_estimator (lock_detectors.cc:71-90) over `length` prompts
+static __device__ __forceinline__ float loop_cn0_svn_estimator(const float2* prompt_buffer, int length, double coh_integration_time_s)
+{
+    double Psig = 0.0, Ptot = 0.0;
+    for (int i = 0; i < length; i++)
+        {
+            const float2 v = prompt_buffer[i];
+            Psig += fabs((double)v.x);
+            Ptot += (double)v.y * (double)v.y + (double)v.x * (double)v.x;
+        }
+    Psig /= (double)length;
+    Psig = Psig * Psig;
+    Ptot /= (double)length;
+    const double SNR = Psig / (Ptot - Psig);
+    return (float)(10.0 * log10(SNR) - 10.0 * log10(coh_integration_time_s));
+}
+
+// carrier_lock_detector (lock_detectors.cc:94-111)
+static __device__ __forceinline__ float loop_carrier_lock_detector(const float2* prompt_buffer, int length)
+{
+    float sum_I = 0.f, sum_Q = 0.f;
+    for (int i = 0; i < length; i++)
+        {
+            sum_I += prompt_buffer[i].x;
+            sum_Q += prompt_buffer[i].y;
+        }
+    const float NBP = sum_I * sum_I + sum_Q * sum_Q, NBD = sum_I * sum_I - sum_Q * sum_Q;
+    return NBD / NBP;
+}
+
 // cn0_and_tracking_lock_status (:839-878); false = loss of lock
 static __device__ __forceinline__ bool loop_lock_status(LoopChan& s, double coh_integration_time_s)
 {
@@ -266,23 +296,8 @@ static __device__ __forceinline__ bool loop_lock_status(LoopChan& s, double coh_
             return true;
         }
     s.cn0_estimation_counter = 0;
-    double Psig = 0.0, Ptot = 0.0;
-    float sum_I = 0.f, sum_Q = 0.f;
-    for (int i = 0; i < c.cn0_samples; i++)
-        {
-            const float2 v = s.prompt_buffer[i];
-            Psig += fabs((double)v.x);
-            Ptot += (double)v.y * (double)v.y + (double)v.x * (double)v.x;
-            sum_I += v.x;
-            sum_Q += v.y;
-        }
-    Psig /= (double)c.cn0_samples;
-    Psig = Psig * Psig;
-    Ptot /= (double)c.cn0_samples;
-    const double SNR = Psig / (Ptot - Psig);
-    s.cn0_db_hz = (double)(float)(10.0 * log10(SNR) - 10.0 * log10(coh_integration_time_s));
-    const float NBP = sum_I * sum_I + sum_Q * sum_Q, NBD = sum_I * sum_I - sum_Q * sum_Q;
-    s.carrier_lock_test = (double)(NBD / NBP);
+    s.cn0_db_hz = (double)loop_cn0_svn_estimator(s.prompt_buffer, c.cn0_samples, coh_integration_time_s);
+    s.carrier_lock_test = (double)loop_carrier_lock_detector(s.prompt_buffer, c.cn0_samples);
     if (!s.pull_in_transitory)
         {
             if (s.carrier_lock_test < c.carrier_lock_th || s.cn0_db_hz < c.cn0_min)

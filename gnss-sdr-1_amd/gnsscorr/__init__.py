@@ -114,6 +114,17 @@ class LoopConf(C.Structure):
     ]
 
 
+class GlonassLoopConf(C.Structure):
+    """gc_glonass_loop_conf: what the GLONASS L1 / L2 C/A tracking block knows at start_tracking()."""
+    _fields_ = [
+        ("fs_in", C.c_double), ("band_carrier_freq_hz", C.c_double), ("channel_offset_hz", C.c_double), ("carrier_lock_th", C.c_double),
+        ("acq_delay_samples", C.c_double), ("acq_doppler_hz", C.c_double), ("acq_samplestamp_samples", C.c_uint64),
+        ("sample_counter", C.c_uint64), ("vector_length", C.c_uint32), ("cn0_samples", C.c_int32), ("cn0_min", C.c_int32),
+        ("max_lock_fail", C.c_int32), ("pll_bw_hz", C.c_float), ("dll_bw_hz", C.c_float), ("early_late_space_chips", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+
 LOOP_RECORD_DTYPE = np.dtype([
     ("corr", np.float32, (10,)), ("carrier_doppler_hz", np.float32), ("code_freq_chips", np.float32),
     ("carr_phase_error_hz", np.float32), ("carr_error_filt_hz", np.float32), ("code_error_chips", np.float32),
@@ -307,6 +318,9 @@ API = {
     "gc_trk_loop_set_sync": (C.c_int, [_vp, C.c_int, C.POINTER(LoopSyncConf), _fp, C.c_int]),
     "gc_loop_sync_for_signal": (C.c_int, [C.c_char, C.c_char_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(LoopSyncConf)]),
     "gc_trk_loop_start": (C.c_int, [_vp, C.c_int, C.POINTER(LoopConf), _fp, C.c_int]),
+    "gc_glonass_loop_conf_size": (C.c_size_t, []),
+    "gc_trk_loop_start_glonass": (C.c_int, [_vp, C.c_int, C.POINTER(GlonassLoopConf)]),
+    "gc_glonass_loop_pull_in": (C.c_int, [C.POINTER(GlonassLoopConf), C.POINTER(C.c_int32), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "gc_trk_loop_stop": (C.c_int, [_vp, C.c_int]),
     "gc_trk_loop_run_dev": (C.c_int, [_vp, C.c_int, _vp, _vp]),
     "gc_trk_loop_set_geometry": (C.c_int, [_vp, C.c_int, C.c_int]),
@@ -437,6 +451,9 @@ def load_library():
         if lib.gc_blanking_conf_size() != C.sizeof(BlankingConf):
             raise GnsscorrError(GC_ERR_INVALID, "gc_blanking_conf is %d bytes in the library, %d here -- rebuild with __graft_entry__.build()"
                 % (lib.gc_blanking_conf_size(), C.sizeof(BlankingConf)))
+        if lib.gc_glonass_loop_conf_size() != C.sizeof(GlonassLoopConf):
+            raise GnsscorrError(GC_ERR_INVALID, "gc_glonass_loop_conf is %d bytes in the library, %d here -- rebuild with __graft_entry__.build()"
+                % (lib.gc_glonass_loop_conf_size(), C.sizeof(GlonassLoopConf)))
         if lib.gc_resampler_conf_size() != C.sizeof(ResamplerConf):
             raise GnsscorrError(GC_ERR_INVALID, "gc_resampler_conf is %d bytes in the library, %d here -- rebuild with __graft_entry__.build()"
                 % (lib.gc_resampler_conf_size(), C.sizeof(ResamplerConf)))
@@ -1316,6 +1333,14 @@ def stream_broadcast_pinned(streams, host_ptr, n_samples):
     _check(load_library().gc_stream_broadcast_pinned(arr, len(streams), _vp(host_ptr), int(n_samples)))
 
 
+def glonass_loop_pull_in(conf):
+    """gc_glonass_loop_pull_in: the pull-in alignment a GLONASS start with `conf` (GlonassLoopConf) performs before its first
+    period, computed on the host: (samples skipped, sample counter behind them, accumulated carrier phase in rad)."""
+    off, counter, phase = C.c_int32(0), C.c_uint64(0), C.c_double(0.0)
+    _check(load_library().gc_glonass_loop_pull_in(C.byref(conf), C.byref(off), C.byref(counter), C.byref(phase)))
+    return int(off.value), int(counter.value), float(phase.value)
+
+
 class TrackingBatch:
     """gc_trk_batch: all channels of one GPU, many epochs per launch."""
 
@@ -1448,6 +1473,11 @@ class TrackingLoop:
     def start(self, ch, conf, code):
         code = np.ascontiguousarray(code, np.float32)
         _check(load_library().gc_trk_loop_start(self._h, ch, C.byref(conf), _f32p(code), code.size))
+
+    def start_glonass(self, ch, conf):
+        """gc_trk_loop_start_glonass: channel `ch` runs the GLONASS L1 / L2 C/A block's own loop (conf: GlonassLoopConf); the
+        library generates the 511-chip replica.  The running channels of an engine are all of one kind."""
+        _check(load_library().gc_trk_loop_start_glonass(self._h, ch, C.byref(conf)))
 
     def stop(self, ch):
         _check(load_library().gc_trk_loop_stop(self._h, ch))

@@ -638,6 +638,63 @@ gc_status gc_trk_loop_set_mixed(gc_trk_loop* l, int on);
 gc_status gc_trk_loop_run_dev(gc_trk_loop* l, int n_epochs, gc_loop_record* dev_records, void* stream);
 gc_status gc_trk_loop_run(gc_trk_loop* l, int n_epochs, gc_loop_record* host_records);
 
+/* GLONASS L1 / L2 C/A channels of a loop engine: the reference tracks them with a block of its own
+ * (glonass_l1_ca_dll_pll_tracking_cc.cc / glonass_l2_...: start_tracking :160-243, general_work :549-777) whose loop is not the
+ * veml loop -- second-order Tracking_2nd_DLL_filter / Tracking_2nd_PLL_filter, the FDMA channel offset in the carrier NCO but
+ * not in the Doppler, a block length round()-ed every period with the code NCO command folded in (the period correlates the
+ * length of the previous update and consumes the new one), a C/N0 window of its own.  What the block knows at start_tracking(): */
+typedef struct
+{
+    double fs_in;                     /* a whole number of samples per second (the block's int64_t fs_in) */
+    double band_carrier_freq_hz;      /* 1.602e9 (L1) or 1.246e9 (L2) */
+    double channel_offset_hz;         /* DFRQ * k of the slot: 0.5625e6 * k or 0.4375e6 * k */
+    double carrier_lock_th;
+    double acq_delay_samples, acq_doppler_hz;
+    uint64_t acq_samplestamp_samples, sample_counter;
+    uint32_t vector_length;           /* round(fs_in / 1000) */
+    int32_t cn0_samples, cn0_min, max_lock_fail;   /* cn0_samples 1..64 */
+    float pll_bw_hz, dll_bw_hz, early_late_space_chips;
+    uint32_t reserved;
+} gc_glonass_loop_conf;
+size_t gc_glonass_loop_conf_size(void);
+/* start_tracking of the GLONASS block for channel `ch`; the library generates the 511-chip replica itself (the engine's
+ * max_code_length must be >= 511).  Input binding, stop, geometry, run and run_dev are those of every loop engine.  The running
+ * channels of an engine are all veml (gc_trk_loop_start) or all GLONASS: starting the other kind while a channel runs is
+ * GC_ERR_STATE, and so is a GLONASS start on a mixed engine (gc_trk_loop_set_mixed) -- a receiver runs a GLONASS engine beside
+ * its other engine.  With ring input 2 * vector_length <= the stream's max_window (GC_ERR_INVALID
+ * otherwise, like every argument out of range).  Every argument is checked before anything touches a device.
+ * A period runs only when its whole block [position, position + current block length) lies below the launch's limit (the end of
+ * the bound block, or the ring's head); otherwise that epoch and every later one of the launch write invalid records (all zero
+ * but `state` and `sample_counter`) and the state is unchanged, so records do not depend on how input is cut into pushes or
+ * launches.  The pull-in alignment runs before the first period and emits no record.  Loss of lock (the fail counter exceeds
+ * max_lock_fail): that period's record is still valid, the channel then sits in state 0 like a veml channel that lost lock.
+ * Deviation from the reference, which reads past the 2 * vector_length items its scheduler guarantees: a new block length outside
+ * [1, 2 * vector_length] ends tracking the same way (state 0, a lost-lock event) and that period consumes nothing.
+ * gc_loop_record of a GLONASS channel:
+ *   corr[0..5]                    E, P, L
+ *   accu[0..5]                    the same values
+ *   prompt_data                   the prompt
+ *   carrier_doppler_hz            Doppler WITHOUT the FDMA offset
+ *   code_freq_chips               code frequency after the update
+ *   carr_phase_error_hz / carr_error_filt_hz      PLL discriminator output (cycles) and the PLL filter's output
+ *   code_error_chips / code_error_filt_chips      DLL discriminator output and the DLL filter's output
+ *   cn0_db_hz, carrier_lock_test  as in the block
+ *   sample_counter                the block's Tracking_sample_counter: counter + new block length
+ *   acc_carrier_phase_rad, rem_code_phase_samples as in the block
+ *   current_prn_length_samples    the new block length
+ *   state                         0 standby / 1 pull-in pending / 2 tracking
+ *   valid                         1
+ *   integrating, extend_count     0
+ * A second deviation: a start is the start of a fresh block object.  The reference's start_tracking keeps the C/N0 window's fill, the
+ * last C/N0 and the last lock test of the object's previous run; here every start clears them (C/N0 0, lock test 1 until the first
+ * estimate), whatever the slot tracked before. */
+gc_status gc_trk_loop_start_glonass(gc_trk_loop* l, int ch, const gc_glonass_loop_conf* conf);
+/* The pull-in alignment that a start with `conf` performs before its first period (glonass_l1_ca_dll_pll_tracking_cc.cc:570-590),
+ * computed on the host by the statements the kernel runs; needs no device.  Any output pointer may be NULL: the samples skipped,
+ * the block's d_sample_counter behind them (the Tracking_sample_counter of the item the block writes there) and its
+ * d_acc_carrier_phase_rad.  The loop fields of `conf` (bandwidths, C/N0 settings, vector_length) are not read. */
+gc_status gc_glonass_loop_pull_in(const gc_glonass_loop_conf* conf, int32_t* samples_offset, uint64_t* sample_counter, double* acc_carrier_phase_rad);
+
 /* ------------------------------------------------------------------------ */
 /* PRN replica generators (host side, set-up path).  Same outputs as the      */
 /* reference's generators; dest buffers are caller-owned host memory.         */
