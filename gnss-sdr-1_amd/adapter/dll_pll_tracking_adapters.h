@@ -15,6 +15,8 @@
 
 #include "hip_dll_pll_veml_tracking.h"
 #include "hip_dll_pll_veml_tracking_dev.h"
+#include "tracking_adapter_base.h"
+#include "tracking_signals.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -22,66 +24,18 @@
 #include <string>
 #include <type_traits>
 
-namespace gnsscorr
-{
-enum class TrkSignal
-{
-    GPS_L1_CA,
-    GALILEO_E1,
-    BEIDOU_B1I,
-    GPS_L2_M,
-    GPS_L5,
-    GALILEO_E5A,
-    BEIDOU_B3I
-};
-
-//! what differs between the reference's adapters: signal constants, default loop settings, extension / pilot rules
-struct TrkSignalTraits
-{
-    const char* implementation;
-    char system;
-    const char* signal;
-    double code_rate_hz, code_length_chips;
-    float pll_bw_hz, dll_bw_hz, pll_bw_narrow_hz, dll_bw_narrow_hz;
-    float early_late_space_chips, early_late_space_narrow_chips;
-    bool veml;
-    int cn0_min;
-    double carrier_lock_th;
-    bool has_pilot;
-    int max_extension_data;  //!< longest integration (symbols) on the data component; 0: only with the pilot
-};
-
-inline const TrkSignalTraits& trk_traits(TrkSignal s)
-{
-    static const TrkSignalTraits t[] = {
-        {"GPS_L1_CA_DLL_PLL_Tracking_HIP", 'G', "1C", 1.023e6, 1023.0, 50.0f, 2.0f, 20.0f, 2.0f, 0.5f, 0.5f, false, 30, 0.80, false, 20},
-        {"Galileo_E1_DLL_PLL_VEML_Tracking_HIP", 'E', "1B", 1.023e6, 4092.0, 5.0f, 0.5f, 2.0f, 0.25f, 0.15f, 0.15f, true, 25, 0.85, true, 0},
-        {"BEIDOU_B1I_DLL_PLL_Tracking_HIP", 'C', "B1", 2.046e6, 2046.0, 50.0f, 2.0f, 20.0f, 2.0f, 0.5f, 0.5f, false, 25, 0.85, false, 20},
-        // gps_l2_m_dll_pll_tracking.cc:47-170: one 20 ms code per symbol, extension forced to 1
-        {"GPS_L2_M_DLL_PLL_Tracking_HIP", 'G', "2S", 0.5115e6, 10230.0, 2.0f, 0.75f, 2.0f, 0.75f, 0.5f, 0.5f, false, 25, 0.85, false, 1},
-        // gps_l5_dll_pll_tracking.cc:47-200: data component L5I (NH10) or pilot L5Q (NH20)
-        {"GPS_L5_DLL_PLL_Tracking_HIP", 'G', "L5", 10.23e6, 10230.0, 50.0f, 2.0f, 2.0f, 0.25f, 0.5f, 0.15f, false, 25, 0.75, true, 10},
-        // galileo_e5a_dll_pll_tracking.cc:47-200: data component E5a-I (CS20) or pilot E5a-Q (CS100 per PRN)
-        {"Galileo_E5a_DLL_PLL_Tracking_HIP", 'E', "5X", 10.23e6, 10230.0, 20.0f, 20.0f, 5.0f, 2.0f, 0.5f, 0.15f, false, 25, 0.85, true, 20},
-        // beidou_b3i_dll_pll_tracking.cc:47-190
-        {"BEIDOU_B3I_DLL_PLL_Tracking_HIP", 'C', "B3", 10.23e6, 10230.0, 50.0f, 2.0f, 20.0f, 2.0f, 0.5f, 0.5f, false, 25, 0.85, false, 20}};
-    return t[static_cast<int>(s)];
-}
-}  // namespace gnsscorr
-
 //! Block: hip_dll_pll_veml_tracking (one level-1 correlator call per code period, host loop maths) or
 //! hip_dll_pll_veml_tracking_dev (every complete code period of a work() call in one launch of the device loop)
 template <gnsscorr::TrkSignal SIG, class Block = hip_dll_pll_veml_tracking>
-class DllPllTrackingHip : public TrackingInterface
+class DllPllTrackingHip : public TrackingAdapterBase<Block>
 {
 public:
     DllPllTrackingHip(ConfigurationInterface* configuration, const std::string& role, unsigned int in_streams, unsigned int out_streams)
-        : role_(role), in_streams_(in_streams), out_streams_(out_streams)
+        : TrackingAdapterBase<Block>(role, in_streams, out_streams)
     {
-        const gnsscorr::TrkSignalTraits& t = gnsscorr::trk_traits(SIG);
+        const gnsscorr::TrkSignalInfo& t = gnsscorr::trk_signal(SIG);
         Dll_Pll_Conf trk_param = Dll_Pll_Conf();
-        int fs_in_deprecated = configuration->property("GNSS-SDR.internal_fs_hz", 2048000);
-        int fs_in = configuration->property("GNSS-SDR.internal_fs_sps", fs_in_deprecated);
+        const int fs_in = this->read_fs(configuration);
         trk_param.fs_in = fs_in;
         trk_param.high_dyn = configuration->property(role + ".high_dyn", false);
         trk_param.dump = configuration->property(role + ".dump", false);
@@ -124,7 +78,7 @@ public:
                 trk_param.very_early_late_space_chips = 0.0;
                 trk_param.very_early_late_space_narrow_chips = 0.0;
             }
-        trk_param.vector_length = std::round(static_cast<double>(fs_in) / (t.code_rate_hz / t.code_length_chips));
+        trk_param.vector_length = std::round(static_cast<double>(fs_in) / (t.code_chip_rate_hz / static_cast<double>(t.code_length_chips)));
         trk_param.system = t.system;
         std::memcpy(trk_param.signal, t.signal, 3);
         trk_param.track_pilot = track_pilot;
@@ -133,37 +87,18 @@ public:
         trk_param.max_lock_fail = configuration->property(role + ".max_lock_fail", 50);
         trk_param.carrier_lock_th = configuration->property(role + ".carrier_lock_th", t.carrier_lock_th);
         conf_ = trk_param;
-        tracking_ = std::make_shared<Block>(trk_param);
+        this->tracking_ = std::make_shared<Block>(trk_param);
     }
 
-    std::string role() override { return role_; }
     std::string implementation() override
     {
-        const std::string name = gnsscorr::trk_traits(SIG).implementation;
+        const std::string name = gnsscorr::trk_signal(SIG).implementation;
         return std::is_same<Block, hip_dll_pll_veml_tracking>::value ? name : name + "_DEV";
     }
-    size_t item_size() override { return sizeof(gr_complex); }
-
-    void start_tracking() override { tracking_->start_tracking(); }
-    void stop_tracking() override { tracking_->stop_tracking(); }
-    void set_channel(unsigned int channel) override
-    {
-        channel_ = channel;
-        tracking_->set_channel(channel);
-    }
-    void set_gnss_synchro(Gnss_Synchro* p_gnss_synchro) override { tracking_->set_gnss_synchro(p_gnss_synchro); }
-
-    //! the block (get_left_block()/get_right_block() in the reference)
-    std::shared_ptr<Block> block() { return tracking_; }
     const Dll_Pll_Conf& conf() const { return conf_; }
 
 private:
-    std::shared_ptr<Block> tracking_;
     Dll_Pll_Conf conf_;
-    std::string role_;
-    unsigned int channel_ = 0;
-    unsigned int in_streams_;
-    unsigned int out_streams_;
 };
 
 using GpsL1CaDllPllTrackingHip = DllPllTrackingHip<gnsscorr::TrkSignal::GPS_L1_CA>;

@@ -28,6 +28,7 @@
 #include "hip_multicorrelator_real_codes.h"
 #include "mat5_writer.h"
 #include "tracking_loop_maths.h"
+#include "tracking_signals.h"
 #include <cmath>
 #include <cstring>
 #include <deque>
@@ -43,28 +44,29 @@ public:
     explicit hip_dll_pll_veml_tracking(const Dll_Pll_Conf& conf_) : trk_parameters(conf_)
     {
         signal_type = std::string(trk_parameters.signal);
+        // the signal's constants, pilot and I/Q rules (:113-336): its row of the signal table
+        const gnsscorr::TrkSignalInfo* sig = gnsscorr::trk_signal_find(trk_parameters.system, signal_type);
+        if (sig != nullptr)
+            {
+                d_signal_carrier_freq = sig->carrier_freq_hz;
+                d_code_period = sig->code_period_s;
+                d_code_chip_rate = sig->code_chip_rate_hz;
+                d_code_length_chips = sig->code_length_chips;
+                d_code_samples_per_chip = sig->code_samples_per_chip;
+                d_correlation_length_ms = sig->correlation_length_ms;
+                d_veml = sig->veml;
+                if (!sig->has_pilot) trk_parameters.track_pilot = false;  // no pilot component, no secondary code
+                interchange_iq = trk_parameters.track_pilot && sig->interchange_iq_with_pilot;
+            }
+        // symbol synchronisation: symbols per bit, secondary code, telemetry preamble
         d_symbols_per_bit = 1;
         if (trk_parameters.system == 'G' && signal_type == "1C")
             {
-                d_signal_carrier_freq = 1575.42e6;  // GPS_L1_FREQ_HZ
-                d_code_period = 0.001;
-                d_code_chip_rate = 1.023e6;
                 d_symbols_per_bit = 20;  // GPS_CA_TELEMETRY_SYMBOLS_PER_BIT
-                d_correlation_length_ms = 1;
-                d_code_samples_per_chip = 1;
-                d_code_length_chips = 1023;
-                trk_parameters.track_pilot = false;  // no pilot component, no secondary code
                 set_preamble({1, 0, 0, 0, 1, 0, 1, 1}, 20);  // GPS_PREAMBLE, one entry per 1 ms symbol (:129-150)
             }
         else if (trk_parameters.system == 'E' && signal_type == "1B")
             {
-                d_signal_carrier_freq = 1575.42e6;  // Galileo_E1_FREQ_HZ
-                d_code_period = 0.004;
-                d_code_chip_rate = 1.023e6;
-                d_code_length_chips = 4092;
-                d_correlation_length_ms = 4;
-                d_code_samples_per_chip = 2;  // sinBOC(1,1) replica, 2 samples per chip
-                d_veml = true;
                 d_symbols_per_bit = 1;
                 if (trk_parameters.track_pilot)
                     {
@@ -74,68 +76,31 @@ public:
             }
         else if (trk_parameters.system == 'C' && signal_type == "B1")
             {
-                d_signal_carrier_freq = 1.561098e9;  // BEIDOU_B1I_FREQ_HZ
-                d_code_period = 0.001;
-                d_code_chip_rate = 2.046e6;
-                d_code_length_chips = 2046;
-                d_correlation_length_ms = 1;
-                d_code_samples_per_chip = 1;
                 d_symbols_per_bit = 20;  // BEIDOU_B1I_TELEMETRY_SYMBOLS_PER_BIT
                 d_secondary = true;
                 d_secondary_code_string = "00000100110101001110";  // BEIDOU_B1I_SECONDARY_CODE_STR (NH20)
-                trk_parameters.track_pilot = false;
             }
         else if (trk_parameters.system == 'G' && signal_type == "2S")
-            {
-                d_signal_carrier_freq = 1.22760e9;  // GPS_L2_FREQ_HZ
-                d_code_period = 0.02;               // GPS_L2_M_PERIOD
-                d_code_chip_rate = 0.5115e6;
-                d_code_length_chips = 10230;
-                d_symbols_per_bit = 1;  // GPS_L2_SAMPLES_PER_SYMBOL
-                d_correlation_length_ms = 20;
-                d_code_samples_per_chip = 1;
-                trk_parameters.track_pilot = false;  // no pilot component, no secondary code
-            }
+            d_symbols_per_bit = 1;  // GPS_L2_SAMPLES_PER_SYMBOL
         else if (trk_parameters.system == 'G' && signal_type == "L5")
             {
-                d_signal_carrier_freq = 1.17645e9;  // GPS_L5_FREQ_HZ
-                d_code_period = 0.001;
-                d_code_chip_rate = 10.23e6;
                 d_symbols_per_bit = 10;  // GPS_L5_SAMPLES_PER_SYMBOL
-                d_correlation_length_ms = 1;
-                d_code_samples_per_chip = 1;
-                d_code_length_chips = 10230;
                 d_secondary = true;
                 // pilot: Q5 with NH20, in quadrature with the data component; data: I5 with NH10
                 d_secondary_code_string = trk_parameters.track_pilot ? "00000100110101001110" : "0000110101";
-                interchange_iq = trk_parameters.track_pilot;
             }
         else if (trk_parameters.system == 'E' && signal_type == "5X")
             {
-                d_signal_carrier_freq = 1.17645e9;  // GALILEO_E5A_FREQ_HZ
-                d_code_period = 0.001;
-                d_code_chip_rate = 1.023e7;
                 d_symbols_per_bit = 20;
-                d_correlation_length_ms = 1;
-                d_code_samples_per_chip = 1;
-                d_code_length_chips = 10230;
                 // pilot: E5a-Q with the 100-symbol secondary code of the PRN (set in start_tracking); on the data component the
                 // secondary code is left to the telemetry decoder
                 d_secondary = trk_parameters.track_pilot;
-                interchange_iq = trk_parameters.track_pilot;
             }
         else if (trk_parameters.system == 'C' && signal_type == "B3")
             {
-                d_signal_carrier_freq = 1.268520e9;  // BEIDOU_B3I_FREQ_HZ
-                d_code_period = 0.001;
-                d_code_chip_rate = 10.23e6;
-                d_code_length_chips = 10230;
                 d_symbols_per_bit = 20;
-                d_correlation_length_ms = 1;
-                d_code_samples_per_chip = 1;
                 d_secondary = true;
                 d_secondary_code_string = "00000100110101001110";  // BEIDOU_B3I_SECONDARY_CODE_STR (NH20)
-                trk_parameters.track_pilot = false;
             }
         if (trk_parameters.extend_correlation_symbols > 1)
             d_enable_extended_integration = true;
@@ -255,82 +220,28 @@ public:
         d_carrier_loop_filter.initialize(static_cast<float>(d_acq_carrier_doppler_hz));
         d_code_loop_filter.initialize();
         const uint32_t prn = d_acquisition_gnss_synchro->PRN;
-        if (trk_parameters.system == 'G' && signal_type == "2S")
-            gc_gps_l2c_m_code_gen_float(d_tracking_code.data(), prn);
-        else if (trk_parameters.system == 'G' && signal_type == "L5")
+        // the replica the loop runs on, and the data component's when it runs on the pilot (:566-705)
+        gnsscorr::trk_generate_replicas(trk_parameters.system, signal_type.c_str(), prn, trk_parameters.track_pilot, d_tracking_code.data(),
+            trk_parameters.track_pilot ? d_data_code.data() : nullptr);
+        if (trk_parameters.track_pilot)
             {
-                if (trk_parameters.track_pilot)
-                    {
-                        gc_gps_l5q_code_gen_float(d_tracking_code.data(), prn);
-                        gc_gps_l5i_code_gen_float(d_data_code.data(), prn);
-                        d_Prompt_Data = gr_complex(0.0, 0.0);
-                        correlator_data_cpu.set_local_code_and_taps(d_code_length_chips, d_data_code.data(), &d_local_code_shift_chips[1]);
-                    }
-                else
-                    gc_gps_l5i_code_gen_float(d_tracking_code.data(), prn);
-            }
-        else if (trk_parameters.system == 'E' && signal_type == "5X")
-            {
-                // the complex primary code holds E5a-I in the real and E5a-Q in the imaginary part (:606-626)
-                std::vector<float> aux(2 * d_code_length_chips);
-                gc_galileo_e5_a_code_gen_complex_primary(aux.data(), static_cast<int32_t>(prn), "5X");
-                if (trk_parameters.track_pilot)
+                if (trk_parameters.system == 'E' && signal_type == "5X")
                     {
                         char sec[128];
                         int32_t len = 0;
                         if (gc_secondary_code("5Q", prn, sec, sizeof sec, &len) == GC_OK) d_secondary_code_string.assign(sec, len);
-                        for (uint32_t i = 0; i < d_code_length_chips; i++)
-                            {
-                                d_tracking_code[i] = aux[2 * i + 1];
-                                d_data_code[i] = aux[2 * i];
-                            }
-                        d_Prompt_Data = gr_complex(0.0, 0.0);
-                        correlator_data_cpu.set_local_code_and_taps(d_code_length_chips, d_data_code.data(), &d_local_code_shift_chips[1]);
                     }
-                else
-                    for (uint32_t i = 0; i < d_code_length_chips; i++) d_tracking_code[i] = aux[2 * i];
+                d_Prompt_Data = gr_complex(0.0, 0.0);
+                // the data correlator's only tap IS the prompt shift of the main correlator (pointer, not copy)
+                correlator_data_cpu.set_local_code_and_taps(d_code_samples_per_chip * d_code_length_chips, d_data_code.data(), &d_local_code_shift_chips[d_veml ? 2 : 1]);
             }
-        else if (trk_parameters.system == 'C' && signal_type == "B3")
+        if (trk_parameters.system == 'C' && prn > 0 && prn < 6)
             {
-                gc_beidou_b3i_code_gen_float(d_tracking_code.data(), static_cast<int32_t>(prn), 0);
-                if (prn > 0 and prn < 6)
-                    {
-                        // GEO satellites broadcast D2 (:672-705)
-                        d_symbols_per_bit = 2;
-                        d_secondary = false;
-                        d_secondary_code_string.clear();
-                        set_preamble({1, 1, 1, 0, 0, 0, 1, 0, 0, 1, 0}, 2);
-                    }
-            }
-        else if (trk_parameters.system == 'G')
-            gc_gps_l1_ca_code_gen_float(d_tracking_code.data(), static_cast<int32_t>(d_acquisition_gnss_synchro->PRN), 0);
-        else if (trk_parameters.system == 'E')
-            {
-                char sig[3] = "1B";
-                if (trk_parameters.track_pilot)
-                    {
-                        char pilot_signal[3] = "1C";
-                        gc_galileo_e1_code_gen_sinboc11_float(d_tracking_code.data(), pilot_signal, d_acquisition_gnss_synchro->PRN);
-                        gc_galileo_e1_code_gen_sinboc11_float(d_data_code.data(), sig, d_acquisition_gnss_synchro->PRN);
-                        d_Prompt_Data = gr_complex(0.0, 0.0);
-                        // the data correlator's only tap IS the prompt shift of the main correlator (pointer, not copy)
-                        correlator_data_cpu.set_local_code_and_taps(d_code_samples_per_chip * d_code_length_chips, d_data_code.data(),
-                            &d_local_code_shift_chips[2]);
-                    }
-                else
-                    gc_galileo_e1_code_gen_sinboc11_float(d_tracking_code.data(), sig, d_acquisition_gnss_synchro->PRN);
-            }
-        else
-            {
-                gc_beidou_b1i_code_gen_float(d_tracking_code.data(), static_cast<int32_t>(d_acquisition_gnss_synchro->PRN), 0);
-                if (d_acquisition_gnss_synchro->PRN > 0 and d_acquisition_gnss_synchro->PRN < 6)
-                    {
-                        // GEO satellites broadcast D2: 2 symbols per bit, no NH code, 11-bit preamble (:631-665)
-                        d_symbols_per_bit = 2;
-                        d_secondary = false;
-                        d_secondary_code_string.clear();
-                        set_preamble({1, 1, 1, 0, 0, 0, 1, 0, 0, 1, 0}, 2);
-                    }
+                // GEO satellites broadcast D2: 2 symbols per bit, no NH code, 11-bit preamble (:631-665, :672-705)
+                d_symbols_per_bit = 2;
+                d_secondary = false;
+                d_secondary_code_string.clear();
+                set_preamble({1, 1, 1, 0, 0, 0, 1, 0, 0, 1, 0}, 2);
             }
         multicorrelator_cpu.set_local_code_and_taps(d_code_samples_per_chip * d_code_length_chips, d_tracking_code.data(), d_local_code_shift_chips.data());
         std::fill(d_correlator_outs.begin(), d_correlator_outs.end(), gr_complex(0.0, 0.0));

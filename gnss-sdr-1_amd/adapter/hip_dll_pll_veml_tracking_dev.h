@@ -2,7 +2,8 @@
  * \file hip_dll_pll_veml_tracking_dev.h
  * \brief The dll_pll_veml_tracking block on the DEVICE loop (gc_trk_loop): one work() call pushes the new input items into an
  * HBM ring and runs every code period that is complete in it -- correlations, synchronisation, extended integration and loop
- * maths in one launch -- then hands out one Gnss_Synchro per valid period.  GNU Radio's general_work may produce several
+ * maths in one launch -- then hands out one Gnss_Synchro per valid period (hip_device_loop_block, tracking_block_base.h, under the
+ * veml policy; this header holds what a start and a record mean for the veml loop).  GNU Radio's general_work may produce several
  * output items per call (noutput_items), so the block keeps the reference interface while the per-millisecond host round trip
  * of the CPU block (and of hip_dll_pll_veml_tracking, which calls the level-1 correlator once per period) disappears.
  *
@@ -14,73 +15,27 @@
 #define GNSSCORR_HIP_DLL_PLL_VEML_TRACKING_DEV_H_
 
 #include "gnss_sdr_types.h"
+#include "tracking_block_base.h"
 #include "tracking_loop_maths.h"
+#include "tracking_signals.h"
 #include <algorithm>
-#include <cmath>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <vector>
 
 namespace gnsscorr
 {
-//! per-signal constants of the block's constructor (dll_pll_veml_tracking.cc:113-336)
-struct TrkSignalConstants
-{
-    double carrier_freq_hz, code_period_s, code_chip_rate_hz;
-    uint32_t code_length_chips, code_samples_per_chip;
-    bool veml, has_pilot, interchange_iq_with_pilot;
-    int32_t correlation_length_ms;
-};
-inline bool trk_signal_constants(char system, const std::string& signal, TrkSignalConstants* c)
-{
-    if (system == 'G' && signal == "1C") *c = {1575.42e6, 0.001, 1.023e6, 1023, 1, false, false, false, 1};
-    else if (system == 'G' && signal == "2S") *c = {1.22760e9, 0.02, 0.5115e6, 10230, 1, false, false, false, 20};
-    else if (system == 'G' && signal == "L5") *c = {1.17645e9, 0.001, 10.23e6, 10230, 1, false, true, true, 1};
-    else if (system == 'E' && signal == "1B") *c = {1575.42e6, 0.004, 1.023e6, 4092, 2, true, true, false, 4};
-    else if (system == 'E' && signal == "5X") *c = {1.17645e9, 0.001, 1.023e7, 10230, 1, false, true, true, 1};
-    else if (system == 'C' && signal == "B1") *c = {1.561098e9, 0.001, 2.046e6, 2046, 1, false, false, false, 1};
-    else if (system == 'C' && signal == "B3") *c = {1.268520e9, 0.001, 10.23e6, 10230, 1, false, false, false, 1};
-    else return false;
-    return true;
-}
-
 /*! start_tracking (:549-747) of one channel of a device loop: replicas, synchronisation data, loop start.  `sample_counter` is the
  *  stream position the channel starts consuming at (the block's d_sample_counter). */
-inline gc_status loop_start_channel(gc_trk_loop* loop, int ch, const Dll_Pll_Conf& trk_parameters, const TrkSignalConstants& sig, const Gnss_Synchro& acq,
+inline gc_status loop_start_channel(gc_trk_loop* loop, int ch, const Dll_Pll_Conf& trk_parameters, const TrkSignalInfo& sig, const Gnss_Synchro& acq,
     uint64_t sample_counter, float bit_sync_min_time_s = 10.0f)
 {
     const uint32_t prn = acq.PRN;
-    const std::string signal(trk_parameters.signal);
     const int code_len = static_cast<int>(sig.code_length_chips * sig.code_samples_per_chip);
     std::vector<float> code(code_len), data_code(code_len);
     const bool pilot = trk_parameters.track_pilot && sig.has_pilot;
-    gc_status st = GC_OK;
     // the replica the loop runs on, and the data component's when the loop runs on the pilot (:566-705)
-    if (trk_parameters.system == 'G' && signal == "1C") st = gc_gps_l1_ca_code_gen_float(code.data(), static_cast<int32_t>(prn), 0);
-    else if (trk_parameters.system == 'G' && signal == "2S") st = gc_gps_l2c_m_code_gen_float(code.data(), prn);
-    else if (trk_parameters.system == 'G' && signal == "L5")
-        {
-            st = pilot ? gc_gps_l5q_code_gen_float(code.data(), prn) : gc_gps_l5i_code_gen_float(code.data(), prn);
-            if (pilot && st == GC_OK) st = gc_gps_l5i_code_gen_float(data_code.data(), prn);
-        }
-    else if (trk_parameters.system == 'E' && signal == "1B")
-        {
-            st = gc_galileo_e1_code_gen_sinboc11_float(code.data(), pilot ? "1C" : "1B", prn);
-            if (pilot && st == GC_OK) st = gc_galileo_e1_code_gen_sinboc11_float(data_code.data(), "1B", prn);
-        }
-    else if (trk_parameters.system == 'E' && signal == "5X")
-        {
-            std::vector<float> aux(2 * code_len);
-            st = gc_galileo_e5_a_code_gen_complex_primary(aux.data(), static_cast<int32_t>(prn), "5X");
-            for (int i = 0; i < code_len; i++)
-                {
-                    code[i] = pilot ? aux[2 * i + 1] : aux[2 * i];
-                    data_code[i] = aux[2 * i];
-                }
-        }
-    else if (trk_parameters.system == 'C' && signal == "B1") st = gc_beidou_b1i_code_gen_float(code.data(), static_cast<int32_t>(prn), 0);
-    else st = gc_beidou_b3i_code_gen_float(code.data(), static_cast<int32_t>(prn), 0);
+    gc_status st = trk_generate_replicas(sig.system, sig.signal, prn, pilot, code.data(), data_code.data());
     if (st != GC_OK) return st;
     gc_loop_sync_conf y;
     st = gc_loop_sync_for_signal(trk_parameters.system, trk_parameters.signal, prn, pilot ? 1 : 0, std::max(1, trk_parameters.extend_correlation_symbols), &y);
@@ -125,7 +80,7 @@ inline gc_status loop_start_channel(gc_trk_loop* loop, int ch, const Dll_Pll_Con
 }
 
 //! what a valid period hands to the telemetry decoder (:1693-1725, :1898-1906), from the device loop's record
-inline Gnss_Synchro synchro_from_record(const gc_loop_record& r, const Gnss_Synchro& acq, const TrkSignalConstants& sig, bool interchange_iq, double fs_in)
+inline Gnss_Synchro synchro_from_record(const gc_loop_record& r, const Gnss_Synchro& acq, const TrkSignalInfo& sig, bool interchange_iq, double fs_in)
 {
     Gnss_Synchro s = acq;
     s.Prompt_I = static_cast<double>(interchange_iq ? r.prompt_data[1] : r.prompt_data[0]);
@@ -142,169 +97,45 @@ inline Gnss_Synchro synchro_from_record(const gc_loop_record& r, const Gnss_Sync
 }
 }  // namespace gnsscorr
 
-class hip_dll_pll_veml_tracking_dev
+//! one channel with a ring of its own: hip_device_loop_block under the veml policy
+class hip_dll_pll_veml_tracking_dev : public hip_device_loop_block
 {
 public:
     /*! ring_periods: code periods of input the HBM ring holds (a work() call may bring at most that many) */
-    explicit hip_dll_pll_veml_tracking_dev(const Dll_Pll_Conf& conf_, int device = 0, int ring_periods = 64) : trk_parameters(conf_), d_ring_periods(ring_periods)
+    explicit hip_dll_pll_veml_tracking_dev(const Dll_Pll_Conf& conf_, int device = 0, int ring_periods = 64)
+        : hip_dll_pll_veml_tracking_dev(conf_, gnsscorr::trk_signal_find(conf_.system, std::string(conf_.signal)), device, ring_periods)
     {
-        d_ok = gnsscorr::trk_signal_constants(trk_parameters.system, std::string(trk_parameters.signal), &d_sig);
-        if (!d_ok)
-            {
-                d_status = GC_ERR_INVALID;
-                return;
-            }
-        if (!d_sig.has_pilot) trk_parameters.track_pilot = false;
-        if (trk_parameters.extend_correlation_symbols < 1) trk_parameters.extend_correlation_symbols = 1;
-        const int code_len = static_cast<int>(d_sig.code_length_chips * d_sig.code_samples_per_chip);
-        d_status = gc_ctx_create(device, &d_ctx);
-        if (d_status == GC_OK)
-            d_status = gc_stream_create(d_ctx, GC_IQ_F32, static_cast<uint64_t>(trk_parameters.vector_length) * ring_periods, 2 * trk_parameters.vector_length, &d_ring);
-        if (d_status == GC_OK) d_status = gc_trk_loop_create(d_ctx, 1, code_len, &d_loop);
-        if (d_status == GC_OK) d_status = gc_trk_loop_set_input_stream(d_loop, 0, d_ring);
-        d_records.resize(ring_periods + 2);
     }
 
-    ~hip_dll_pll_veml_tracking_dev()
-    {
-        if (d_loop) gc_trk_loop_destroy(d_loop);
-        if (d_ring) gc_stream_destroy(d_ring);
-        if (d_ctx) gc_ctx_destroy(d_ctx);
-    }
-    hip_dll_pll_veml_tracking_dev(const hip_dll_pll_veml_tracking_dev&) = delete;
-    hip_dll_pll_veml_tracking_dev& operator=(const hip_dll_pll_veml_tracking_dev&) = delete;
-
-    void set_channel(uint32_t channel) { d_channel = channel; }
-    void set_gnss_synchro(Gnss_Synchro* p_gnss_synchro) { d_acquisition_gnss_synchro = p_gnss_synchro; }
     //! the reference waits 10 s before looking for the telemetry preamble (:1648); tests shorten it
     void set_bit_sync_min_time_s(float t) { d_bit_sync_min_time_s = t; }
 
+protected:
     //! start_tracking (:549-747): replicas, synchronisation data and the loop start on the device
-    void start_tracking()
+    gc_status start_channel(uint64_t sample_counter, Gnss_Synchro*) override
     {
-        std::lock_guard<std::mutex> l(d_setlock);
-        if (d_status != GC_OK || !d_ok) return;
-        const bool pilot = trk_parameters.track_pilot;
-        d_status = gnsscorr::loop_start_channel(d_loop, 0, trk_parameters, d_sig, *d_acquisition_gnss_synchro, d_sample_counter, d_bit_sync_min_time_s);
-        d_interchange_iq = pilot && d_sig.interchange_iq_with_pilot;
-        d_state = d_status == GC_OK ? 1 : 0;
+        return gnsscorr::loop_start_channel(d_loop, 0, trk_parameters, *d_sig, *d_acquisition_gnss_synchro, sample_counter, d_bit_sync_min_time_s);
     }
-
-    void stop_tracking()
+    Gnss_Synchro to_synchro(const gc_loop_record& r) const override
     {
-        std::lock_guard<std::mutex> l(d_setlock);
-        d_state = 0;
+        return gnsscorr::synchro_from_record(r, *d_acquisition_gnss_synchro, *d_sig, trk_parameters.track_pilot && d_sig->interchange_iq_with_pilot, trk_parameters.fs_in);
     }
-
-    //! forecast: like the reference block, at least two code periods
-    int required_input_items() const { return static_cast<int>(trk_parameters.vector_length) * 2; }
-
-    /*! general_work: `in` points at the first unconsumed item, ninput_items are available, at most max_out Gnss_Synchro fit in
-     *  `out`.  Returns the items consumed; *produced = Gnss_Synchro written. */
-    int work(const gr_complex* in, int ninput_items, Gnss_Synchro* out, int max_out, int* produced)
-    {
-        std::lock_guard<std::mutex> l(d_setlock);
-        *produced = 0;
-        if (d_state == 0 || d_status != GC_OK)
-            {
-                // standby: the items pass by (they are not needed in HBM), the counters move on
-                d_sample_counter += static_cast<uint64_t>(ninput_items);
-                d_pushed = std::max(d_pushed, d_sample_counter);
-                return ninput_items;
-            }
-        // 1. the items that are not in the ring yet (the scheduler shows again what was not consumed last time)
-        const uint64_t have = d_pushed - d_sample_counter;  // already pushed, not yet consumed
-        uint64_t fresh = static_cast<uint64_t>(ninput_items) > have ? static_cast<uint64_t>(ninput_items) - have : 0;
-        const uint64_t room = static_cast<uint64_t>(trk_parameters.vector_length) * d_ring_periods - have;
-        fresh = std::min(fresh, room);
-        if (fresh > 0)
-            {
-                if (d_ring_head != d_pushed)
-                    {
-                        // items went by in standby: the ring's numbering continues at the stream position (zeros fill the gap)
-                        d_status = skip_to(d_pushed);
-                        if (d_status != GC_OK) return 0;
-                    }
-                d_status = gc_stream_push(d_ring, in + have, fresh, nullptr);
-                if (d_status != GC_OK) return 0;
-                d_pushed += fresh;
-                d_ring_head = d_pushed;
-            }
-        // 2. every complete code period in one launch
-        const int n_periods = std::min<int>(std::min<int>(max_out, static_cast<int>(d_records.size())),
-            static_cast<int>((d_pushed - d_sample_counter) / trk_parameters.vector_length) + 1);
-        if (n_periods <= 0) return 0;
-        d_status = gc_trk_loop_run(d_loop, n_periods, d_records.data());
-        if (d_status != GC_OK) return 0;
-        // 3. records -> Gnss_Synchro (:1693-1725, :1898-1906); the launch stops at the first period that is not complete
-        uint64_t position = d_sample_counter;
-        for (int k = 0; k < n_periods; k++)
-            {
-                const gc_loop_record& r = d_records[k];
-                if (r.sample_counter == position && r.valid == 0 && r.state >= 2) break;  // nothing was correlated: out of input
-                position = r.sample_counter;
-                d_state = r.state;
-                d_last = r;
-                if (r.valid)
-                    {
-                        const Gnss_Synchro s = gnsscorr::synchro_from_record(r, *d_acquisition_gnss_synchro, d_sig, d_interchange_iq, trk_parameters.fs_in);
-                        out[(*produced)++] = s;
-                    }
-                if (r.state == 0)
-                    {
-                        d_events.push_back(3);  // loss of lock (:868)
-                        break;
-                    }
-            }
-        const int consumed = static_cast<int>(position - d_sample_counter);
-        d_sample_counter = position;
-        return consumed;
-    }
-
-    int32_t state() const { return d_state; }
-    double carrier_doppler_hz() const { return d_last.carrier_doppler_hz; }
-    double code_freq_chips() const { return d_last.code_freq_chips; }
-    double cn0_db_hz() const { return d_last.cn0_db_hz; }
-    double carrier_lock_test() const { return d_last.carrier_lock_test; }
-    uint64_t sample_counter() const { return d_sample_counter; }
-    const gc_loop_record& last_record() const { return d_last; }
-    const std::vector<int>& events() const { return d_events; }
-    gc_status last_status() const { return d_status; }
 
 private:
-    //! appends zeros until the ring's head is at absolute sample `index`
-    gc_status skip_to(uint64_t index)
+    //! sig == NULL (not a signal of the block): nothing is created, last_status() is GC_ERR_INVALID and start_tracking does nothing
+    hip_dll_pll_veml_tracking_dev(const Dll_Pll_Conf& conf_, const gnsscorr::TrkSignalInfo* sig, int device, int ring_periods)
+        : hip_device_loop_block(gnsscorr::kVemlLoopPolicy, conf_.vector_length, sig ? static_cast<int>(sig->code_length_chips * sig->code_samples_per_chip) : 0, device, ring_periods,
+              sig ? GC_OK : GC_ERR_INVALID),
+          trk_parameters(conf_), d_sig(sig)
     {
-        std::vector<gr_complex> zeros(std::min<uint64_t>(index - d_ring_head, 1u << 16));
-        while (d_ring_head < index)
-            {
-                const uint64_t n = std::min<uint64_t>(index - d_ring_head, zeros.size());
-                gc_status s = gc_stream_push(d_ring, zeros.data(), n, nullptr);
-                if (s != GC_OK) return s;
-                d_ring_head += n;
-            }
-        return GC_OK;
+        if (d_sig == nullptr) return;
+        if (!d_sig->has_pilot) trk_parameters.track_pilot = false;
+        if (trk_parameters.extend_correlation_symbols < 1) trk_parameters.extend_correlation_symbols = 1;
     }
 
     Dll_Pll_Conf trk_parameters;
-    gnsscorr::TrkSignalConstants d_sig{};
-    bool d_ok = false, d_interchange_iq = false;
-    int d_ring_periods;
-    std::mutex d_setlock;
-    gc_ctx* d_ctx = nullptr;
-    gc_stream* d_ring = nullptr;
-    gc_trk_loop* d_loop = nullptr;
-    gc_status d_status = GC_OK;
-    Gnss_Synchro* d_acquisition_gnss_synchro = nullptr;
-    uint32_t d_channel = 0;
-    int32_t d_state = 0;
+    const gnsscorr::TrkSignalInfo* d_sig;
     float d_bit_sync_min_time_s = 10.0f;
-    uint64_t d_sample_counter = 0;  // absolute index of the first unconsumed item (the block's d_sample_counter)
-    uint64_t d_pushed = 0;          // absolute index one past the last item seen
-    uint64_t d_ring_head = 0;       // absolute index one past the last item in the ring
-    std::vector<gc_loop_record> d_records;
-    gc_loop_record d_last{};
-    std::vector<int> d_events;
 };
 
 #endif  // GNSSCORR_HIP_DLL_PLL_VEML_TRACKING_DEV_H_

@@ -20,11 +20,14 @@
 
 #include "gnss_sdr_types.h"
 #include "hip_multicorrelator.h"
+#include "tracking_adapter_base.h"
 #include "tracking_loop_maths.h"
+#include "tracking_signals.h"
 #include <cmath>
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 //! Tracking_2nd_DLL_filter (src/algorithms/tracking/libs/tracking_2nd_DLL_filter.cc:40-96)
@@ -96,16 +99,6 @@ private:
 
 namespace gnsscorr
 {
-//! GLONASS_L1_L2_CA.h:84-97
-struct GlonassBand
-{
-    double freq_hz, dfreq_hz;
-    const char* implementation;
-};
-inline GlonassBand glonass_band(int band)
-{
-    return band == 2 ? GlonassBand{1.246e9, 0.4375e6, "GLONASS_L2_CA_DLL_PLL_Tracking_HIP"} : GlonassBand{1.602e9, 0.5625e6, "GLONASS_L1_CA_DLL_PLL_Tracking_HIP"};
-}
 //! GLONASS_PRN (GLONASS_L1_L2_CA.h:129-154): slot -> frequency channel of the constellation the reference was written against
 inline const std::map<uint32_t, int32_t>& glonass_default_channels()
 {
@@ -298,8 +291,8 @@ public:
 
 private:
     static constexpr double kTwoPi = 6.283185307179586;  // GLONASS_TWO_PI
-    static constexpr double kCodeRateHz = 0.511e6;       // GLONASS_L1_CA_CODE_RATE_HZ (L2 C/A: the same)
-    static constexpr double kCodeLengthChips = 511.0;
+    static constexpr double kCodeRateHz = gnsscorr::kGlonassCaCodeRateHz;
+    static constexpr double kCodeLengthChips = gnsscorr::kGlonassCaCodeLengthChips;
 
     gnsscorr::GlonassBand d_band;
     int64_t d_fs_in;
@@ -328,42 +321,37 @@ private:
     std::vector<int> d_events;
 };
 
-//! TrackingInterface adapter (glonass_l1_ca_dll_pll_tracking.cc:46-130; glonass_l2_ca_dll_pll_tracking.cc is the same with "2G")
-template <int BAND>
-class GlonassCaDllPllTrackingHip : public TrackingInterface
+/*! TrackingInterface adapter (glonass_l1_ca_dll_pll_tracking.cc:46-130; glonass_l2_ca_dll_pll_tracking.cc is the same with "2G").
+ *  Block: hip_glonass_ca_dll_pll_tracking (host loop) or hip_glonass_ca_dll_pll_tracking_dev (device loop, its own header) */
+template <int BAND, class Block>
+class GlonassCaDllPllTrackingAdapter : public TrackingAdapterBase<Block>
 {
 public:
-    GlonassCaDllPllTrackingHip(ConfigurationInterface* configuration, const std::string& role, unsigned int in_streams, unsigned int out_streams)
-        : role_(role), in_streams_(in_streams), out_streams_(out_streams)
+    GlonassCaDllPllTrackingAdapter(ConfigurationInterface* configuration, const std::string& role, unsigned int in_streams, unsigned int out_streams)
+        : TrackingAdapterBase<Block>(role, in_streams, out_streams)
     {
-        int fs_in_deprecated = configuration->property("GNSS-SDR.internal_fs_hz", 2048000);
-        const int fs_in = configuration->property("GNSS-SDR.internal_fs_sps", fs_in_deprecated);
+        const int fs_in = this->read_fs(configuration);
         const float pll_bw_hz = configuration->property(role + ".pll_bw_hz", 50.0f);
         const float dll_bw_hz = configuration->property(role + ".dll_bw_hz", 2.0f);
         const float early_late_space_chips = configuration->property(role + ".early_late_space_chips", 0.5f);
-        vector_length_ = std::round(fs_in / (0.511e6 / 511.0));
-        tracking_ = std::make_shared<hip_glonass_ca_dll_pll_tracking>(BAND, fs_in, vector_length_, pll_bw_hz, dll_bw_hz, early_late_space_chips,
-            configuration->property(role + ".cn0_samples", 20), configuration->property(role + ".cn0_min", 25), configuration->property(role + ".max_lock_fail", 50),
-            configuration->property(role + ".carrier_lock_th", 0.85));
+        vector_length_ = std::round(fs_in / (gnsscorr::kGlonassCaCodeRateHz / gnsscorr::kGlonassCaCodeLengthChips));
+        this->tracking_ = std::make_shared<Block>(BAND, fs_in, vector_length_, pll_bw_hz, dll_bw_hz, early_late_space_chips, configuration->property(role + ".cn0_samples", 20),
+            configuration->property(role + ".cn0_min", 25), configuration->property(role + ".max_lock_fail", 50), configuration->property(role + ".carrier_lock_th", 0.85));
     }
 
-    std::string role() override { return role_; }
-    std::string implementation() override { return gnsscorr::glonass_band(BAND).implementation; }
-    size_t item_size() override { return sizeof(gr_complex); }
-    void start_tracking() override { tracking_->start_tracking(); }
-    void stop_tracking() override { tracking_->stop_tracking(); }
-    void set_channel(unsigned int channel) override { tracking_->set_channel(channel); }
-    void set_gnss_synchro(Gnss_Synchro* p_gnss_synchro) override { tracking_->set_gnss_synchro(p_gnss_synchro); }
-    std::shared_ptr<hip_glonass_ca_dll_pll_tracking> block() { return tracking_; }
+    std::string implementation() override
+    {
+        const gnsscorr::GlonassBand band = gnsscorr::glonass_band(BAND);
+        return std::is_same<Block, hip_glonass_ca_dll_pll_tracking>::value ? band.implementation : band.implementation_dev;
+    }
     unsigned int vector_length() const { return vector_length_; }
 
 private:
-    std::shared_ptr<hip_glonass_ca_dll_pll_tracking> tracking_;
-    std::string role_;
-    unsigned int in_streams_, out_streams_;
     unsigned int vector_length_ = 0;
 };
 
+template <int BAND>
+using GlonassCaDllPllTrackingHip = GlonassCaDllPllTrackingAdapter<BAND, hip_glonass_ca_dll_pll_tracking>;
 using GlonassL1CaDllPllTrackingHip = GlonassCaDllPllTrackingHip<1>;
 using GlonassL2CaDllPllTrackingHip = GlonassCaDllPllTrackingHip<2>;
 

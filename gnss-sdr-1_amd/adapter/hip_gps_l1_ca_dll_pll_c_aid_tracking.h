@@ -19,7 +19,9 @@
 #include "hip_glonass_ca_dll_pll_tracking.h"  // Tracking_2nd_DLL_filter
 #include "hip_multicorrelator.h"
 #include "hip_multicorrelator_16sc.h"
+#include "tracking_adapter_base.h"
 #include "tracking_loop_maths.h"
+#include "tracking_signals.h"
 #include <cmath>
 #include <deque>
 #include <map>
@@ -58,8 +60,16 @@ struct CAidSignal
     bool is_glonass;
     char system;
     double code_rate_hz, code_length_chips, carrier_freq_hz, channel_spacing_hz;
-    static CAidSignal gps_l1() { return {false, 'G', 1.023e6, 1023.0, 1575.42e6, 0.0}; }
-    static CAidSignal glonass(int band) { return band == 2 ? CAidSignal{true, 'R', 0.511e6, 511.0, 1.246e9, 0.4375e6} : CAidSignal{true, 'R', 0.511e6, 511.0, 1.602e9, 0.5625e6}; }
+    static CAidSignal gps_l1()
+    {
+        const gnsscorr::TrkSignalInfo& l1 = gnsscorr::gps_l1_ca();
+        return {false, 'G', l1.code_chip_rate_hz, static_cast<double>(l1.code_length_chips), l1.carrier_freq_hz, 0.0};
+    }
+    static CAidSignal glonass(int band)
+    {
+        const gnsscorr::GlonassBand b = gnsscorr::glonass_band(band);
+        return {true, 'R', gnsscorr::kGlonassCaCodeRateHz, static_cast<double>(gnsscorr::kGlonassCaCodeLengthChips), b.freq_hz, b.dfreq_hz};
+    }
 };
 
 template <class Item>
@@ -345,8 +355,8 @@ public:
 
 private:
     static constexpr double kTwoPi = 6.283185307179586;  // GPS_TWO_PI / GLONASS_TWO_PI
-    double kCodeRateHz = 1.023e6, kCodeLengthChips = 1023.0;
-    double kL1FreqHz = 1575.42e6;  // the carrier the code rate is aided against (GLONASS: the slot's own, set in start_tracking)
+    double kCodeRateHz = 0.0, kCodeLengthChips = 0.0;  // the signal's, set by the constructor
+    double kL1FreqHz = 0.0;  // the carrier the code rate is aided against (GLONASS: the slot's own, set in start_tracking)
 
     CAidSignal d_sig;
     std::map<uint32_t, int32_t> d_glonass_prn;
@@ -383,18 +393,17 @@ private:
 //! TrackingInterface adapter; item_type "gr_complex" or "cshort" picks the block (gps_l1_ca_dll_pll_c_aid_tracking.cc:62-125,
 //! glonass_l1_ca_dll_pll_c_aid_tracking.cc, glonass_l2_ca_dll_pll_c_aid_tracking.cc).  BAND: 0 = GPS L1 C/A, 1 / 2 = GLONASS L1 / L2 C/A
 template <int BAND>
-class DllPllCAidTrackingHip : public TrackingInterface
+class DllPllCAidTrackingHip : public TrackingAdapterRole
 {
 public:
     typedef hip_gps_l1_ca_dll_pll_c_aid_tracking<gr_complex> block_cc;
     typedef hip_gps_l1_ca_dll_pll_c_aid_tracking<std::complex<int16_t>> block_sc;
 
     DllPllCAidTrackingHip(ConfigurationInterface* configuration, const std::string& role, unsigned int in_streams, unsigned int out_streams)
-        : role_(role), in_streams_(in_streams), out_streams_(out_streams)
+        : TrackingAdapterRole(role, in_streams, out_streams)
     {
         item_type_ = configuration->property(role + ".item_type", std::string("gr_complex"));
-        int fs_in_deprecated = configuration->property("GNSS-SDR.internal_fs_hz", 2048000);
-        const int fs_in = configuration->property("GNSS-SDR.internal_fs_sps", fs_in_deprecated);
+        const int fs_in = read_fs(configuration);
         const float pll_bw_hz = configuration->property(role + ".pll_bw_hz", 50.0f);
         const float dll_bw_hz = configuration->property(role + ".dll_bw_hz", 2.0f);
         const float pll_bw_narrow_hz = configuration->property(role + ".pll_bw_narrow_hz", 20.0f);
@@ -417,7 +426,6 @@ public:
             }
     }
 
-    std::string role() override { return role_; }
     std::string implementation() override
     {
         return BAND == 0 ? "GPS_L1_CA_DLL_PLL_C_Aid_Tracking_HIP" : BAND == 1 ? "GLONASS_L1_CA_DLL_PLL_C_Aid_Tracking_HIP" : "GLONASS_L2_CA_DLL_PLL_C_Aid_Tracking_HIP";
@@ -435,8 +443,7 @@ public:
 private:
     std::shared_ptr<block_cc> tracking_cc_;
     std::shared_ptr<block_sc> tracking_sc_;
-    std::string role_, item_type_;
-    unsigned int in_streams_, out_streams_;
+    std::string item_type_;
     unsigned int vector_length_ = 0;
 };
 

@@ -956,6 +956,32 @@ static void test_tracking_group(int iq_format)
         EXPECT(!group.active(5) && group.events(5).size() == 1 && group.events(5)[0] == 3, "group: the ghost satellite's slot did not report loss of lock (%zu events)",
             group.events(5).size());
         EXPECT(!group.active(3) && out[3].empty(), "group: the unused slot produced %zu items", out[3].size());
+        // a restart that fails: slot 4 is running; PRN 99 is one the C/A generator refuses.  The slot was stopped for the restart, so it
+        // is inactive now and the next run() must not report a loss of lock that never happened; the other slots go on as they were
+        if (launches > 0)
+            {
+                const size_t pushed = static_cast<size_t>(launches) * block;
+                const std::vector<std::vector<Gnss_Synchro>> before = out;
+                const size_t events_before = group.events(4).size();
+                Gnss_Synchro refused = acq_of(1, pushed);
+                refused.PRN = 99;
+                EXPECT(group.start_tracking(4, refused, pushed) != GC_OK, "group: a restart with PRN 99 was accepted");
+                EXPECT(!group.active(4), "group: the slot is still active after its restart failed");
+                const void* tail = iq_format == GC_IQ_I16 ? static_cast<const void*>(xs.data() + pushed) : static_cast<const void*>(x.data() + pushed);
+                EXPECT(gc_stream_push(ring, tail, n - pushed, nullptr) == GC_OK, "group: push of the tail (%s)", gc_last_error());
+                EXPECT(group.run(out) >= 0, "group: run after the failed restart, status %d (%s)", group.last_status(), gc_last_error());
+                EXPECT(group.events(4).size() == events_before && out[4].size() == before[4].size(), "group: the slot whose restart failed got %zu events and %zu items",
+                    group.events(4).size() - events_before, out[4].size() - before[4].size());
+                for (int k : {0, 2, 1})
+                    {
+                        bool same = out[k].size() > before[k].size() && group.active(k);
+                        for (size_t i = 0; same && i < before[k].size(); i++)
+                            same = out[k][i].Tracking_sample_counter == before[k][i].Tracking_sample_counter && out[k][i].Prompt_I == before[k][i].Prompt_I &&
+                                   out[k][i].Carrier_Doppler_hz == before[k][i].Carrier_Doppler_hz;
+                        EXPECT(same && out[k].back().Tracking_sample_counter - before[k].back().Tracking_sample_counter <= (n - pushed) + 4003,
+                            "group: slot %d did not go on as before after another slot's restart failed (%zu -> %zu items)", k, before[k].size(), out[k].size());
+                    }
+            }
         std::printf("tracking group (%s ring): 4 satellites + 1 ghost on 6 slots, %d launches for %.0f ms of signal: %zu / %zu / %zu / %zu Gnss_Synchro, ghost lost lock after %zu\n",
             iq_format == GC_IQ_I16 ? "cshort" : "gr_complex", launches, n / fs * 1e3, out[0].size(), out[4].size(), out[2].size(), out[1].size(), out[5].size());
     }
