@@ -63,15 +63,17 @@ def preconditions(r):
 
 # ---- 1. the matrix against the restatement ----------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("N, f", list(SHAPES), ids=SHAPE_IDS)
-def test_matrix_against_the_restatement(gctx, oracle, N, f):
+def check_against_the_restatement(gctx, oracle, N, f, case, truth_checked):
+    """One engine, one dwell of `case` = (x, truth, code, restatement's result) for a code period of N samples folded f times: the
+    grid, row maxima, result, candidates and delay, the folded code spectrum and a wipe-off row.  Shared with
+    tests/test_acq_kind_matrix_gpu.py; returns the engine for what a caller runs on top (the caller closes it)."""
     import gnsscorr
-    x, truth, code, ref = reference(oracle, N, f)
+    x, truth, code, ref = case
     M, L = N // f, f * N
     margin, ratio = preconditions(ref)
     print("restatement: k* %d bin %d delay %d, margin %.3g, candidate ratio %.3g" % (ref.indext, ref.doppler_index, ref.acq_delay_samples, margin, ratio))
     assert margin > 10 * TOL and ratio >= 2.0
-    if N % f == 0:
+    if truth_checked:
         # the true delay and the nearest bin; (4000, 3) folds 1333-sample pieces of 4000-sample periods and slips a sample per period
         expect = (-truth["tau0"] * N * 1000 / 1.023e6) % N
         d = abs(ref.acq_delay_samples - expect)
@@ -111,7 +113,12 @@ def test_matrix_against_the_restatement(gctx, oracle, N, f):
     got = acq.peek(acq.PEEK_CODE, 0)
     assert got.size == M and np.max(np.abs(got - cf)) <= TOL * np.max(np.abs(cf))
     assert acq.peek(acq.PEEK_SPECTRUM, 2).size == M
-    acq.close()
+    return acq
+
+
+@pytest.mark.parametrize("N, f", list(SHAPES), ids=SHAPE_IDS)
+def test_matrix_against_the_restatement(gctx, oracle, N, f):
+    check_against_the_restatement(gctx, oracle, N, f, reference(oracle, N, f), N % f == 0).close()
 
 
 # ---- 2. f = 1 is the plain search --------------------------------------------------------------------------------------------------

@@ -3,7 +3,9 @@ Bars are those of tests/test_acquisition_gpu.py: indices and Doppler exact, magn
 thresholds are chosen on the restatement alone (tests/tong_cases.py) under two conditions every test asserts before it touches the
 GPU: every q_d = d_mag / dwell_count lies at least 1e-2 (50 x the 2 TOL the engine's mag may be off) from the threshold, which sits
 in the geometric middle of a gap of ratio >= 1.05 between sorted q values; and a result's cell is compared exactly only where the
-restatement's top cell beats its runner-up by more than 10 TOL -- otherwise any cell it holds within TOL of its maximum is accepted."""
+restatement's top cell beats its runner-up by more than 10 TOL -- otherwise any cell it holds within TOL of its maximum is accepted.
+The sizes here (N = 2000, 4000, 6625, 25000 and the five-satellite engine's 2000) reach the column sizes N1 = 2, 4, 5 and 25 only; the
+column kernel at every instantiated N1 is tests/test_acq_kind_matrix_gpu.py's."""
 import numpy as np
 import pytest
 
@@ -97,10 +99,12 @@ def snapshot(acq, res, status):
     return [(_fields(res[s_]), _status(status[s_]), acq.grid(s_).tobytes(), acq.peek(acq.PEEK_ROW_MAX, s_).tobytes()) for s_ in range(acq.n_sats)]
 
 
-# ---- 1. the matrix against the restatement ----------------------------------------------------------------------------------------
+# ---- 1. four walks against the restatement -----------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("N", list(SHAPES))
 def test_matrix_against_the_restatement(gctx, oracle, N):
+    """Four sizes (column sizes N1 = 2, 4, 5 and 25), one per kind of walk: no matrix of the column kernel's instances, in spite of
+    the name.  All 17 N1 of acq_cols_tong_kernel run in tests/test_acq_kind_matrix_gpu.py."""
     import gnsscorr
     x, code, recs, thr, ratio = matrix_reference(oracle, N)
     walk = tc.outcome(recs, thr, TONG)
