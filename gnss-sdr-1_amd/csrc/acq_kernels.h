@@ -4,7 +4,7 @@
 #include "gnsscorr.h"
 #include <hip/hip_runtime.h>
 #include "acq_phase_segments.h"
-#include "acq_plan.h"  // AcqFftPlan, acq_plan_make, acq_rows_lds_bytes, acq_cols_blocks
+#include "acq_plan.h"  // AcqFftPlan, acq_plan_make, acq_rows_lds_bytes, acq_cols_blocks, AcqRowsPlan
 
 // which array slice a cell reads: index = (cell / div) % mod
 struct AcqCellMap
@@ -55,8 +55,12 @@ void acq_stage_twiddles(const AcqFftPlan& plan, float2* out /* 2*N2 entries */);
 hipError_t acq_launch_permute(hipStream_t st, const float2* in, const float2* mul, float2* out,
     const AcqFftPlan& plan, int n_valid, int n_arrays, size_t in_stride, size_t mul_stride, size_t out_stride);
 
+// the row kernel of every acq_launch_rows with this plan (acq_rows_plan_make under the experiments build's cap on the rows per
+// workgroup): an engine makes it once, beside its plan
+AcqRowsPlan acq_rows_plan(const AcqFftPlan& plan);
+
 // rows pass: Q[cell][k1][n2] = twiddle * FFT_N2(A[mapA(cell)][k1][.] * B[mapB(cell)][k1][.])
-hipError_t acq_launch_rows(hipStream_t st, bool inverse, const AcqFftPlan& plan, int n_cells,
+hipError_t acq_launch_rows(hipStream_t st, bool inverse, const AcqFftPlan& plan, const AcqRowsPlan& rows, int n_cells,
     const float2* A, AcqCellMap mapA, const float2* B, AcqCellMap mapB,
     float2* Q, const float2* wN2, const float2* wN);
 
@@ -71,12 +75,13 @@ hipError_t acq_launch_cols(hipStream_t st, bool inverse, int epilogue, const Acq
 hipError_t acq_launch_cols_tong(hipStream_t st, bool accumulate, const AcqFftPlan& plan, int n_cells, const float2* Q, const AcqMagArgs& mag,
     const int* frozen, const float* power);
 
+#ifdef GNSSCORR_EXPERIMENTS
 // The inverse row pass of one batch (arguments as acq_launch_rows, inverse) and the two-dwell column pass (epilogue ACQ_EPI_MAG2 /
 // _MAG2_ACC, n_cells_cols grid cells read from Qc) of the previous batch in ONE launch; only for plans acq_rows_cols_fusable() accepts
 // (N = 25 x 1000, the planar pair row kernel)
-bool acq_rows_cols_fusable(const AcqFftPlan& plan);
-hipError_t acq_launch_rows_cols(hipStream_t st, const AcqFftPlan& plan, int n_cells, const float2* A, AcqCellMap mapA, const float2* B,
-    AcqCellMap mapB, float2* Q, const float2* wN2, const float2* wN, int epilogue, int n_cells_cols, const float2* Qc, const AcqMagArgs& mag);
+bool acq_rows_cols_fusable(const AcqFftPlan& plan, const AcqRowsPlan& rows);
+hipError_t acq_launch_rows_cols(hipStream_t st, const AcqFftPlan& plan, const AcqRowsPlan& rows, int n_cells, const float2* A, AcqCellMap mapA,
+    const float2* B, AcqCellMap mapB, float2* Q, const float2* wN2, const float2* wN, int epilogue, int n_cells_cols, const float2* Qc, const AcqMagArgs& mag);
 
 // The whole inverse transform of every cell on chip (no inter-pass buffer), for plans acq_inv_fusable() accepts (N = 25 x 1000):
 // grid cell (sat, bin) <- |IFFT(A[bin] * B[sat])|^2 (n_tr = 1), or that of A[bin] and then of A[n_bins + bin] on top (n_tr = 2: a
@@ -85,6 +90,7 @@ hipError_t acq_launch_rows_cols(hipStream_t st, const AcqFftPlan& plan, int n_ce
 bool acq_inv_fusable(const AcqFftPlan& plan);
 hipError_t acq_launch_inv_fused(hipStream_t st, const AcqFftPlan& plan, int n_sats, int n_bins, int n_tr, bool accumulate, const float2* A, const float2* B,
     const float2* wN2, const float2* wN, const AcqMagArgs& mag, int n_cus);
+#endif  // GNSSCORR_EXPERIMENTS
 
 // out[bin][(n % N1) * N2 + n / N1] = (cos, sin) of the float32 running phase of sample n (volk_gnsssdr_s32f_sincos_32fc): the table in the
 // row-permuted layout the forward row pass reads, in one kernel from the rows' arithmetic-progression segments (acq_phase_segments.h):
@@ -105,7 +111,7 @@ struct AcqFinalArgs
     const unsigned* blk_max_idx;
     const float* input_power;
     gc_acq_result* results;
-    float* part_val;     // [sat][ACQ_FINAL_PIECES][2]: second-peak candidates of the row pieces
+    float* part_val;     // [sat][ACQ_FINAL_SPLIT][2]: second-peak candidates of the row pieces
     unsigned* part_cnt;  // [sat]: ticket counters, zero between launches
     int n_bins, n_blocks, fft_size;
     int doppler_max, doppler_step;
@@ -116,7 +122,7 @@ struct AcqFinalArgs
     float center_step_two, doppler_step2;
     int n_bins_step2;
 };
-#define ACQ_FINAL_PIECES 8  // = ACQ_FINAL_SPLIT of acq_kernels.hip
+#define ACQ_FINAL_SPLIT 8  // row pieces, one workgroup each (acq_final_kernel)
 hipError_t acq_launch_final(hipStream_t st, const AcqFinalArgs& a, int n_sats);
 
 #endif

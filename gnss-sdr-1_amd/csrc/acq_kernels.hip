@@ -25,6 +25,7 @@
 #include <cstdio>
 #include <vector>
 #include <algorithm>
+#include <type_traits>
 
 #ifndef ACQ_PK_CMUL
 #define ACQ_PK_CMUL 0  // 1: complex multiplies as two hand-written packed-FP32 instructions.  Measured: the compiler already emits the same
@@ -355,13 +356,11 @@ __global__ __launch_bounds__(ACQ_THREADS) void acq_rows_kernel(AcqFftPlan plan,
 // workgroups per CU).  The kernel is a template of its stage list (radix and butterflies per thread of
 // every stage): row length, strides and the first/last roles are compile-time constants, and each
 // instantiation holds only its own stages, which keeps it at <= 128 VGPRs (one switch over all radices
-// in one kernel made the register allocator spill).  acq_rows2_registry lists the instantiated
+// in one kernel made the register allocator spill).  ACQ_ROWS2_LIST (acq_plan.h) lists the instantiated
 // stage lists; any other row length runs acq_rows_kernel.
 #ifndef ACQ_ROWS2_WAVES
 #define ACQ_ROWS2_WAVES 4  // waves per SIMD the register allocator must leave room for
 #endif
-#define ACQ_ROWS2_POINTS 20       // R * ITER: points a thread holds per stage
-#define ACQ_ROWS2_LDS_BYTES 40000 // rows * N2 * 8 per workgroup: four workgroups per CU
 
 struct AcqRows2Args
 {
@@ -1142,77 +1141,13 @@ __global__ __launch_bounds__(ACQ_THREADS, ACQ_ROWS2_WAVES) void acq_rows2_kernel
     Rows2Run<INV, Rows2Len<RI...>::value, 1, 0, RI...>::run(plan, g, sm, row0, nrow);
 }
 
-// instantiated stage lists (radix, butterflies per thread), as acq_rows2_config derives them for the row
-// lengths the planner picks for 1/2/4/8 ms blocks at 2 ... 25 Msps (and the power-of-two sizes)
+// the instances of ACQ_ROWS2_LIST, in its order: AcqRowsPlan::entry indexes both
 typedef void (*AcqRows2Fn)(AcqFftPlan, AcqRows2Args);
-struct AcqRows2Entry
-{
-    int n_stages;
-    int ri[4];
-    AcqRows2Fn fwd, inv;
-    AcqRows2Fn pair_fwd, pair_inv;  // the same stage list on butterfly pairs (rows2p_stage), where its shape conditions hold
-};
-#define R2(r, i) ((r) * 16 + (i))
-#define ROWS2_ENTRY3(a, b, c) {3, {a, b, c, 0}, &acq_rows2_kernel<false, a, b, c>, &acq_rows2_kernel<true, a, b, c>, nullptr, nullptr}
-#define ROWS2_ENTRY4(a, b, c, d) {4, {a, b, c, d}, &acq_rows2_kernel<false, a, b, c, d>, &acq_rows2_kernel<true, a, b, c, d>, nullptr, nullptr}
-static const AcqRows2Entry acq_rows2_registry[] = {
-    {3, {R2(10, 2), R2(10, 2), R2(10, 2), 0}, &acq_rows2_kernel<false, R2(10, 2), R2(10, 2), R2(10, 2)>, &acq_rows2_kernel<true, R2(10, 2), R2(10, 2), R2(10, 2)>,
-        &acq_rows3_kernel<false>, &acq_rows3_kernel<true>},  // 1000: N = 2000 ... 25000 (planar pair kernel)
-    ROWS2_ENTRY3(R2(10, 1), R2(10, 1), R2(10, 1)),            // 1000, at most 2 rows per workgroup
-    ROWS2_ENTRY3(R2(16, 1), R2(16, 1), R2(4, 4)),             // 1024
-    ROWS2_ENTRY4(R2(10, 2), R2(5, 4), R2(5, 4), R2(5, 4)),    // 1250: N = 2500, 6250, 12500
-    ROWS2_ENTRY3(R2(16, 1), R2(16, 1), R2(5, 4)),             // 1280: N = 32000
-    ROWS2_ENTRY3(R2(16, 1), R2(16, 1), R2(8, 2)),             // 2048
-    ROWS2_ENTRY3(R2(16, 1), R2(10, 2), R2(10, 2)),            // 1600: N = 40000
-    ROWS2_ENTRY4(R2(16, 1), R2(5, 4), R2(5, 4), R2(5, 4)),    // 2000: N = 50000
-    ROWS2_ENTRY3(R2(16, 1), R2(16, 1), R2(10, 1)),            // 2560: N = 64000
-    ROWS2_ENTRY3(R2(16, 1), R2(16, 1), R2(16, 1)),            // 4096
-    ROWS2_ENTRY4(R2(16, 1), R2(10, 2), R2(5, 4), R2(5, 4)),   // 4000: N = 100000
-    ROWS2_ENTRY4(R2(16, 1), R2(10, 2), R2(3, 4), R2(2, 8)),   // 960: N = 24000
-    ROWS2_ENTRY4(R2(16, 1), R2(10, 2), R2(10, 2), R2(2, 8)),  // 3200: N = 80000
-};
-#undef ROWS2_ENTRY3
-#undef ROWS2_ENTRY4
-
-// rows per workgroup and per-stage butterflies per thread for the packed kernel; false: use acq_rows_kernel
-static bool acq_rows2_config(const AcqFftPlan& plan, int* rpw_out, int* iters)
-{
-    const int radices_ok[] = {2, 3, 4, 5, 8, 10, 16};
-    for (int f = 0; f < plan.n_fac; f++)
-        {
-            bool ok = false;
-            for (int r : radices_ok) ok = ok || (plan.fac[f] == r);
-            if (!ok) return false;
-        }
-    if ((size_t)plan.N2 * sizeof(float2) > 64 * 1024) return false;
-    int rpw = (int)(ACQ_ROWS2_LDS_BYTES / ((size_t)plan.N2 * sizeof(float2)));
-    if (rpw < 1) rpw = 1;
-    if (rpw > 16) rpw = 16;
-    static const int rpw_cap = [] {
-        const char* e = gc_exp_env("GNSSCORR_ACQ_RPW");  // tuning knob: cap on the rows per workgroup
-        return e ? std::atoi(e) : 0;
-    }();
-    if (rpw_cap > 0 && rpw > rpw_cap) rpw = rpw_cap;
-    for (; rpw >= 1; rpw--)
-        {
-            bool fits = true;
-            for (int f = 0; f < plan.n_fac && fits; f++)
-                {
-                    const int R = plan.fac[f], nb = plan.N2 / R;
-                    const int need = (rpw * nb + ACQ_THREADS - 1) / ACQ_THREADS;
-                    int it = 1;
-                    while (it < need) it *= 2;
-                    if (it * R > ACQ_ROWS2_POINTS || it > 8) fits = false;
-                    iters[f] = it;
-                }
-            if (fits)
-                {
-                    *rpw_out = rpw;
-                    return true;
-                }
-        }
-    return false;
-}
+#define ROWS2_FNS(...) {&acq_rows2_kernel<false, __VA_ARGS__>, &acq_rows2_kernel<true, __VA_ARGS__>},
+static const AcqRows2Fn acq_rows2_fns[][2] = {ACQ_ROWS2_LIST(ROWS2_FNS)};  // [entry][inverse]
+#undef ROWS2_FNS
+// the same stage list on butterfly pairs, where its shape conditions hold: ACQ_ROWS2_PAIR_ENTRY only
+static const AcqRows2Fn acq_rows2_pair_fns[2] = {&acq_rows3_kernel<false>, &acq_rows3_kernel<true>};
 
 // ---- register-resident N1-point DFT (Stockham, fully unrolled) ----
 template <int N>
@@ -2118,9 +2053,7 @@ __global__ __launch_bounds__(1024) void acq_input_power_kernel(const float2* __r
 // scan of the peak's row (N elements, ~35 instructions each) is cut into ACQ_FINAL_SPLIT pieces, one workgroup each, so that a
 // satellite's statistic is not the work of a single CU (one 1024-thread workgroup per satellite took 18-20 us for N = 25000, on 32
 // of the chip's 256 CUs).  The last workgroup of a satellite to finish combines the pieces (ticket counter in global memory, reset
-// for the next launch; release / acquire fences at agent scope around it).
-#define ACQ_FINAL_SPLIT 8
-static_assert(ACQ_FINAL_SPLIT == ACQ_FINAL_PIECES, "acq_kernels.h sizes the hand-over buffer");
+// for the next launch; release / acquire fences at agent scope around it).  ACQ_FINAL_SPLIT: acq_kernels.h, which sizes the hand-over buffer
 #define ACQ_FINAL_THREADS 256
 struct MaxKey
 {
@@ -2351,15 +2284,62 @@ void acq_stage_twiddles(const AcqFftPlan& plan, float2* out)
         }
 }
 
+// The tuning switches of the experiments build ($GNSSCORR_ACQ_*), read once.  The product library reads none:
+// gc_exp_env answers null there and every field keeps the default written here.
+struct AcqRowKnobs
+{
+    bool force_wg;           // _ROWS=wg: the general row kernel for every size
+    bool no_pairs;           // _ROWS=nopair: the plain packed kernel where a pair kernel exists
+    bool interleaved_pairs;  // _ROWS=pair2p: the pair kernel with (re, im) packing
+    bool permute_plain;      // _PERMUTE=plain: the untiled permutation
+    // _ROW_ORDER, row order of the pair kernel: 0 = (bin, sat, k1), 1 = (bin, k1, sat), 2 = (k1, bin, sat) with the last digit running fastest.
+    // An XCD walks a contiguous eighth of the rows; with 2 it needs row k1 of every spectrum and of every code at a time (a few
+    // hundred KB, read once per launch), with 0 / 1 it sweeps all the codes once per bin and its L2 (4 MB) has dropped them by then.
+    int row_order;
+    // _PERSIST, workgroups per CU of the persistent row launch (0: one block per group).  Measured: with the (bin, k1, sat) order 4 per CU
+    // (what the LDS admits) was 2 % faster than a block per group, with the (k1, bin, sat) order a block per group is 2-3 % faster
+    // (0.311-0.321 vs 0.320-0.327 ms per search)
+    int persist;
+    int rpw_cap;          // _RPW: cap on the rows per workgroup of the packed kernel (0: none)
+    int row_threads;      // _ROW_THREADS: 64 / 128 / 256 threads for the general row kernel (0: ACQ_THREADS)
+    int dbg;              // _DBG: phase-elimination timing (ACQ_ROWS3_DBG builds only)
+    const char* ts_file;  // _TS_FILE: where the stamps of _DBG & 64 go as well
+};
+static const AcqRowKnobs& acq_row_knobs()
+{
+    static const AcqRowKnobs knobs = [] {
+        const auto is = [](const char* name, const char* value) {
+            const char* e = gc_exp_env(name);
+            return e && std::strcmp(e, value) == 0;
+        };
+        const auto num = [](const char* name, int none) {
+            const char* e = gc_exp_env(name);
+            return e ? std::atoi(e) : none;
+        };
+        AcqRowKnobs k;
+        k.force_wg = is("GNSSCORR_ACQ_ROWS", "wg");
+        k.no_pairs = is("GNSSCORR_ACQ_ROWS", "nopair");
+        k.interleaved_pairs = is("GNSSCORR_ACQ_ROWS", "pair2p");
+        k.permute_plain = is("GNSSCORR_ACQ_PERMUTE", "plain");
+        k.row_order = num("GNSSCORR_ACQ_ROW_ORDER", 2);
+        k.persist = num("GNSSCORR_ACQ_PERSIST", 0);
+        k.rpw_cap = num("GNSSCORR_ACQ_RPW", 0);
+        k.row_threads = num("GNSSCORR_ACQ_ROW_THREADS", 0);
+        if (k.row_threads != 64 && k.row_threads != 128 && k.row_threads != 256) k.row_threads = 0;
+        k.dbg = num("GNSSCORR_ACQ_DBG", 0);
+        k.ts_file = gc_exp_env("GNSSCORR_ACQ_TS_FILE");
+        return k;
+    }();
+    return knobs;
+}
+
+AcqRowsPlan acq_rows_plan(const AcqFftPlan& plan) { return acq_rows_plan_make(plan, acq_row_knobs().rpw_cap); }
+
 hipError_t acq_launch_permute(hipStream_t st, const float2* in, const float2* mul, float2* out,
     const AcqFftPlan& plan, int n_valid, int n_arrays, size_t in_stride, size_t mul_stride, size_t out_stride)
 {
-    static const bool plain = [] {
-        const char* e = gc_exp_env("GNSSCORR_ACQ_PERMUTE");
-        return e && std::strcmp(e, "plain") == 0;
-    }();
     const size_t lds = sizeof(float2) * ACQ_PERM_TB * (size_t)plan.N1;
-    if (!plain && lds <= 48 * 1024)
+    if (!acq_row_knobs().permute_plain && lds <= 48 * 1024)
         {
             dim3 grid((plan.N2 + ACQ_PERM_TB - 1) / ACQ_PERM_TB, n_arrays);
             hipLaunchKernelGGL(acq_permute_tiled_kernel, grid, dim3(256), lds, st, in, mul, out, plan.N, plan.N1, plan.N2, n_valid, in_stride, mul_stride,
@@ -2372,31 +2352,12 @@ hipError_t acq_launch_permute(hipStream_t st, const float2* in, const float2* mu
     return hipGetLastError();
 }
 
-static int acq_rows_order()
+// the arguments of a packed or pair row kernel over n_cells cells, numbered cell = sat * n_bins + bin
+static AcqRows2Args fill_rows_args(const AcqFftPlan& plan, const AcqRowsPlan& rows, int n_cells, const float2* A, AcqCellMap mapA, const float2* B,
+    AcqCellMap mapB, float2* Q, const float2* wN2, const float2* wN)
 {
-    static const int row_order = [] {
-        const char* e = gc_exp_env("GNSSCORR_ACQ_ROW_ORDER");
-        return e ? std::atoi(e) : 2;
-    }();
-    return row_order;
-}
-
-#ifdef GNSSCORR_EXPERIMENTS
-bool acq_rows_cols_fusable(const AcqFftPlan& plan)
-{
-    int rpw, iters[ACQ_MAX_FACTORS];
-    return plan.N1 == 25 && plan.N2 == 1000 && plan.n_fac == 3 && plan.fac[0] == 10 && plan.fac[1] == 10 && plan.fac[2] == 10 &&
-           acq_rows2_config(plan, &rpw, iters) && (size_t)rpw * plan.N2 * sizeof(float2) >= (size_t)(25 * ACQ_THREADS + 2 * (ACQ_THREADS / 64)) * sizeof(float);
-}
-
-hipError_t acq_launch_rows_cols(hipStream_t st, const AcqFftPlan& plan, int n_cells, const float2* A, AcqCellMap mapA, const float2* B,
-    AcqCellMap mapB, float2* Q, const float2* wN2, const float2* wN, int epilogue, int n_cells_cols, const float2* Qc, const AcqMagArgs& mag)
-{
-    if (!acq_rows_cols_fusable(plan) || (epilogue != ACQ_EPI_MAG2 && epilogue != ACQ_EPI_MAG2_ACC)) return hipErrorInvalidValue;
     AcqRows2Args g;
     std::memset(&g, 0, sizeof g);
-    int iters[ACQ_MAX_FACTORS];
-    acq_rows2_config(plan, &g.rpw, iters);
     g.A = A;
     g.mapA = mapA;
     g.B = B;
@@ -2405,10 +2366,26 @@ hipError_t acq_launch_rows_cols(hipStream_t st, const AcqFftPlan& plan, int n_ce
     g.wN2 = wN2;
     g.wN = wN;
     g.n_rows = plan.N1 * n_cells;
+    g.rpw = rows.rpw;
     g.n_bins = mapA.mod;
     g.n_sats = n_cells / mapA.mod;
     g.n_groups = (g.n_rows + g.rpw - 1) / g.rpw;
-    g.sat_fastest = g.n_sats > 1 ? acq_rows_order() : 0;
+    g.sat_fastest = (B != nullptr && g.n_sats > 1) ? acq_row_knobs().row_order : 0;
+    return g;
+}
+
+#ifdef GNSSCORR_EXPERIMENTS
+bool acq_rows_cols_fusable(const AcqFftPlan& plan, const AcqRowsPlan& rows)
+{
+    return plan.N1 == 25 && plan.N2 == 1000 && plan.n_fac == 3 && plan.fac[0] == 10 && plan.fac[1] == 10 && plan.fac[2] == 10 && rows.entry >= 0 &&
+           (size_t)rows.rpw * plan.N2 * sizeof(float2) >= (size_t)(25 * ACQ_THREADS + 2 * (ACQ_THREADS / 64)) * sizeof(float);
+}
+
+hipError_t acq_launch_rows_cols(hipStream_t st, const AcqFftPlan& plan, const AcqRowsPlan& rows, int n_cells, const float2* A, AcqCellMap mapA,
+    const float2* B, AcqCellMap mapB, float2* Q, const float2* wN2, const float2* wN, int epilogue, int n_cells_cols, const float2* Qc, const AcqMagArgs& mag)
+{
+    if (!acq_rows_cols_fusable(plan, rows) || (epilogue != ACQ_EPI_MAG2 && epilogue != ACQ_EPI_MAG2_ACC)) return hipErrorInvalidValue;
+    const AcqRows2Args g = fill_rows_args(plan, rows, n_cells, A, mapA, B, mapB, Q, wN2, wN);
     const size_t lds2 = (size_t)g.rpw * plan.N2 * sizeof(float2);
     const int n_xblk = acq_cols_blocks(plan);
     dim3 grid(256 * 4);  // 4 workgroups per CU (what the row pass's LDS admits), a multiple of 32
@@ -2418,151 +2395,85 @@ hipError_t acq_launch_rows_cols(hipStream_t st, const AcqFftPlan& plan, int n_ce
         hipLaunchKernelGGL(acq_rows3_cols_kernel<ACQ_EPI_MAG2_ACC>, grid, dim3(ACQ_THREADS), lds2, st, plan, g, Qc, mag, n_cells_cols, n_xblk);
     return hipGetLastError();
 }
-
 #endif  // GNSSCORR_EXPERIMENTS
 
-hipError_t acq_launch_rows(hipStream_t st, bool inverse, const AcqFftPlan& plan, int n_cells,
-    const float2* A, AcqCellMap mapA, const float2* B, AcqCellMap mapB,
-    float2* Q, const float2* wN2, const float2* wN)
+#if ACQ_ROWS3_DBG
+// TIMING EXPERIMENT ($GNSSCORR_ACQ_DBG & 64): run the launch with a stamp buffer, fetch the stamps, print where a workgroup's lifetime
+// goes (synchronises the device)
+static hipError_t launch_rows_stamped(AcqRows2Fn fn, dim3 grid, AcqRows2Args& g, void** args, size_t lds, hipStream_t st)
 {
-    static const bool force_wg = [] {
-        const char* e = gc_exp_env("GNSSCORR_ACQ_ROWS");
-        return e && std::strcmp(e, "wg") == 0;
-    }();
-    AcqRows2Args g;
-    std::memset(&g, 0, sizeof g);
-    int iters[ACQ_MAX_FACTORS];
-    const AcqRows2Entry* entry = nullptr;
-    // the packed kernel understands the engine's cell numbering only: cell = sat * n_bins + bin
-    const bool cell_layout_ok = mapA.div == 1 && n_cells % mapA.mod == 0 && (B == nullptr ? n_cells == mapA.mod : (mapB.div == mapA.mod && mapB.mod >= (1 << 30)));
-    if (!force_wg && cell_layout_ok && plan.n_fac <= 4 && acq_rows2_config(plan, &g.rpw, iters))
+    static unsigned long long* d_ts = nullptr;
+    static size_t ts_cap = 0;
+    if (ts_cap < (size_t)g.n_groups * 8)
         {
-            for (const AcqRows2Entry& e : acq_rows2_registry)
-                {
-                    bool same = (e.n_stages == plan.n_fac);
-                    for (int f = 0; f < plan.n_fac && same; f++) same = (e.ri[f] == R2(plan.fac[f], iters[f]));
-                    if (same) entry = &e;
-                }
+            (void)hipFree(d_ts);
+            ts_cap = (size_t)g.n_groups * 8;
+            (void)hipMalloc(&d_ts, ts_cap * sizeof(unsigned long long));
         }
-    if (entry)
+    g.ts = d_ts;
+    hipError_t el = hipLaunchKernel(reinterpret_cast<const void*>(fn), grid, dim3(ACQ_THREADS), args, lds, st);
+    if (!g.ts) return el;
+    (void)hipDeviceSynchronize();
+    static int printed = 0;
+    if (printed++ % 40 == 39)
         {
-            g.A = A;
-            g.mapA = mapA;
-            g.B = B;
-            g.mapB = mapB;
-            g.Q = Q;
-            g.wN2 = wN2;
-            g.wN = wN;
-            g.n_rows = plan.N1 * n_cells;
-            g.n_bins = mapA.mod;
-            g.n_sats = n_cells / mapA.mod;
-            g.n_groups = (g.n_rows + g.rpw - 1) / g.rpw;
-            dim3 grid2((unsigned)((g.n_groups + 7) / 8 * 8));
-            const size_t lds2 = (size_t)g.rpw * plan.N2 * sizeof(float2);
-            AcqFftPlan plan_arg = plan;
-            void* args[] = {&plan_arg, &g};
-            static const bool no_pairs = [] {
-                const char* e = gc_exp_env("GNSSCORR_ACQ_ROWS");
-                return e && std::strcmp(e, "nopair") == 0;  // A/B knob: the plain packed kernel
-            }();
-            AcqRows2Fn fn = inverse ? entry->inv : entry->fwd;
-            if (!no_pairs && entry->pair_fwd) fn = inverse ? entry->pair_inv : entry->pair_fwd;
-            static const bool interleaved_pairs = [] {
-                const char* e = gc_exp_env("GNSSCORR_ACQ_ROWS");
-                return e && std::strcmp(e, "pair2p") == 0;  // A/B knob: the pair kernel with (re, im) packing
-            }();
-#ifdef GNSSCORR_EXPERIMENTS
-            if (interleaved_pairs && entry->pair_fwd)
-                fn = inverse ? reinterpret_cast<AcqRows2Fn>(&acq_rows2p_kernel<true, 10, 10, 10>) : reinterpret_cast<AcqRows2Fn>(&acq_rows2p_kernel<false, 10, 10, 10>);
-#else
-            (void)interleaved_pairs;
-#endif
-            // row order of the pair kernel: 0 = (bin, sat, k1), 1 = (bin, k1, sat), 2 = (k1, bin, sat) with the last digit running fastest.
-            // An XCD walks a contiguous eighth of the rows; with 2 it needs row k1 of every spectrum and of every code at a time (a few
-            // hundred KB, read once per launch), with 0 / 1 it sweeps all the codes once per bin and its L2 (4 MB) has dropped them by then.
-            g.sat_fastest = (B != nullptr && g.n_sats > 1) ? acq_rows_order() : 0;
-            static const int dbg = [] {
-                const char* e = gc_exp_env("GNSSCORR_ACQ_DBG");  // phase-elimination timing (ACQ_ROWS3_DBG builds only)
-                return e ? std::atoi(e) : 0;
-            }();
-            g.dbg = dbg;
-#if ACQ_ROWS3_DBG
-            static unsigned long long* d_ts = nullptr;
-            static size_t ts_cap = 0;
-            if ((dbg & 64) && inverse)
+            std::vector<unsigned long long> h((size_t)g.n_groups * 8);
+            (void)hipMemcpy(h.data(), g.ts, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+            double sum[6] = {0, 0, 0, 0, 0, 0};
+            unsigned long long tmin = ~0ull, tmax = 0;
+            for (int i = 0; i < g.n_groups; i++)
                 {
-                    if (ts_cap < (size_t)g.n_groups * 8)
-                        {
-                            (void)hipFree(d_ts);
-                            ts_cap = (size_t)g.n_groups * 8;
-                            (void)hipMalloc(&d_ts, ts_cap * sizeof(unsigned long long));
-                        }
-                    g.ts = d_ts;
+                    const unsigned long long* t = &h[(size_t)i * 8];
+                    for (int k = 0; k < 6; k++) sum[k] += (double)(t[k + 1] - t[k]);
+                    tmin = std::min(tmin, t[0]);
+                    tmax = std::max(tmax, t[6]);
                 }
-#endif
-            static const int persist = [] {
-                const char* e = gc_exp_env("GNSSCORR_ACQ_PERSIST");  // workgroups per CU of the persistent row launch (0: one block per group)
-                return e ? std::atoi(e) : 0;  // measured: with the (bin, k1, sat) order 4 per CU (what the LDS admits) was 2 % faster than a block per group,
-                                              // with the (k1, bin, sat) order a block per group is 2-3 % faster (0.311-0.321 vs 0.320-0.327 ms per search)
-            }();
-            if (persist > 0 && entry->pair_fwd && fn == (inverse ? entry->pair_inv : entry->pair_fwd))
+            if (FILE* f = acq_row_knobs().ts_file ? std::fopen(acq_row_knobs().ts_file, "wb") : nullptr)
                 {
-                    const unsigned cap = (unsigned)(persist * 256);
-                    if (grid2.x > cap) grid2.x = cap;
+                    std::fwrite(h.data(), sizeof(unsigned long long), h.size(), f);
+                    std::fclose(f);
                 }
-#if ACQ_ROWS3_DBG
-            if ((dbg & 64) && inverse && g.ts)
-                {
-                    // TIMING EXPERIMENT: run the launch, fetch the stamps, print where a workgroup's lifetime goes (synchronises the device)
-                    hipError_t el = hipLaunchKernel(reinterpret_cast<const void*>(fn), grid2, dim3(ACQ_THREADS), args, lds2, st);
-                    (void)hipDeviceSynchronize();
-                    static int printed = 0;
-                    if (printed++ % 40 == 39)
-                        {
-                            std::vector<unsigned long long> h((size_t)g.n_groups * 8);
-                            (void)hipMemcpy(h.data(), g.ts, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-                            double sum[6] = {0, 0, 0, 0, 0, 0};
-                            unsigned long long tmin = ~0ull, tmax = 0;
-                            for (int i = 0; i < g.n_groups; i++)
-                                {
-                                    const unsigned long long* t = &h[(size_t)i * 8];
-                                    for (int k = 0; k < 6; k++) sum[k] += (double)(t[k + 1] - t[k]);
-                                    tmin = std::min(tmin, t[0]);
-                                    tmax = std::max(tmax, t[6]);
-                                }
-                            if (const char* tf = std::getenv("GNSSCORR_ACQ_TS_FILE"))
-                                {
-                                    if (FILE* f = std::fopen(tf, "wb"))
-                                        {
-                                            std::fwrite(h.data(), sizeof(unsigned long long), h.size(), f);
-                                            std::fclose(f);
-                                        }
-                                }
-                            std::fprintf(stderr, "rows3 stamps (10 ns ticks, mean over %d workgroups): inputs+stage1 %.0f | barrier1 %.0f | stage2 %.0f | stage3 to stores %.0f | stores issue %.0f | last barrier %.0f ; kernel span %.0f\n",
-                                g.n_groups, sum[0] / g.n_groups, sum[1] / g.n_groups, sum[2] / g.n_groups, sum[3] / g.n_groups, sum[4] / g.n_groups, sum[5] / g.n_groups, (double)(tmax - tmin));
-                        }
-                    return el;
-                }
-#endif
+            std::fprintf(stderr, "rows3 stamps (10 ns ticks, mean over %d workgroups): inputs+stage1 %.0f | barrier1 %.0f | stage2 %.0f | stage3 to stores %.0f | stores issue %.0f | last barrier %.0f ; kernel span %.0f\n",
+                g.n_groups, sum[0] / g.n_groups, sum[1] / g.n_groups, sum[2] / g.n_groups, sum[3] / g.n_groups, sum[4] / g.n_groups, sum[5] / g.n_groups, (double)(tmax - tmin));
+        }
+    return el;
+}
+
+// TIMING EXPERIMENT ($GNSSCORR_ACQ_DBG & 32): a columns-first mock in place of the two-dwell column pass.  As many transforms as the
+// real pass (2 per cell), but writing 8N each: the buffer must hold operands + results; the mock keeps to the first 400 transforms'
+// worth of space by wrapping the result slot (slot index modulo what fits behind the operands)
+static hipError_t launch_cols_first_mock(hipStream_t st, const AcqFftPlan& plan, int n_cells, const float2* Q, const AcqMagArgs& m)
+{
+    const int n_sats = n_cells / m.n_bins, n_spectra = 2 * m.n_bins;
+    hipLaunchKernelGGL(acq_cols_first_mock_kernel, dim3(acq_cols_blocks(plan), (unsigned)(2 * n_cells - n_spectra - n_sats - 1)), dim3(ACQ_THREADS), 0, st, plan,
+        const_cast<float2*>(Q), n_sats, n_spectra);
+    return hipGetLastError();
+}
+#endif  // ACQ_ROWS3_DBG
+
 #if ACQ_ROWS3_THREADS != 256
-            if (fn == (inverse ? reinterpret_cast<AcqRows2Fn>(&acq_rows3_kernel<true>) : reinterpret_cast<AcqRows2Fn>(&acq_rows3_kernel<false>)))
-                {
-                    g.rpw *= ACQ_ROWS3_THREADS / 256;
-                    g.n_groups = (g.n_rows + g.rpw - 1) / g.rpw;
-                    const dim3 grid3((unsigned)((g.n_groups + 7) / 8 * 8));
-                    const size_t lds3 = (size_t)g.rpw * plan.N2 * sizeof(float2);
-                    static bool attr_set[2] = {false, false};
-                    if (!attr_set[inverse ? 1 : 0])
-                        {
-                            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
-                            if (ea != hipSuccess) return ea;
-                            attr_set[inverse ? 1 : 0] = true;
-                        }
-                    return hipLaunchKernel(reinterpret_cast<const void*>(fn), grid3, dim3(ACQ_ROWS3_THREADS), args, lds3, st);
-                }
-#endif
-            return hipLaunchKernel(reinterpret_cast<const void*>(fn), grid2, dim3(ACQ_THREADS), args, lds2, st);
+// the planar pair kernel built for wider workgroups: as many more rows per workgroup, and the LDS they need
+static hipError_t launch_rows3_wide(AcqRows2Fn fn, bool inverse, const AcqFftPlan& plan, AcqRows2Args& g, void** args, hipStream_t st)
+{
+    g.rpw *= ACQ_ROWS3_THREADS / 256;
+    g.n_groups = (g.n_rows + g.rpw - 1) / g.rpw;
+    const dim3 grid3((unsigned)((g.n_groups + 7) / 8 * 8));
+    const size_t lds3 = (size_t)g.rpw * plan.N2 * sizeof(float2);
+    static bool attr_set[2] = {false, false};
+    if (!attr_set[inverse ? 1 : 0])
+        {
+            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);
+            if (ea != hipSuccess) return ea;
+            attr_set[inverse ? 1 : 0] = true;
         }
+    return hipLaunchKernel(reinterpret_cast<const void*>(fn), grid3, dim3(ACQ_ROWS3_THREADS), args, lds3, st);
+}
+#endif
+
+// the general row kernel: a row per workgroup, any radix, any cell numbering
+static hipError_t launch_rows_general(hipStream_t st, bool inverse, const AcqFftPlan& plan, int n_cells, const float2* A, AcqCellMap mapA, const float2* B,
+    AcqCellMap mapB, float2* Q, const float2* wN2, const float2* wN)
+{
     dim3 grid(plan.N1, n_cells);
     size_t lds = acq_rows_lds_bytes(plan);
     if (lds > 64 * 1024)
@@ -2574,12 +2485,7 @@ hipError_t acq_launch_rows(hipStream_t st, bool inverse, const AcqFftPlan& plan,
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (ea != hipSuccess) return ea;
         }
-    static const int row_threads = [] {
-        const char* e = gc_exp_env("GNSSCORR_ACQ_ROW_THREADS");
-        int v = e ? std::atoi(e) : 0;
-        return (v == 64 || v == 128 || v == 256) ? v : 0;
-    }();
-    const int nthr = row_threads ? row_threads : ACQ_THREADS;
+    const int nthr = acq_row_knobs().row_threads ? acq_row_knobs().row_threads : ACQ_THREADS;
     if (inverse)
         hipLaunchKernelGGL(acq_rows_kernel<true>, grid, dim3(nthr), lds, st, plan, A, mapA, B, mapB, Q, wN2, wN);
     else
@@ -2587,41 +2493,55 @@ hipError_t acq_launch_rows(hipStream_t st, bool inverse, const AcqFftPlan& plan,
     return hipGetLastError();
 }
 
-template <int N1>
-static hipError_t launch_cols_n1(hipStream_t st, bool inverse, int epilogue, const AcqFftPlan& plan, dim3 grid,
-    const float2* Q, float2* out, const AcqMagArgs& mag)
+hipError_t acq_launch_rows(hipStream_t st, bool inverse, const AcqFftPlan& plan, const AcqRowsPlan& rows, int n_cells,
+    const float2* A, AcqCellMap mapA, const float2* B, AcqCellMap mapB,
+    float2* Q, const float2* wN2, const float2* wN)
 {
-#define LAUNCH(INV, EPI) \
-    hipLaunchKernelGGL((acq_cols_kernel<N1, INV, EPI>), grid, dim3(ACQ_THREADS), 0, st, plan, Q, out, mag)
-    if (inverse)
-        {
-            switch (epilogue)
-                {
-                case ACQ_EPI_COMPLEX: LAUNCH(true, ACQ_EPI_COMPLEX); break;
-                case ACQ_EPI_MAG: LAUNCH(true, ACQ_EPI_MAG); break;
-                case ACQ_EPI_MAG_ACC: LAUNCH(true, ACQ_EPI_MAG_ACC); break;
-                case ACQ_EPI_MAG2: LAUNCH(true, ACQ_EPI_MAG2); break;
-                case ACQ_EPI_MAG2_ACC: LAUNCH(true, ACQ_EPI_MAG2_ACC); break;
-                case ACQ_EPI_PMAX: LAUNCH(true, ACQ_EPI_PMAX); break;
-                case ACQ_EPI_PMAX_ACC: LAUNCH(true, ACQ_EPI_PMAX_ACC); break;
-                case ACQ_EPI_PSUM: LAUNCH(true, ACQ_EPI_PSUM); break;
-                case ACQ_EPI_PSUM_ACC: LAUNCH(true, ACQ_EPI_PSUM_ACC); break;
-                default: return hipErrorInvalidValue;
-                }
-        }
-    else
-        {
-            switch (epilogue)
-                {
-                case ACQ_EPI_COMPLEX: LAUNCH(false, ACQ_EPI_COMPLEX); break;
-                case ACQ_EPI_PERM: LAUNCH(false, ACQ_EPI_PERM); break;
-                case ACQ_EPI_COMPLEX_CONJ_PERM: LAUNCH(false, ACQ_EPI_COMPLEX_CONJ_PERM); break;
-                default: return hipErrorInvalidValue;
-                }
-        }
-#undef LAUNCH
-    return hipGetLastError();
+    const AcqRowKnobs& k = acq_row_knobs();
+    // the packed kernel understands the engine's cell numbering only: cell = sat * n_bins + bin
+    const bool cell_layout_ok = mapA.div == 1 && n_cells % mapA.mod == 0 && (B == nullptr ? n_cells == mapA.mod : (mapB.div == mapA.mod && mapB.mod >= (1 << 30)));
+    if (rows.entry < 0 || !cell_layout_ok || k.force_wg) return launch_rows_general(st, inverse, plan, n_cells, A, mapA, B, mapB, Q, wN2, wN);
+    const bool pairs = rows.entry == ACQ_ROWS2_PAIR_ENTRY;
+    AcqRows2Fn fn = (pairs && !k.no_pairs ? acq_rows2_pair_fns : acq_rows2_fns[rows.entry])[inverse];
+#ifdef GNSSCORR_EXPERIMENTS
+    if (pairs && k.interleaved_pairs)
+        fn = inverse ? reinterpret_cast<AcqRows2Fn>(&acq_rows2p_kernel<true, 10, 10, 10>) : reinterpret_cast<AcqRows2Fn>(&acq_rows2p_kernel<false, 10, 10, 10>);
+#endif
+    AcqRows2Args g = fill_rows_args(plan, rows, n_cells, A, mapA, B, mapB, Q, wN2, wN);
+    g.dbg = k.dbg;
+    AcqFftPlan plan_arg = plan;
+    void* args[] = {&plan_arg, &g};
+    dim3 grid2((unsigned)((g.n_groups + 7) / 8 * 8));
+    const size_t lds2 = (size_t)g.rpw * plan.N2 * sizeof(float2);
+    if (k.persist > 0 && fn == acq_rows2_pair_fns[inverse] && grid2.x > (unsigned)(k.persist * 256)) grid2.x = (unsigned)(k.persist * 256);
+#if ACQ_ROWS3_DBG
+    if ((k.dbg & 64) && inverse) return launch_rows_stamped(fn, grid2, g, args, lds2, st);
+#endif
+#if ACQ_ROWS3_THREADS != 256
+    if (fn == acq_rows2_pair_fns[inverse]) return launch_rows3_wide(fn, inverse, plan, g, args, st);
+#endif
+    return hipLaunchKernel(reinterpret_cast<const void*>(fn), grid2, dim3(ACQ_THREADS), args, lds2, st);
 }
+
+// calls f(std::integral_constant<int, N1>) for the column size of the plan; a size ACQ_N1_LIST lacks has no kernel
+template <typename F>
+static hipError_t for_cols_n1(int n1, F&& f)
+{
+    switch (n1)
+        {
+#define CASE(K) \
+    case K: return f(std::integral_constant<int, K>());
+            ACQ_N1_LIST(CASE)
+#undef CASE
+        default: return hipErrorInvalidValue;
+        }
+}
+
+// the (direction, epilogue) pairs acq_cols_kernel is instantiated for
+#define ACQ_COLS_PAIRS(X)                                                                                                                          \
+    X(false, ACQ_EPI_COMPLEX) X(false, ACQ_EPI_PERM) X(false, ACQ_EPI_COMPLEX_CONJ_PERM) X(true, ACQ_EPI_COMPLEX) X(true, ACQ_EPI_MAG)              \
+    X(true, ACQ_EPI_MAG_ACC) X(true, ACQ_EPI_MAG2) X(true, ACQ_EPI_MAG2_ACC) X(true, ACQ_EPI_PMAX) X(true, ACQ_EPI_PMAX_ACC) X(true, ACQ_EPI_PSUM) \
+    X(true, ACQ_EPI_PSUM_ACC)
 
 hipError_t acq_launch_cols(hipStream_t st, bool inverse, int epilogue, const AcqFftPlan& plan, int n_cells,
     const float2* Q, float2* out, const AcqMagArgs* mag)
@@ -2631,50 +2551,20 @@ hipError_t acq_launch_cols(hipStream_t st, bool inverse, int epilogue, const Acq
     std::memset(&m, 0, sizeof m);
     if (mag) m = *mag;
 #if ACQ_ROWS3_DBG
-    {
-        static const int dbg = [] {
-            const char* e = gc_exp_env("GNSSCORR_ACQ_DBG");
-            return e ? std::atoi(e) : 0;
-        }();
-        if ((dbg & 32) && inverse && mag && plan.N1 == 25 && (epilogue == ACQ_EPI_MAG2 || epilogue == ACQ_EPI_MAG2_ACC))
-            {
-                // as many transforms as the real pass (2 per cell), but writing 8N each: the buffer must hold operands + results; the
-                // mock keeps to the first 400 transforms' worth of space by wrapping the result slot
-                const int n_sats = n_cells / m.n_bins, n_spectra = 2 * m.n_bins;
-                const int n_tr = 2 * n_cells;
-                // results wrap inside the buffer: slot index modulo what fits behind the operands
-                (void)n_tr;
-                hipLaunchKernelGGL(acq_cols_first_mock_kernel, dim3(acq_cols_blocks(plan), (unsigned)(2 * n_cells - n_spectra - n_sats - 1)), dim3(ACQ_THREADS), 0, st, plan,
-                    const_cast<float2*>(Q), n_sats, n_spectra);
-                return hipGetLastError();
-            }
-    }
+    if ((acq_row_knobs().dbg & 32) && inverse && mag && plan.N1 == 25 && (epilogue == ACQ_EPI_MAG2 || epilogue == ACQ_EPI_MAG2_ACC))
+        return launch_cols_first_mock(st, plan, n_cells, Q, m);
 #endif
-    switch (plan.N1)
-        {
-#define CASE(K) \
-    case K: return launch_cols_n1<K>(st, inverse, epilogue, plan, grid, Q, out, m);
-            CASE(1)
-            CASE(2)
-            CASE(3)
-            CASE(4)
-            CASE(5)
-            CASE(6)
-            CASE(8)
-            CASE(9)
-            CASE(10)
-            CASE(12)
-            CASE(15)
-            CASE(16)
-            CASE(20)
-            CASE(25)
-            CASE(32)
-            CASE(40)
-            CASE(50)
-#undef CASE
-        default:
-            return hipErrorInvalidValue;
+    return for_cols_n1(plan.N1, [&](auto n1) {
+#define LAUNCH(INV, EPI)                                                                                                                 \
+    if (inverse == INV && epilogue == EPI)                                                                                               \
+        {                                                                                                                                \
+            hipLaunchKernelGGL((acq_cols_kernel<decltype(n1)::value, INV, EPI>), grid, dim3(ACQ_THREADS), 0, st, plan, Q, out, m); \
+            return hipGetLastError();                                                                                                    \
         }
+        ACQ_COLS_PAIRS(LAUNCH)
+#undef LAUNCH
+        return hipErrorInvalidValue;
+    });
 }
 
 hipError_t acq_launch_cols_tong(hipStream_t st, bool accumulate, const AcqFftPlan& plan, int n_cells, const float2* Q, const AcqMagArgs& mag,
@@ -2682,36 +2572,13 @@ hipError_t acq_launch_cols_tong(hipStream_t st, bool accumulate, const AcqFftPla
 {
     if (!frozen || !power || mag.n_bins <= 0) return hipErrorInvalidValue;
     dim3 grid(acq_cols_blocks(plan), n_cells);
-    switch (plan.N1)
-        {
-#define CASE(K)                                                                                                                          \
-    case K:                                                                                                                              \
-        if (accumulate)                                                                                                                  \
-            hipLaunchKernelGGL((acq_cols_tong_kernel<K, ACQ_EPI_TONG_ACC>), grid, dim3(ACQ_THREADS), 0, st, plan, Q, mag, frozen, power); \
-        else                                                                                                                             \
-            hipLaunchKernelGGL((acq_cols_tong_kernel<K, ACQ_EPI_TONG>), grid, dim3(ACQ_THREADS), 0, st, plan, Q, mag, frozen, power);     \
+    return for_cols_n1(plan.N1, [&](auto n1) {
+        if (accumulate)
+            hipLaunchKernelGGL((acq_cols_tong_kernel<decltype(n1)::value, ACQ_EPI_TONG_ACC>), grid, dim3(ACQ_THREADS), 0, st, plan, Q, mag, frozen, power);
+        else
+            hipLaunchKernelGGL((acq_cols_tong_kernel<decltype(n1)::value, ACQ_EPI_TONG>), grid, dim3(ACQ_THREADS), 0, st, plan, Q, mag, frozen, power);
         return hipGetLastError();
-            CASE(1)
-            CASE(2)
-            CASE(3)
-            CASE(4)
-            CASE(5)
-            CASE(6)
-            CASE(8)
-            CASE(9)
-            CASE(10)
-            CASE(12)
-            CASE(15)
-            CASE(16)
-            CASE(20)
-            CASE(25)
-            CASE(32)
-            CASE(40)
-            CASE(50)
-#undef CASE
-        default:
-            return hipErrorInvalidValue;
-        }
+    });
 }
 
 hipError_t acq_launch_wipeoff_segments(hipStream_t st, const AcqPhaseSeg* segs, const int* seg_off, float2* out, int n_bins, const AcqFftPlan& plan)

@@ -134,6 +134,7 @@ struct gc_acq
     float center_step_two = 0.0f;
     uint32_t dwell_counter = 0;
     AcqFftPlan plan{};
+    AcqRowsPlan rows{};  // the row kernel of `plan`
     int n_blocks = 0;
     // Paired engine: GC_ACQ_COMBINE_MAX / _SUM.  Every satellite slot holds TWO replicas (d_codes is [sat][2][N]); the inverse row pass
     // runs over 2 * n_bins cells per satellite -- the dwell's n_bins spectra against replica A, then the same spectra against replica B
@@ -327,6 +328,7 @@ static gc_status acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, co
     a->n_bins = z.n_bins;
     if (!acq_plan_make(&a->plan, (int)z.fft_size, 160 * 1024))  // the LDS of a CU
         return gc_fail(GC_ERR_INVALID, "gc_acq_create: fft_size %u has no supported factorisation", z.fft_size);
+    a->rows = acq_rows_plan(a->plan);
     const size_t N = z.fft_size, ns = (size_t)n_sats, cells = ns * z.n_bins_alloc;
     a->n_blocks = acq_cols_blocks(a->plan);
     AcqExperiments& x = a->exp;
@@ -335,7 +337,7 @@ static gc_status acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, co
     if (const char* e = gc_exp_env("GNSSCORR_ACQ_OVERLAP")) x.overlap = std::atoi(e) != 0;
     if (const char* e = gc_exp_env("GNSSCORR_ACQ_ROLES")) x.roles = std::atoi(e) != 0;
     if (const char* e = gc_exp_env("GNSSCORR_ACQ_ONCHIP")) x.onchip = std::atoi(e) != 0;
-    x.roles = x.roles && a->held.fuse_dwells && acq_rows_cols_fusable(a->plan);
+    x.roles = x.roles && a->held.fuse_dwells && acq_rows_cols_fusable(a->plan, a->rows);
     if (a->kind == ACQ_PAIRED || a->kind == ACQ_CAF) x.roles = x.overlap = x.onchip = false;  // the experiment launches know one replica per satellite only
     if (x.roles && n_sats > 1) x.q_stride = z.q_cells * N;  // second inter-pass buffer
     if (x.overlap && z.sats_per_batch < n_sats)
@@ -390,7 +392,7 @@ static gc_status acq_create(gc_ctx* ctx, const gc_acq_conf* conf, int n_sats, co
             GC_HIP(a->caf.d_choice.alloc(cells, true));
         }
     GC_HIP(a->d_results.alloc(ns, a->kind == ACQ_QUICKSYNC));  // the QuickSync candidate check reads its winner from here
-    GC_HIP(a->d_part_val.alloc(ns * ACQ_FINAL_PIECES * 2));
+    GC_HIP(a->d_part_val.alloc(ns * ACQ_FINAL_SPLIT * 2));
     GC_HIP(a->d_part_cnt.alloc(ns, true));
     GC_HIP(a->h_results.alloc(ns));
     a->code_set.assign(n_sats, 0);
@@ -431,7 +433,7 @@ static gc_status acq_load_padded(gc_acq* a, hipStream_t st, const std::vector<fl
     GC_HIP(hipMemcpyAsync(a->d_in, buf.data(), N * sizeof(float2), hipMemcpyHostToDevice, st));
     // FFT, conjugate (:272-273), kept in the row-permuted layout the inverse rows pass reads
     hipError_t e = acq_launch_permute(st, a->d_in, nullptr, a->d_xw, a->plan, (int)N, 1, 0, 0, 0);
-    if (e == hipSuccess) e = acq_launch_rows(st, false, a->plan, 1, a->d_xw, AcqCellMap{1, 1}, nullptr, AcqCellMap{1, 1}, a->d_Q, a->d_wN2, a->d_wN);
+    if (e == hipSuccess) e = acq_launch_rows(st, false, a->plan, a->rows, 1, a->d_xw, AcqCellMap{1, 1}, nullptr, AcqCellMap{1, 1}, a->d_Q, a->d_wN2, a->d_wN);
     if (e == hipSuccess) e = acq_launch_cols(st, false, ACQ_EPI_COMPLEX_CONJ_PERM, a->plan, 1, a->d_Q, a->d_codes + slot * N, nullptr);
     if (e != hipSuccess) return gc_fail(GC_ERR_HIP, "gc_acq_set_local_code: %s", hipGetErrorString(e));
     GC_HIP(hipStreamSynchronize(st));  // buf goes out of scope
@@ -766,7 +768,7 @@ gc_status gc_acq_set_step_two(gc_acq* a, int enable, float doppler_center_hz)
 static hipError_t acq_forward(gc_acq* a, hipStream_t st, int n_blocks)
 {
     const int n_bins = (int)a->n_bins;
-    hipError_t e = acq_launch_rows(st, false, a->plan, n_blocks * n_bins, a->d_wipe, AcqCellMap{1, n_bins}, a->d_xw, AcqCellMap{n_bins, 1 << 30},
+    hipError_t e = acq_launch_rows(st, false, a->plan, a->rows, n_blocks * n_bins, a->d_wipe, AcqCellMap{1, n_bins}, a->d_xw, AcqCellMap{n_bins, 1 << 30},
         a->d_Q, a->d_wN2, a->d_wN);
     if (e == hipSuccess) e = acq_launch_cols(st, false, ACQ_EPI_PERM, a->plan, n_blocks * n_bins, a->d_Q, a->d_X, nullptr);
     return e;
@@ -791,7 +793,7 @@ static hipError_t acq_take_block(gc_acq* a, hipStream_t st, const float2* x, boo
 // the code of slot sat * R + replica.  x_spectra is n_bins, or 2 * n_bins for a dwell pair ([sat][dwell][bin]).
 static hipError_t acq_inverse_rows(gc_acq* a, hipStream_t st, const AcqBatch& b, int R, int x_spectra, float2* Q)
 {
-    return acq_launch_rows(st, true, a->plan, b.ns * R * x_spectra, a->d_X, AcqCellMap{1, x_spectra}, a->d_codes + (size_t)b.s0 * R * a->sz.fft_size,
+    return acq_launch_rows(st, true, a->plan, a->rows, b.ns * R * x_spectra, a->d_X, AcqCellMap{1, x_spectra}, a->d_codes + (size_t)b.s0 * R * a->sz.fft_size,
         AcqCellMap{x_spectra, 1 << 30}, Q, a->d_wN2, a->d_wN);
 }
 
@@ -837,7 +839,7 @@ static bool acq_inverse_experiment(gc_acq* a, hipStream_t st, bool pair, bool ac
                 if (b.index == 0)
                     eb = acq_inverse_rows(a, st, b, 1, x_spectra, Q);
                 else
-                    eb = acq_launch_rows_cols(st, a->plan, b.ns * x_spectra, a->d_X, AcqCellMap{1, x_spectra}, a->d_codes + (size_t)b.s0 * a->sz.fft_size,
+                    eb = acq_launch_rows_cols(st, a->plan, a->rows, b.ns * x_spectra, a->d_X, AcqCellMap{1, x_spectra}, a->d_codes + (size_t)b.s0 * a->sz.fft_size,
                         AcqCellMap{x_spectra, 1 << 30}, Q, a->d_wN2, a->d_wN, epi, prev.ns * n_bins, a->d_Q + (size_t)(prev.index & 1) * x.q_stride,
                         acq_mag_args(a, prev.s0, n_bins, true, offset));
                 prev = b;
@@ -986,7 +988,7 @@ static hipError_t acq_enqueue_quicksync(gc_acq* a, const float2* x, hipStream_t 
     hipError_t e = acq_launch_input_power(st, x, L, L, a->d_power, nullptr, 0, 0);
     // x * wipeoff[bin] folded f * f times (:382-396) into the rows the forward transform reads, which then runs with no second operand
     if (e == hipSuccess) e = acq_qs_launch_fold(st, x, a->d_wipe, a->d_xw, n_bins, L, f * f, a->plan);
-    if (e == hipSuccess) e = acq_launch_rows(st, false, a->plan, n_bins, a->d_xw, AcqCellMap{1, n_bins}, nullptr, AcqCellMap{1, 1}, a->d_Q, a->d_wN2, a->d_wN);
+    if (e == hipSuccess) e = acq_launch_rows(st, false, a->plan, a->rows, n_bins, a->d_xw, AcqCellMap{1, n_bins}, nullptr, AcqCellMap{1, 1}, a->d_Q, a->d_wN2, a->d_wN);
     if (e == hipSuccess) e = acq_launch_cols(st, false, ACQ_EPI_PERM, a->plan, n_bins, a->d_Q, a->d_X, nullptr);
     // * conj(FFT_M(folded code)), IFFT_M, |.|^2 stored (:405-414); first maximum and max / M^4 / input_power (:420-422, :480)
     if (e == hipSuccess) e = acq_inverse(a, st, false, false);

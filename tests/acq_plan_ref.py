@@ -1,18 +1,17 @@
-"""The acquisition planner in Python: which kernel instances an FFT size runs (gnss-sdr-1_amd/csrc/acq_plan.h and the row-kernel
-choice of acq_launch_rows in acq_kernels.hip), and the size matrix of tests/test_acquisition_matrix_gpu.py.
+"""The acquisition planner in Python: which kernel instances an FFT size runs (gnss-sdr-1_amd/csrc/acq_plan.h: acq_plan_make and
+the row-kernel choice acq_rows_plan_make), and the size matrix of tests/test_acquisition_matrix_gpu.py.
 
-tests/test_acq_plan.py holds plan() to the compiled planner (tests/acq_plan_selftest.cpp) and guards what MATRIX covers."""
-import os
-import re
+tests/test_acq_plan.py holds plan(), row_kernel() and the two lists to the compiled planner (tests/acq_plan_selftest.cpp) and
+guards what MATRIX covers."""
 
 ACQ_THREADS = 256
 ACQ_MAX_FACTORS = 12
 LDS_LIMIT_BYTES = 160 * 1024      # gc_acq_create
 ACQ_ROWS2_POINTS = 20
 ACQ_ROWS2_LDS_BYTES = 40000
-N1_CANDIDATES = (1, 2, 3, 4, 5, 6, 8, 9, 10, 12, 15, 16, 20, 25, 32, 40, 50)  # the instantiated column sizes (CASE list of acq_launch_cols)
+N1_CANDIDATES = (1, 2, 3, 4, 5, 6, 8, 9, 10, 12, 15, 16, 20, 25, 32, 40, 50)  # the instantiated column sizes (ACQ_N1_LIST)
 
-# acq_rows2_registry: the instantiated stage lists of the packed row kernel as (radix, butterflies per thread)
+# ACQ_ROWS2_LIST: the instantiated stage lists of the packed row kernel as (radix, butterflies per thread)
 ROWS2_REGISTRY = (
     ((10, 2), (10, 2), (10, 2)),
     ((10, 1), (10, 1), (10, 1)),
@@ -85,13 +84,15 @@ def plan(n, lds_limit_bytes=LDS_LIMIT_BYTES):
     return best, n2, factor_rows(n2), cols_perm_map(best, n2, n_xblk)
 
 
-def rows2_config(n2, fac):
-    """acq_rows2_config without the tuning knob: (rows per workgroup, butterflies per thread of every stage) or None."""
+def rows2_config(n2, fac, rpw_cap=0):
+    """acq_rows2_config: (rows per workgroup, butterflies per thread of every stage) or None.  rpw_cap: the experiment build's cap."""
     if any(r not in (2, 3, 4, 5, 8, 10, 16) for r in fac):
         return None
     if n2 * 8 > 64 * 1024:
         return None
     rpw = min(max(ACQ_ROWS2_LDS_BYTES // (n2 * 8), 1), 16)
+    if rpw_cap > 0:
+        rpw = min(rpw, rpw_cap)
     while rpw >= 1:
         iters = []
         for r in fac:
@@ -108,28 +109,15 @@ def rows2_config(n2, fac):
     return None
 
 
-def row_kernel(n):
-    """The row kernel acq_launch_rows picks for FFT size n: an entry of ROWS2_REGISTRY, or GENERAL_ROWS."""
+def row_kernel(n, rpw_cap=0):
+    """The row kernel acq_rows_plan_make picks for FFT size n: an entry of ROWS2_REGISTRY, or GENERAL_ROWS."""
     _, n2, fac, _ = plan(n)
-    cfg = rows2_config(n2, fac) if len(fac) <= 4 else None
+    cfg = rows2_config(n2, fac, rpw_cap) if len(fac) <= 4 else None
     if cfg:
         stages = tuple(zip(fac, cfg[1]))
         if stages in ROWS2_REGISTRY:
             return stages
     return GENERAL_ROWS
-
-
-def registry_in_source():
-    """The stage lists as acq_kernels.hip spells them, to keep ROWS2_REGISTRY honest."""
-    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gnss-sdr-1_amd", "csrc", "acq_kernels.hip")).read()
-    body = src[src.index("static const AcqRows2Entry acq_rows2_registry[] = {"):]
-    body = body[:body.index("};")]
-    out = []
-    for line in body.splitlines():
-        m = re.match(r"\s*(?:\{\d, \{|ROWS2_ENTRY\d\()((?:R2\(\d+, \d+\)(?:, )?)+)", line)
-        if m:
-            out.append(tuple((int(a), int(b)) for a, b in re.findall(r"R2\((\d+), (\d+)\)", m.group(1))))
-    return tuple(out)
 
 
 # N1 -> (sizes stored with the plain column mapping, sizes stored with perm_map); every size at most 64000 samples

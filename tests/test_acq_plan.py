@@ -13,12 +13,25 @@ import acq_plan_ref as P
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _line(n):
+def _line(n, rpw_cap=0):
     p = P.plan(n)
     if p is None:
         return "%d none" % n
     n1, n2, fac, perm = p
-    return "%d %d %d %s %d" % (n, n1, n2, "x".join(str(r) for r in fac) or "1", int(perm))
+    rows = P.row_kernel(n, rpw_cap)
+    if rows != P.GENERAL_ROWS:
+        rows = "%s/%d" % (_stages(rows), P.rows2_config(n2, fac, rpw_cap)[0])
+    return "%d %d %d %s %d %s" % (n, n1, n2, "x".join(str(r) for r in fac) or "1", int(perm), rows)
+
+
+def _stages(stages):
+    return ",".join("%dx%d" % ri for ri in stages)
+
+
+def _run(selftest, *args):
+    out = subprocess.run([selftest] + [str(a) for a in args], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stderr
+    return out.stdout.splitlines()
 
 
 @pytest.fixture(scope="module")
@@ -31,16 +44,26 @@ def selftest(tmp_path_factory):
 
 def test_python_planner_equals_the_compiled_planner(selftest):
     """Every size of the matrix, the long-row sizes, the sizes of test_acquisition_gpu.py, and sizes around them that the planner
-    treats differently: no candidate divides (primes), nothing fits the LDS, N = 1, more stages than a plan holds."""
+    treats differently: no candidate divides (primes), nothing fits the LDS, N = 1, more stages than a plan holds; then every size
+    up to the matrix's largest.  Each line carries the row kernel and its rows per workgroup as well."""
     sizes = sorted(set(P.MATRIX_SIZES + P.LONG_ROW_SIZES + P.EXISTING_SIZES + (1, 2, 7, 1000, 10007, 20479, 20483, 10241, 512000, 512050,
         3 ** 13, 2 * 3 ** 12, 999983, 1 << 20)))
-    out = subprocess.run([selftest] + [str(n) for n in sizes], capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stderr
-    assert out.stdout.splitlines() == [_line(n) for n in sizes]
+    assert _run(selftest, *sizes) == [_line(n) for n in sizes]
+    assert _run(selftest, "--range", 1, P.MATRIX_MAX_N) == [_line(n) for n in range(1, P.MATRIX_MAX_N + 1)]
 
 
-def test_registry_data_equals_the_source():
-    assert P.registry_in_source() == P.ROWS2_REGISTRY
+def test_column_sizes_equal_the_source(selftest):
+    assert _run(selftest, "--n1") == [str(n1) for n1 in P.N1_CANDIDATES]
+
+
+def test_registry_data_equals_the_source(selftest):
+    assert _run(selftest, "--registry") == [_stages(e) for e in P.ROWS2_REGISTRY]
+
+
+def test_rows_per_workgroup_cap_selects_the_unreachable_list(selftest):
+    """Two rows of 1000 points per workgroup leave a thread one butterfly per stage: the list no uncapped size runs."""
+    assert P.row_kernel(25000, 2) == P.ROWS2_UNREACHABLE[0] == ((10, 1), (10, 1), (10, 1))
+    assert _run(selftest, "--rpw-cap", 2, 25000) == [_line(25000, 2)] == ["25000 25 1000 10x10x10 1 10x1,10x1,10x1/2"]
 
 
 def test_matrix_reaches_every_column_kernel_and_both_store_mappings():
@@ -59,7 +82,7 @@ def test_matrix_reaches_every_column_kernel_and_both_store_mappings():
 
 
 def test_matrix_reaches_every_row_kernel():
-    """Every entry of acq_rows2_registry and the general row kernel: the matrix runs all that a size up to 64000 can reach (checked
+    """Every entry of ACQ_ROWS2_LIST and the general row kernel: the matrix runs all that a size up to 64000 can reach (checked
     against all of them), LONG_ROW_SIZES the rest, but for the one list the product build cannot select."""
     reached = {P.row_kernel(n) for n in P.MATRIX_SIZES}
     assert P.GENERAL_ROWS in reached

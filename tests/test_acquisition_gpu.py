@@ -210,7 +210,7 @@ def test_cshort_input_block(gctx, oracle):
     acq.close()
 
 
-# FFT sizes of the ROW kernels: stage lists of the packed row kernel (acq_rows2_registry in acq_kernels.hip) and the general row
+# FFT sizes of the ROW kernels: stage lists of the packed row kernel (ACQ_ROWS2_LIST in acq_plan.h) and the general row
 # kernel (prime radices 11 / 31, or a stage list outside the registry).  Of the column kernel this list runs N1 = 2, 4, 5, 8, 12, 16,
 # 25, 32, 40 and 50 only, and four stage lists of the registry need other sizes: tests/test_acquisition_matrix_gpu.py walks every
 # column size, both store mappings and every reachable row kernel, and tests/test_acq_plan.py guards that it does
