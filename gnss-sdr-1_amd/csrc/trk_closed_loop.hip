@@ -13,8 +13,9 @@
 // general_work runs here: pull-in (1), wide tracking with secondary-code / preamble synchronisation (2,
 // :1601-1773), extended coherent integration (3, :1774-1826) and narrow tracking (4, :1827-1896), with the
 // data-component prompt correlator of pilot tracking (:899-910) and the high-dynamics rate smoothers (:1016-1064).
-// The device side (state, loop maths, per-period body) lives in trk_loop_device.hpp; the mixed kernel of
-// gc_trk_loop_set_mixed in trk_closed_loop_mixed.hip.
+// One engine, three kinds of kernel over one shell (trk_loop_device.hpp: state, loop maths, channel shell, period loop, launch): the
+// persistent kernel here, the mixed kernel of gc_trk_loop_set_mixed (trk_closed_loop_mixed.hip) and the GLONASS kernel of
+// gc_trk_loop_start_glonass (trk_closed_loop_glonass.hip).  Which kinds may run side by side is trk_loop_kind.h's rule.
 #include "gc_internal.h"
 #include <algorithm>
 #include <cmath>
@@ -22,6 +23,7 @@
 #include <cstdlib>
 #include "gc_stream.h"
 #include "trk_batch_plan.h"
+#include "trk_loop_kind.h"
 #include "trk_loop_device.hpp"
 #include "trk_glonass_loop_device.hpp"
 #include <cstring>
@@ -39,34 +41,9 @@ __global__ __launch_bounds__(THREADS) void trk_closed_loop_kernel(LoopChan* __re
     __shared__ gc_epoch_params s_p;
     __shared__ float2 s_corr[GC_MAX_TAPS];
     __shared__ int s_go;
-    const int ch = blockIdx.x;
-    const int tid = threadIdx.x;
-    {
-        // cooperative copy of the channel state into LDS
-        const unsigned* src = reinterpret_cast<const unsigned*>(&chans[ch]);
-        unsigned* dst = reinterpret_cast<unsigned*>(&s);
-        for (unsigned i = tid; i < sizeof(LoopChan) / 4; i += THREADS) dst[i] = src[i];
-    }
-    __syncthreads();
-    if (s.n_taps != NTAPS)
-        {
-            // a channel that has not been started (or was stopped): standby records, nothing else
-            for (int e = 0; e < n_epochs; e++)
-                {
-                    unsigned* w = reinterpret_cast<unsigned*>(&recs[(size_t)ch * n_epochs + e]);
-                    for (unsigned i = tid; i < sizeof(gc_loop_record) / 4; i += THREADS) w[i] = 0u;
-                }
-            return;
-        }
-    // samples available to this launch: the channel's buffer length, or (ring input) the stream's head
-    const unsigned long long limit = limits ? limits[ch] : s.chan.n_iq;
-    loop_periods<NTAPS, THREADS, FMT, DATA, HD>(s, s_p, s_corr, s_go, lds, &recs[(size_t)ch * n_epochs], n_epochs, lds_table_floats, limit, resident);
-    __syncthreads();
-    {
-        unsigned* dst = reinterpret_cast<unsigned*>(&chans[ch]);
-        const unsigned* src = reinterpret_cast<const unsigned*>(&s);
-        for (unsigned i = tid; i < sizeof(LoopChan) / 4; i += THREADS) dst[i] = src[i];
-    }
+    loop_channel<THREADS>(s, chans, recs, n_epochs, limits, [&] { return s.n_taps != NTAPS; }, [&](gc_loop_record* crec, unsigned long long limit) {
+        loop_periods<VemlLoopKind<NTAPS, DATA, HD>, THREADS, FMT>(s, s_p, s_corr, s_go, lds, crec, n_epochs, lds_table_floats, limit, resident);
+    });
 }
 
 #ifdef GNSSCORR_EXPERIMENTS
@@ -108,11 +85,7 @@ __global__ __launch_bounds__(64) void trk_loop_prepare_kernel(LoopChan* __restri
     __shared__ LoopChan s;
     __shared__ gc_epoch_params s_p;
     const int ch = blockIdx.x, tid = threadIdx.x;
-    {
-        const unsigned* src = reinterpret_cast<const unsigned*>(&chans[ch]);
-        unsigned* dst = reinterpret_cast<unsigned*>(&s);
-        for (unsigned i = tid; i < sizeof(LoopChan) / 4; i += 64) dst[i] = src[i];
-    }
+    loop_copy_state<64>(&s, &chans[ch]);
     __syncthreads();
     if (s.n_taps == 0) return;  // standby slot: the slice kernel writes its all-zero records
     if (tid == 0)
@@ -123,11 +96,7 @@ __global__ __launch_bounds__(64) void trk_loop_prepare_kernel(LoopChan* __restri
             prep[ch].go = go;
         }
     __syncthreads();
-    {
-        unsigned* dst = reinterpret_cast<unsigned*>(&chans[ch]);
-        const unsigned* src = reinterpret_cast<const unsigned*>(&s);
-        for (unsigned i = tid; i < sizeof(LoopChan) / 4; i += 64) dst[i] = src[i];
-    }
+    loop_copy_state<64>(&chans[ch], &s);
 }
 
 // code period `e` of every channel: blockIdx -> (channel, slice) with all slices of a channel on one XCD (they share the window)
@@ -159,11 +128,7 @@ __global__ __launch_bounds__(THREADS) void trk_closed_loop_slice_kernel(LoopChan
     if (s.n_taps != NTAPS)
         {
             // a channel that has not been started (or was stopped): standby record, written by its first slice
-            if (slice == 0)
-                {
-                    unsigned* w = reinterpret_cast<unsigned*>(rec);
-                    for (unsigned i = tid; i < sizeof(gc_loop_record) / 4; i += THREADS) w[i] = 0u;
-                }
+            if (slice == 0) loop_standby_records<THREADS>(rec, 1);
             return;
         }
     if (s_go)
@@ -197,11 +162,7 @@ __global__ __launch_bounds__(THREADS) void trk_closed_loop_slice_kernel(LoopChan
     if (!s_last) return;
     // ---- the last slice to finish: the rest of general_work for this period ----
     // (the channel state and prep[] were written by the PREVIOUS launch: visible across the kernel boundary to plain loads)
-    {
-        const unsigned* src = reinterpret_cast<const unsigned*>(&chans[ch]);
-        unsigned* dst = reinterpret_cast<unsigned*>(&s);
-        for (unsigned i = tid; i < sizeof(LoopChan) / 4; i += THREADS) dst[i] = src[i];
-    }
+    loop_copy_state<THREADS>(&s, &chans[ch]);
     __syncthreads();
     if (tid == 0)
         {
@@ -233,11 +194,7 @@ __global__ __launch_bounds__(THREADS) void trk_closed_loop_slice_kernel(LoopChan
             __hip_atomic_store(tickets + ch, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
         }
     __syncthreads();
-    {
-        unsigned* dst = reinterpret_cast<unsigned*>(&chans[ch]);
-        const unsigned* src = reinterpret_cast<const unsigned*>(&s);
-        for (unsigned i = tid; i < sizeof(LoopChan) / 4; i += THREADS) dst[i] = src[i];
-    }
+    loop_copy_state<THREADS>(&chans[ch], &s);
 }
 
 #else
@@ -265,17 +222,15 @@ struct gc_trk_loop
 {
     gc_ctx* ctx = nullptr;
     gc_ctx_ref ctx_ref;
-    int n_channels = 0, max_code_len = 0, n_taps = 0;
+    int n_channels = 0, max_code_len = 0;
+    LoopKind kind = {LOOP_VEML, 0, 0, 0};     // of the running channels, set by the start that finds no other channel running (trk_loop_kind.h)
     gc_dev_buf<LoopChan> d_chans;
     gc_dev_buf<float> d_codes;
     gc_dev_buf<float> d_data_codes;           // pilot tracking: data-component replicas, allocated on first use
     std::vector<LoopSync> sync;               // per channel (gc_trk_loop_set_sync); extend_symbols == 0: none installed
     std::vector<int> data_code_len;           // samples of the data replica uploaded for the channel (0: none)
-    int pilot = -1;                           // pilot mode of the started channels (-1: none started yet)
-    int high_dyn = 0;                         // high-dynamics mode of the started channels
     int mixed = 0;                            // gc_trk_loop_set_mixed: tap count and pilot mode per channel (the mixed kernel)
-    int glonass = 0;                          // the running channels are GLONASS channels (gc_trk_loop_start_glonass): their kernel, their state
-    gc_dev_buf<GloChan> d_glo;                // the GLONASS channels' state, allocated on first use
+    gc_dev_buf<GloChan> d_glo;                // the state of LOOP_GLONASS channels, allocated on first use
     std::vector<int> code_len;                // per channel: samples of the replica it was started with
     std::vector<char> track_pilot;            // per channel: pilot mode it was started with
     gc_dev_buf<gc_loop_record> d_recs;
@@ -316,6 +271,94 @@ static hipError_t loop_quiesce(gc_trk_loop* l)
     hipError_t e = hipStreamSynchronize(l->ctx->stream);
     if (e == hipSuccess && l->launched) e = hipEventSynchronize(l->last_launch);
     return e;
+}
+
+// The kind rule (trk_loop_kind.h) for a request on slot `ch` (-1: for no slot), with the engine's one scan of its running channels:
+// `first` is the lowest running channel (-1: none), the one a refusal names
+struct LoopAdmission
+{
+    LoopKindVerdict verdict;
+    int first;
+    bool others;  // a channel other than `ch` runs
+};
+static LoopAdmission loop_admission(const gc_trk_loop* l, int ch, const LoopKind& req)
+{
+    LoopAdmission a = {LOOP_ADMIT, -1, false};
+    for (int i = l->n_channels - 1; i >= 0; i--)
+        if (l->started[i])
+            {
+                a.first = i;
+                a.others |= i != ch;
+            }
+    a.verdict = loop_kind_admit(l->kind, l->mixed != 0, a.others, a.first >= 0, req);
+    return a;
+}
+
+// f(slot `ch` of the state buffer the engine's running channels live in): LoopChan*, or GloChan* for LOOP_GLONASS
+template <class F>
+static gc_status loop_with_slot(gc_trk_loop* l, int ch, F f)
+{
+    return l->kind.family == LOOP_GLONASS ? f(l->d_glo + ch) : f(l->d_chans + ch);
+}
+
+// a running channel keeps its state; only the input block changes (stream position restarts at 0)
+template <class State>
+static gc_status loop_rebind_input(State* d_slot, const void* dev_iq, uint64_t n_samples)
+{
+    State h;
+    GC_HIP(hipMemcpy(&h, d_slot, sizeof h, hipMemcpyDeviceToHost));
+    h.chan.iq = dev_iq;
+    h.chan.n_iq = n_samples;
+    h.chan.ring_len = 0;
+    h.pos = 0;
+    GC_HIP(hipMemcpy(d_slot, &h, sizeof h, hipMemcpyHostToDevice));
+    return GC_OK;
+}
+
+// n_taps = 0 marks the slot as standby for the kernel; the rest of the state is rewritten by the next start
+template <class State>
+static gc_status loop_mark_standby(State* d_slot)
+{
+    const int zero = 0;
+    GC_HIP(hipMemcpy(reinterpret_cast<char*>(d_slot) + offsetof(State, n_taps), &zero, sizeof zero, hipMemcpyHostToDevice));
+    return GC_OK;
+}
+
+// The slot binding of both starts, once every check has passed (the ring-window check included: a refused start leaves the engine
+// and a running slot as they were).  h carries the kind's own part of the state; this uploads the replica, fills in the slot's
+// correlator descriptor and position, does the host's bookkeeping and uploads the state to its buffer.
+template <class State>
+static gc_status loop_bind_slot(gc_trk_loop* l, int ch, State& h, State* d_slot, const float* code, int code_length, int track_pilot, uint64_t sample_counter)
+{
+    const size_t at = (size_t)ch * l->max_code_len;
+    GC_HIP(hipMemcpy(l->d_codes + at, code, sizeof(float) * code_length, hipMemcpyHostToDevice));
+    l->code_len[ch] = code_length;
+    l->track_pilot[ch] = (char)track_pilot;
+    h.chan.iq = l->iq[ch];
+    h.chan.n_iq = l->n_iq[ch];
+    h.chan.code = l->d_codes + at;
+    h.chan.code_len = code_length;
+    h.chan.code2 = track_pilot ? l->d_data_codes + at : nullptr;
+    h.chan.ring_len = l->streams[ch] ? (unsigned)l->streams[ch]->capacity : 0;
+    // ring input is addressed with absolute stream sample numbers: the channel starts where its counter says
+    h.pos = l->streams[ch] ? sample_counter : 0;
+    l->pos_host[ch] = h.pos;
+    l->pos_known[ch] = 1;
+    l->idle[ch] = 0;
+    GC_HIP(hipMemcpy(d_slot, &h, sizeof h, hipMemcpyHostToDevice));
+    return GC_OK;
+}
+
+// what gc_trk_loop_start_glonass and gc_glonass_loop_pull_in both ask of a configuration (`who`: the caller, for the message)
+static gc_status glo_conf_check(const gc_glonass_loop_conf* conf, const char* who)
+{
+    GC_REQUIRE(conf, "%s: NULL configuration", who);
+    GC_REQUIRE(conf->fs_in >= 1000.0 && conf->fs_in <= 1e9 && conf->fs_in == std::floor(conf->fs_in), "%s: fs_in must be a whole number of samples per second in 1e3..1e9", who);
+    GC_REQUIRE(conf->band_carrier_freq_hz > 0 && conf->band_carrier_freq_hz + conf->channel_offset_hz > 0, "%s: bad carrier frequency", who);
+    GC_REQUIRE(std::isfinite(conf->acq_delay_samples) && std::isfinite(conf->acq_doppler_hz) && std::fabs(conf->acq_delay_samples) <= 1e9 && std::fabs(conf->acq_doppler_hz) <= 1e6,
+        "%s: bad acquisition hand-over", who);
+    GC_REQUIRE(conf->sample_counter >= conf->acq_samplestamp_samples, "%s: sample_counter lies before acq_samplestamp_samples", who);
+    return GC_OK;
 }
 
 extern "C" {
@@ -387,8 +430,8 @@ gc_status gc_trk_loop_set_mixed(gc_trk_loop* l, int on)
 {
     GC_REQUIRE(l, "gc_trk_loop_set_mixed: NULL handle");
     std::lock_guard<std::mutex> lk(l->ctx->mtx);
-    for (int i = 0; i < l->n_channels; i++)
-        if (l->started[i]) return gc_fail(GC_ERR_STATE, "gc_trk_loop_set_mixed: channel %d is running; set the mode before any gc_trk_loop_start", i);
+    const LoopAdmission adm = loop_admission(l, -1, {LOOP_MODE, 0, 0, 0});
+    if (adm.verdict != LOOP_ADMIT) return gc_fail(GC_ERR_STATE, "gc_trk_loop_set_mixed: channel %d is running; set the mode before any gc_trk_loop_start", adm.first);
     GC_REQUIRE(!on || l->forced_slices <= 1, "gc_trk_loop_set_mixed: a mixed engine runs one workgroup per channel (gc_trk_loop_set_geometry slices %d)",
         l->forced_slices);
     l->mixed = on ? 1 : 0;
@@ -407,30 +450,9 @@ gc_status gc_trk_loop_set_input_dev(gc_trk_loop* l, int ch, const void* dev_iq, 
     l->streams[ch] = nullptr;
     l->iq[ch] = dev_iq;
     l->n_iq[ch] = n_samples;
-    if (l->started[ch])
-        {
-            // a running channel keeps its state; only the input block changes (stream position restarts at 0)
-            GC_HIP(loop_quiesce(l));
-            if (l->glonass)
-                {
-                    GloChan h;
-                    GC_HIP(hipMemcpy(&h, l->d_glo + ch, sizeof h, hipMemcpyDeviceToHost));
-                    h.chan.iq = dev_iq;
-                    h.chan.n_iq = n_samples;
-                    h.chan.ring_len = 0;
-                    h.pos = 0;
-                    GC_HIP(hipMemcpy(l->d_glo + ch, &h, sizeof h, hipMemcpyHostToDevice));
-                    return GC_OK;
-                }
-            LoopChan h;
-            GC_HIP(hipMemcpy(&h, l->d_chans + ch, sizeof h, hipMemcpyDeviceToHost));
-            h.chan.iq = dev_iq;
-            h.chan.n_iq = n_samples;
-            h.chan.ring_len = 0;
-            h.pos = 0;
-            GC_HIP(hipMemcpy(l->d_chans + ch, &h, sizeof h, hipMemcpyHostToDevice));
-        }
-    return GC_OK;
+    if (!l->started[ch]) return GC_OK;
+    GC_HIP(loop_quiesce(l));
+    return loop_with_slot(l, ch, [&](auto* d_slot) { return loop_rebind_input(d_slot, dev_iq, n_samples); });
 }
 
 gc_status gc_trk_loop_set_input_format(gc_trk_loop* l, int iq_format)
@@ -533,20 +555,6 @@ gc_status gc_trk_loop_start(gc_trk_loop* l, int ch, const gc_loop_conf* conf, co
     const int n_taps = conf->veml ? 5 : 3;
     gc_device_guard g(l->ctx->device);
     std::lock_guard<std::mutex> lk(l->ctx->mtx);
-    if (l->glonass)
-        {
-            // the running channels of an engine are all of one kind: free again once every GLONASS channel has been stopped
-            for (int i = 0; i < l->n_channels; i++)
-                if (l->started[i]) return gc_fail(GC_ERR_STATE, "gc_trk_loop_start: channel %d runs as a GLONASS channel (gc_trk_loop_start_glonass); stop it first", i);
-            l->glonass = 0;
-        }
-    if (!l->mixed)
-        {
-            // the engine's tap count is that of its running channels: it is free again once every channel has been stopped
-            bool any_started = false;
-            for (int i = 0; i < l->n_channels; i++) any_started |= (i != ch && l->started[i]);
-            GC_REQUIRE(!any_started || l->n_taps == n_taps, "gc_trk_loop_start: all channels of one loop engine use the same tap count (%d)", l->n_taps);
-        }
     LoopSync y = l->sync[ch];
     if (y.extend_symbols == 0)
         {
@@ -554,44 +562,28 @@ gc_status gc_trk_loop_start(gc_trk_loop* l, int ch, const gc_loop_conf* conf, co
             y.extend_symbols = 1;
             y.symbols_per_bit = 2;
         }
+    // the running channels of an engine are of one kind (trk_loop_kind.h): it is free again once every channel has been stopped
+    const LoopKind req = {LOOP_VEML, n_taps, y.track_pilot, conf->high_dyn_smoother_length > 0 ? 1 : 0};
+    const LoopAdmission adm = loop_admission(l, ch, req);
+    if (adm.verdict == LOOP_REFUSE_GLONASS_RUNS)
+        return gc_fail(GC_ERR_STATE, "gc_trk_loop_start: channel %d runs as a GLONASS channel (gc_trk_loop_start_glonass); stop it first", adm.first);
+    GC_REQUIRE(adm.verdict != LOOP_REFUSE_TAPS, "gc_trk_loop_start: all channels of one loop engine use the same tap count (%d)", l->kind.n_taps);
     if (y.track_pilot)
         GC_REQUIRE(l->data_code_len[ch] == code_length, "gc_trk_loop_start: the data replica has %d samples, the tracking replica %d", l->data_code_len[ch],
             code_length);
-    {
-        bool others_started = false;
-        for (int i = 0; i < l->n_channels; i++) others_started |= (i != ch && l->started[i]);
-        if (!others_started) l->pilot = -1;
-    }
-    const int hd = conf->high_dyn_smoother_length > 0 ? 1 : 0;
-    if (l->pilot < 0)
-        {
-            l->pilot = y.track_pilot;
-            l->high_dyn = hd;
-        }
-    GC_REQUIRE(l->mixed || l->pilot == y.track_pilot, "gc_trk_loop_start: all channels of one loop engine share the pilot mode (track_pilot = %d)", l->pilot);
-    GC_REQUIRE(l->high_dyn == hd, "gc_trk_loop_start: all channels of one loop engine share the high_dyn mode (%d)", l->high_dyn);
+    GC_REQUIRE(adm.verdict != LOOP_REFUSE_PILOT, "gc_trk_loop_start: all channels of one loop engine share the pilot mode (track_pilot = %d)", l->kind.pilot);
+    GC_REQUIRE(adm.verdict != LOOP_REFUSE_HIGH_DYN, "gc_trk_loop_start: all channels of one loop engine share the high_dyn mode (%d)", l->kind.high_dyn);
+    if (gc_stream* r = l->streams[ch])
+        GC_REQUIRE(conf->vector_length <= r->mirror, "gc_trk_loop_start: vector_length %u exceeds the stream's max_window %llu", conf->vector_length,
+            (unsigned long long)r->mirror);
 
+    // every check has passed: from here on the engine and the slot change
     hipStream_t st = l->ctx->stream;
     GC_HIP(loop_quiesce(l));
-    l->n_taps = n_taps;  // every check has passed
-    l->code_len[ch] = code_length;
-    l->track_pilot[ch] = (char)y.track_pilot;
-    GC_HIP(hipMemcpy(l->d_codes + (size_t)ch * l->max_code_len, code, sizeof(float) * code_length, hipMemcpyHostToDevice));
     LoopChan h;
     std::memset(&h, 0, sizeof h);
     h.conf = *conf;
     h.sync = y;
-    h.chan.code2 = y.track_pilot ? l->d_data_codes + (size_t)ch * l->max_code_len : nullptr;
-    h.chan.iq = l->iq[ch];
-    h.chan.n_iq = l->n_iq[ch];
-    h.chan.code = l->d_codes + (size_t)ch * l->max_code_len;
-    h.chan.code_len = code_length;
-    if (gc_stream* r = l->streams[ch])
-        {
-            GC_REQUIRE(conf->vector_length <= r->mirror, "gc_trk_loop_start: vector_length %u exceeds the stream's max_window %llu", conf->vector_length,
-                (unsigned long long)r->mirror);
-            h.chan.ring_len = (unsigned)r->capacity;
-        }
     h.n_taps = n_taps;
     // tap shifts in code samples (dll_pll_veml_tracking.cc:372-390, :720-732)
     const float spc = (float)conf->code_samples_per_chip;
@@ -609,15 +601,12 @@ gc_status gc_trk_loop_start(gc_trk_loop* l, int ch, const gc_loop_conf* conf, co
             h.chan.shifts[1] = 0.0f;
             h.chan.shifts[2] = conf->early_late_space_chips * spc;
         }
-    // ring input is addressed with absolute stream sample numbers: the channel starts where its counter says
-    h.pos = l->streams[ch] ? conf->sample_counter : 0;
-    l->pos_host[ch] = h.pos;
-    l->pos_known[ch] = 1;
-    l->idle[ch] = 0;
-    GC_HIP(hipMemcpy(l->d_chans + ch, &h, sizeof h, hipMemcpyHostToDevice));
+    const gc_status bs = loop_bind_slot(l, ch, h, l->d_chans + ch, code, code_length, y.track_pilot, conf->sample_counter);
+    if (bs != GC_OK) return bs;
     hipLaunchKernelGGL(trk_loop_start_kernel, dim3(1), dim3(64), 0, st, l->d_chans, ch);
     GC_HIP(hipGetLastError());
     GC_HIP(hipStreamSynchronize(st));
+    if (!adm.others) l->kind = req;  // the engine's kind changes together with its only running channel
     l->started[ch] = 1;
     return GC_OK;
 }
@@ -632,14 +621,9 @@ extern "C" gc_status gc_trk_loop_stop(gc_trk_loop* l, int ch)
     std::lock_guard<std::mutex> lk(l->ctx->mtx);
     if (!l->started[ch]) return GC_OK;
     GC_HIP(loop_quiesce(l));
-    // n_taps = 0 marks the slot as standby for the kernel; the rest of the state is rewritten by the next start
-    int zero = 0;
-    if (l->glonass)
-        GC_HIP(hipMemcpy(reinterpret_cast<char*>(l->d_glo + ch) + offsetof(GloChan, n_taps), &zero, sizeof zero, hipMemcpyHostToDevice));
-    else
-        GC_HIP(hipMemcpy(reinterpret_cast<char*>(l->d_chans + ch) + offsetof(LoopChan, n_taps), &zero, sizeof zero, hipMemcpyHostToDevice));
-    l->started[ch] = 0;
-    return GC_OK;
+    const gc_status s = loop_with_slot(l, ch, [](auto* d_slot) { return loop_mark_standby(d_slot); });
+    if (s == GC_OK) l->started[ch] = 0;
+    return s;
 }
 
 extern "C" size_t gc_glonass_loop_conf_size(void) { return sizeof(gc_glonass_loop_conf); }
@@ -648,16 +632,12 @@ extern "C" size_t gc_glonass_loop_conf_size(void) { return sizeof(gc_glonass_loo
 // a device -- the configuration first (it needs no handle), then the handle and the engine's state
 extern "C" gc_status gc_trk_loop_start_glonass(gc_trk_loop* l, int ch, const gc_glonass_loop_conf* conf)
 {
-    GC_REQUIRE(conf, "gc_trk_loop_start_glonass: NULL configuration");
-    GC_REQUIRE(conf->fs_in >= 1000.0 && conf->fs_in <= 1e9 && conf->fs_in == std::floor(conf->fs_in), "gc_trk_loop_start_glonass: fs_in must be a whole number of samples per second in 1e3..1e9");
+    const gc_status cc = glo_conf_check(conf, "gc_trk_loop_start_glonass");
+    if (cc != GC_OK) return cc;
     GC_REQUIRE(conf->vector_length >= 1 && conf->vector_length <= (1u << 24), "gc_trk_loop_start_glonass: vector_length must be in 1..2^24");
-    GC_REQUIRE(conf->band_carrier_freq_hz > 0 && conf->band_carrier_freq_hz + conf->channel_offset_hz > 0, "gc_trk_loop_start_glonass: bad carrier frequency");
     GC_REQUIRE(conf->cn0_samples >= 1 && conf->cn0_samples <= LOOP_MAX_CN0, "gc_trk_loop_start_glonass: cn0_samples must be in 1..%d", LOOP_MAX_CN0);
     GC_REQUIRE(conf->pll_bw_hz > 0 && conf->dll_bw_hz > 0, "gc_trk_loop_start_glonass: loop bandwidths must be > 0");
     GC_REQUIRE(conf->early_late_space_chips > 0 && conf->early_late_space_chips <= 16.0f, "gc_trk_loop_start_glonass: early_late_space_chips must be in (0, 16]");
-    GC_REQUIRE(std::isfinite(conf->acq_delay_samples) && std::isfinite(conf->acq_doppler_hz) && std::fabs(conf->acq_delay_samples) <= 1e9 && std::fabs(conf->acq_doppler_hz) <= 1e6,
-        "gc_trk_loop_start_glonass: bad acquisition hand-over");
-    GC_REQUIRE(conf->sample_counter >= conf->acq_samplestamp_samples, "gc_trk_loop_start_glonass: sample_counter lies before acq_samplestamp_samples");
     GloChan h;
     std::memset(&h, 0, sizeof h);
     h.conf = *conf;
@@ -671,16 +651,15 @@ extern "C" gc_status gc_trk_loop_start_glonass(gc_trk_loop* l, int ch, const gc_
     GC_REQUIRE(l->iq[ch] != nullptr, "gc_trk_loop_start_glonass: channel %d has no input (gc_trk_loop_set_input_dev)", ch);
     gc_device_guard g(l->ctx->device);
     std::lock_guard<std::mutex> lk(l->ctx->mtx);
-    if (l->mixed) return gc_fail(GC_ERR_STATE, "gc_trk_loop_start_glonass: a mixed engine (gc_trk_loop_set_mixed) has no GLONASS slots; run a GLONASS engine beside it");
-    if (!l->glonass)
-        for (int i = 0; i < l->n_channels; i++)
-            if (l->started[i]) return gc_fail(GC_ERR_STATE, "gc_trk_loop_start_glonass: channel %d runs as a veml channel (gc_trk_loop_start); stop it first", i);
+    const LoopKind req = {LOOP_GLONASS, 3, 0, 0};
+    const LoopAdmission adm = loop_admission(l, ch, req);
+    if (adm.verdict == LOOP_REFUSE_MIXED_GLONASS)
+        return gc_fail(GC_ERR_STATE, "gc_trk_loop_start_glonass: a mixed engine (gc_trk_loop_set_mixed) has no GLONASS slots; run a GLONASS engine beside it");
+    if (adm.verdict != LOOP_ADMIT)
+        return gc_fail(GC_ERR_STATE, "gc_trk_loop_start_glonass: channel %d runs as a veml channel (gc_trk_loop_start); stop it first", adm.first);
     if (gc_stream* r = l->streams[ch])
-        {
-            GC_REQUIRE(2ull * conf->vector_length <= r->mirror, "gc_trk_loop_start_glonass: 2 * vector_length (%u) exceeds the stream's max_window %llu", conf->vector_length,
-                (unsigned long long)r->mirror);
-            h.chan.ring_len = (unsigned)r->capacity;
-        }
+        GC_REQUIRE(2ull * conf->vector_length <= r->mirror, "gc_trk_loop_start_glonass: 2 * vector_length (%u) exceeds the stream's max_window %llu", conf->vector_length,
+            (unsigned long long)r->mirror);
     float chips[GLO_CODE_LENGTH];
     const gc_status cs = gc_glonass_l1_ca_code_gen_float(chips, 0);
     if (cs != GC_OK) return cs;
@@ -690,24 +669,13 @@ extern "C" gc_status gc_trk_loop_start_glonass(gc_trk_loop* l, int ch, const gc_
             GC_HIP(l->d_glo.alloc(l->n_channels));
             GC_HIP(hipMemset(l->d_glo, 0, sizeof(GloChan) * l->n_channels));
         }
-    l->code_len[ch] = GLO_CODE_LENGTH;
-    l->track_pilot[ch] = 0;
-    GC_HIP(hipMemcpy(l->d_codes + (size_t)ch * l->max_code_len, chips, sizeof chips, hipMemcpyHostToDevice));
-    h.chan.iq = l->iq[ch];
-    h.chan.n_iq = l->n_iq[ch];
-    h.chan.code = l->d_codes + (size_t)ch * l->max_code_len;
-    h.chan.code_len = GLO_CODE_LENGTH;
     h.chan.shifts[0] = -conf->early_late_space_chips;
     h.chan.shifts[1] = 0.0f;
     h.chan.shifts[2] = conf->early_late_space_chips;
     h.n_taps = 3;
-    // ring input is addressed with absolute stream sample numbers: the channel starts where its counter says
-    h.pos = l->streams[ch] ? conf->sample_counter : 0;
-    l->pos_host[ch] = h.pos;
-    l->pos_known[ch] = 1;
-    l->idle[ch] = 0;
-    GC_HIP(hipMemcpy(l->d_glo + ch, &h, sizeof h, hipMemcpyHostToDevice));
-    l->glonass = 1;  // nothing can fail any more: the engine's kind changes together with its first running channel
+    const gc_status bs = loop_bind_slot(l, ch, h, l->d_glo + ch, chips, GLO_CODE_LENGTH, 0, conf->sample_counter);
+    if (bs != GC_OK) return bs;
+    l->kind = req;  // the engine's kind changes together with its first running channel
     l->started[ch] = 1;
     return GC_OK;
 }
@@ -715,12 +683,8 @@ extern "C" gc_status gc_trk_loop_start_glonass(gc_trk_loop* l, int ch, const gc_
 // the pull-in alignment of a start with `conf`, on the host: glo_loop_start and glo_loop_pull_in, the statements the kernel runs
 extern "C" gc_status gc_glonass_loop_pull_in(const gc_glonass_loop_conf* conf, int32_t* samples_offset, uint64_t* sample_counter, double* acc_carrier_phase_rad)
 {
-    GC_REQUIRE(conf, "gc_glonass_loop_pull_in: NULL configuration");
-    GC_REQUIRE(conf->fs_in >= 1000.0 && conf->fs_in <= 1e9 && conf->fs_in == std::floor(conf->fs_in), "gc_glonass_loop_pull_in: fs_in must be a whole number of samples per second in 1e3..1e9");
-    GC_REQUIRE(conf->band_carrier_freq_hz > 0 && conf->band_carrier_freq_hz + conf->channel_offset_hz > 0, "gc_glonass_loop_pull_in: bad carrier frequency");
-    GC_REQUIRE(std::isfinite(conf->acq_delay_samples) && std::isfinite(conf->acq_doppler_hz) && std::fabs(conf->acq_delay_samples) <= 1e9 && std::fabs(conf->acq_doppler_hz) <= 1e6,
-        "gc_glonass_loop_pull_in: bad acquisition hand-over");
-    GC_REQUIRE(conf->sample_counter >= conf->acq_samplestamp_samples, "gc_glonass_loop_pull_in: sample_counter lies before acq_samplestamp_samples");
+    const gc_status cc = glo_conf_check(conf, "gc_glonass_loop_pull_in");
+    if (cc != GC_OK) return cc;
     GloChan h;
     std::memset(&h, 0, sizeof h);
     h.conf = *conf;
@@ -734,47 +698,29 @@ extern "C" gc_status gc_glonass_loop_pull_in(const gc_glonass_loop_conf* conf, i
 }
 
 #ifdef GNSSCORR_EXPERIMENTS
-// one launch per code period: `n_epochs` launches of n_channels x n_slices workgroups behind one prepare launch
-template <int NT, int FM, bool DA, bool HD>
-static hipError_t loop_launch_slices_t(gc_trk_loop* l, int n_epochs, gc_loop_record* dev_records, hipStream_t st, int n_slices, int lds_table_floats,
-    const unsigned long long* limits)
+// one launch per code period: `n_epochs` launches of n_channels x n_slices workgroups behind one prepare launch.  The slices run 256
+// threads on the per-period window, whatever a.plan says: the dynamic LDS is this path's own.
+static hipError_t loop_launch_slices(gc_trk_loop* l, const LoopLaunch& a, bool pilot, int n_slices, int lds_table_floats)
 {
     constexpr int TH = 256;
     const size_t lds_bytes = (size_t)(trk_hdr_floats(TH) + lds_table_floats) * sizeof(float);
-    if (lds_bytes > 48 * 1024)
-        {
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&trk_closed_loop_slice_kernel<NT, TH, FM, DA, HD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-            if (ea != hipSuccess) return ea;
-        }
-    hipLaunchKernelGGL((trk_loop_prepare_kernel<HD>), dim3(l->n_channels), dim3(64), 0, st, l->d_chans, l->d_prep, dev_records, n_epochs, limits);
-    const unsigned grid = (unsigned)(((l->n_channels + 7) / 8) * n_slices * 8);
-    for (int e = 0; e < n_epochs; e++)
-        hipLaunchKernelGGL((trk_closed_loop_slice_kernel<NT, TH, FM, DA, HD>), dim3(grid), dim3(TH), lds_bytes, st, l->d_chans, dev_records, n_epochs, e, l->n_channels, n_slices,
-            lds_table_floats, limits, l->d_prep, l->d_slice_partial, l->d_tickets);
-    return hipGetLastError();
-}
-template <int NT, int FM>
-static hipError_t loop_launch_slices_f(gc_trk_loop* l, bool pilot, bool hd, int n_epochs, gc_loop_record* dev_records, hipStream_t st, int n_slices, int lds_table_floats,
-    const unsigned long long* limits)
-{
-    if (pilot) return hd ? loop_launch_slices_t<NT, FM, true, true>(l, n_epochs, dev_records, st, n_slices, lds_table_floats, limits)
-                         : loop_launch_slices_t<NT, FM, true, false>(l, n_epochs, dev_records, st, n_slices, lds_table_floats, limits);
-    return hd ? loop_launch_slices_t<NT, FM, false, true>(l, n_epochs, dev_records, st, n_slices, lds_table_floats, limits)
-              : loop_launch_slices_t<NT, FM, false, false>(l, n_epochs, dev_records, st, n_slices, lds_table_floats, limits);
-}
-static hipError_t loop_launch_slices(gc_trk_loop* l, bool pilot, int n_epochs, gc_loop_record* dev_records, hipStream_t st, int n_slices, int lds_table_floats,
-    const unsigned long long* limits)
-{
-    const bool hd = l->high_dyn != 0;
-    if (l->n_taps == 5)
-        {
-            if (l->iq_format == GC_IQ_I16) return loop_launch_slices_f<5, GC_IQ_I16>(l, pilot, hd, n_epochs, dev_records, st, n_slices, lds_table_floats, limits);
-            if (l->iq_format == GC_IQ_I8) return loop_launch_slices_f<5, GC_IQ_I8>(l, pilot, hd, n_epochs, dev_records, st, n_slices, lds_table_floats, limits);
-            return loop_launch_slices_f<5, GC_IQ_F32>(l, pilot, hd, n_epochs, dev_records, st, n_slices, lds_table_floats, limits);
-        }
-    if (l->iq_format == GC_IQ_I16) return loop_launch_slices_f<3, GC_IQ_I16>(l, pilot, hd, n_epochs, dev_records, st, n_slices, lds_table_floats, limits);
-    if (l->iq_format == GC_IQ_I8) return loop_launch_slices_f<3, GC_IQ_I8>(l, pilot, hd, n_epochs, dev_records, st, n_slices, lds_table_floats, limits);
-    return loop_launch_slices_f<3, GC_IQ_F32>(l, pilot, hd, n_epochs, dev_records, st, n_slices, lds_table_floats, limits);
+    const unsigned grid = (unsigned)(((a.n_channels + 7) / 8) * n_slices * 8);
+    LoopChan* d_chans = static_cast<LoopChan*>(a.d_state);
+    return loop_switch_format(l->iq_format, [&](auto fm) { return loop_switch_bool(l->kind.n_taps == 5, [&](auto veml) { return loop_switch_bool(pilot, [&](auto da) {
+        return loop_switch_bool(l->kind.high_dyn != 0, [&](auto hd) {
+            const auto kernel = trk_closed_loop_slice_kernel<veml() ? 5 : 3, TH, fm(), da(), hd()>;
+            if (lds_bytes > 48 * 1024)
+                {
+                    hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+                    if (ea != hipSuccess) return ea;
+                }
+            hipLaunchKernelGGL((trk_loop_prepare_kernel<hd()>), dim3(a.n_channels), dim3(64), 0, a.st, d_chans, l->d_prep, a.dev_records, a.n_epochs, a.limits);
+            for (int e = 0; e < a.n_epochs; e++)
+                hipLaunchKernelGGL(kernel, dim3(grid), dim3(TH), lds_bytes, a.st, d_chans, a.dev_records, a.n_epochs, e, a.n_channels, n_slices, lds_table_floats, a.limits, l->d_prep,
+                    l->d_slice_partial, l->d_tickets);
+            return hipGetLastError();
+        });
+    }); }); });
 }
 
 // slice buffers of the engine, grown on demand
@@ -792,53 +738,14 @@ static hipError_t loop_slices_reserve(gc_trk_loop* l, int n_slices, hipStream_t 
 
 #endif  // GNSSCORR_EXPERIMENTS
 
-// The persistent kernel of a plain engine: one launch of n_channels workgroups.  Each runtime axis is switched in one function
-// below -- taps, sample format, data | pilot, threads | high-dynamics -- down to the instance's launch.
-struct LoopLaunch
-{
-    LoopChan* d_chans;
-    int n_channels, n_epochs;
-    gc_loop_record* dev_records;
-    hipStream_t st;
-    TrkLoopPlan plan;
-    const unsigned long long* limits;
-};
-template <int NT, int TH, int FM, bool DA, bool HD>
-static hipError_t loop_launch_k(const LoopLaunch& a)
-{
-    if (a.plan.lds_bytes > 48 * 1024)
-        {
-            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(&trk_closed_loop_kernel<NT, TH, FM, DA, HD>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                (int)a.plan.lds_bytes);
-            if (ea != hipSuccess) return ea;
-        }
-    hipLaunchKernelGGL((trk_closed_loop_kernel<NT, TH, FM, DA, HD>), dim3(a.n_channels), dim3(TH), a.plan.lds_bytes, a.st, a.d_chans, a.dev_records, a.n_epochs,
-        a.plan.lds_table_floats, a.limits, a.plan.resident);
-    return hipGetLastError();
-}
-template <int NT, int FM, bool DA>
-static hipError_t loop_launch_t(const LoopLaunch& a, bool high_dyn)
-{
-    if (high_dyn) return loop_launch_k<NT, 256, FM, DA, true>(a);
-    if (a.plan.threads == 1024) return loop_launch_k<NT, 1024, FM, DA, false>(a);
-    if (a.plan.threads == 512) return loop_launch_k<NT, 512, FM, DA, false>(a);
-    return loop_launch_k<NT, 256, FM, DA, false>(a);
-}
-template <int NT, int FM>
-static hipError_t loop_launch_d(const LoopLaunch& a, bool pilot, bool high_dyn)
-{
-    return pilot ? loop_launch_t<NT, FM, true>(a, high_dyn) : loop_launch_t<NT, FM, false>(a, high_dyn);
-}
-template <int NT>
-static hipError_t loop_launch_f(const LoopLaunch& a, int iq_format, bool pilot, bool high_dyn)
-{
-    if (iq_format == GC_IQ_I16) return loop_launch_d<NT, GC_IQ_I16>(a, pilot, high_dyn);
-    if (iq_format == GC_IQ_I8) return loop_launch_d<NT, GC_IQ_I8>(a, pilot, high_dyn);
-    return loop_launch_d<NT, GC_IQ_F32>(a, pilot, high_dyn);
-}
+// The persistent kernel of a plain engine: sample format, threads | high-dynamics, taps and data | pilot down to the instance's launch
 static hipError_t loop_launch_plain(const LoopLaunch& a, int n_taps, int iq_format, bool pilot, bool high_dyn)
 {
-    return n_taps == 5 ? loop_launch_f<5>(a, iq_format, pilot, high_dyn) : loop_launch_f<3>(a, iq_format, pilot, high_dyn);
+    return loop_switch_format(iq_format, [&](auto fm) { return loop_switch_threads(a.plan.threads, high_dyn, [&](auto th, auto hd) {
+        return loop_switch_bool(n_taps == 5, [&](auto veml) { return loop_switch_bool(pilot, [&](auto da) {
+            return loop_launch_kernel(trk_closed_loop_kernel<veml() ? 5 : 3, th(), fm(), da(), hd()>, th(), a, a.plan.resident);
+        }); });
+    }); });
 }
 
 // Ring inputs of a launch: the distinct rings its running channels read and the floor of each -- the oldest sample a channel with
@@ -879,8 +786,6 @@ static gc_status loop_ring_floors(const gc_trk_loop* l, bool positions_known, un
     return GC_OK;
 }
 
-extern "C" {
-
 static gc_status loop_launch(gc_trk_loop* l, int n_epochs, gc_loop_record* dev_records, hipStream_t st, bool positions_known)
 {
     // channels that were never started (or were stopped) sit in standby: all-zero records, state 0
@@ -912,34 +817,27 @@ static gc_status loop_launch(gc_trk_loop* l, int n_epochs, gc_loop_record* dev_r
             if (ce != hipSuccess) return gc_fail(GC_ERR_HIP, "gc_trk_loop_run: %s", hipGetErrorString(ce));
         }
     const unsigned long long* limits = rings.any ? lim.d.get() : nullptr;
+    // a GLONASS engine: its own kernel and state; its 511-chip replica always sits in LDS as the doubled resident image
+    const bool glonass = l->kind.family == LOOP_GLONASS, pilot = l->kind.pilot > 0, high_dyn = l->kind.high_dyn != 0;
+    const TrkLoopPlan plan = trk_loop_plan(l->n_channels, l->ctx->n_cus, high_dyn, l->forced_threads, l->mixed != 0, l->started.data(), l->code_len.data(),
+        l->track_pilot.data(), glonass ? GLO_CODE_LENGTH : l->max_code_len, pilot);
+    const LoopLaunch a = {glonass ? (void*)l->d_glo.get() : (void*)l->d_chans.get(), l->n_channels, n_epochs, dev_records, st, plan, limits};
     hipError_t le;
-    if (l->glonass)
-        {
-            // a GLONASS engine: its own kernel; the 511-chip replica always sits in LDS as the doubled resident image
-            const TrkLoopPlan gp = trk_loop_plan(l->n_channels, l->ctx->n_cus, false, l->forced_threads, false, nullptr, nullptr, nullptr, GLO_CODE_LENGTH, false);
-            le = glo_loop_launch(l->d_glo, l->n_channels, l->iq_format, gp.threads, n_epochs, dev_records, st, gp.lds_table_floats, gp.lds_bytes, limits);
-        }
-    else
-        {
-            const bool pilot = l->pilot > 0;
-            const TrkLoopPlan plan = trk_loop_plan(l->n_channels, l->ctx->n_cus, l->high_dyn != 0, l->forced_threads, l->mixed != 0, l->started.data(),
-                l->code_len.data(), l->track_pilot.data(), l->max_code_len, pilot);
-            const LoopLaunch a = {l->d_chans, l->n_channels, n_epochs, dev_records, st, plan, limits};
-            // workgroups per channel-period: 1 = the persistent one-workgroup-per-channel kernel (always, in the product library); an
-            // experiments build cuts the period into slices on request (gc_trk_loop_set_geometry), one launch per period: measured slower
+    if (glonass)
+        le = glo_loop_launch(a, l->iq_format);
+    else if (l->mixed)
+        le = loop_launch_mixed(a, l->iq_format, high_dyn);
 #ifdef GNSSCORR_EXPERIMENTS
-            if (!l->mixed && l->forced_slices > 1)
-                {
-                    GC_HIP(loop_slices_reserve(l, l->forced_slices, st));
-                    le = loop_launch_slices(l, pilot, n_epochs, dev_records, st, l->forced_slices, (l->max_code_len + 64) * (pilot ? 2 : 1), limits);
-                }
-            else
-#endif
-            if (l->mixed)
-                le = loop_launch_mixed(l->d_chans, l->n_channels, l->iq_format, l->high_dyn, plan.threads, n_epochs, dev_records, st, plan.lds_table_floats, limits, plan.resident);
-            else
-                le = loop_launch_plain(a, l->n_taps, l->iq_format, pilot, l->high_dyn != 0);
+    // workgroups per channel-period: 1 = the persistent one-workgroup-per-channel kernel (always, in the product library); an
+    // experiments build cuts the period into slices on request (gc_trk_loop_set_geometry), one launch per period: measured slower
+    else if (l->forced_slices > 1)
+        {
+            GC_HIP(loop_slices_reserve(l, l->forced_slices, st));
+            le = loop_launch_slices(l, a, pilot, l->forced_slices, (l->max_code_len + 64) * (pilot ? 2 : 1));
         }
+#endif
+    else
+        le = loop_launch_plain(a, l->kind.n_taps, l->iq_format, pilot, high_dyn);
     if (le != hipSuccess) return gc_fail(GC_ERR_HIP, "gc_trk_loop_run: kernel launch failed: %s", hipGetErrorString(le));
     gc_status out = GC_OK;
     hipError_t ee = hipEventRecord(l->last_launch, st);
@@ -962,6 +860,8 @@ static gc_status loop_launch(gc_trk_loop* l, int n_epochs, gc_loop_record* dev_r
     const gc_status cs = reads.commit();
     return out != GC_OK ? out : cs;
 }
+
+extern "C" {
 
 gc_status gc_trk_loop_run_dev(gc_trk_loop* l, int n_epochs, gc_loop_record* dev_records, void* stream)
 {

@@ -156,12 +156,7 @@ static __device__ __forceinline__ int glo_loop_prepare(GloChan& s, unsigned long
             s_p.n_samples = s.current_prn_length_samples;
         }
     else
-        {
-            unsigned* w = reinterpret_cast<unsigned*>(rec);
-            for (unsigned i = 0; i < sizeof(gc_loop_record) / 4; i++) w[i] = 0u;
-            rec->state = s.state;
-            rec->sample_counter = s.sample_counter;
-        }
+        loop_invalid_record(rec, s.state, s.sample_counter);
     return go;
 }
 
@@ -258,6 +253,15 @@ static __device__ __forceinline__ void glo_loop_after_correlation(GloChan& s, co
     rec->current_prn_length_samples = new_length;
 }
 
-// the GLONASS kernel's launch (trk_closed_loop_glonass.hip) for an engine of n_channels slots
-hipError_t glo_loop_launch(GloChan* d_chans, int n_channels, int iq_format, int threads, int n_epochs, gc_loop_record* dev_records, hipStream_t st,
-    int lds_table_floats, size_t lds_bytes, const unsigned long long* limits);
+// the GLONASS loop as loop_periods takes it: E / P / L on the real replica, no data component, no rate terms
+struct GloLoopKind
+{
+    using State = GloChan;
+    static constexpr int NTAPS = 3;
+    static constexpr bool DATA = false, HD = false;
+    static __device__ __forceinline__ int prepare(GloChan& s, unsigned long long limit, gc_epoch_params& s_p, gc_loop_record* rec) { return glo_loop_prepare(s, limit, s_p, rec); }
+    static __device__ __forceinline__ void after_correlation(GloChan& s, const float2* taps, gc_loop_record* rec) { glo_loop_after_correlation(s, taps, rec); }
+};
+
+// the GLONASS kernel's launch (trk_closed_loop_glonass.hip)
+hipError_t glo_loop_launch(const LoopLaunch& a, int iq_format);

@@ -1,9 +1,12 @@
 // trk_loop_device.hpp -- the device side of the closed-loop tracking engine (trk_closed_loop.hip): the per-channel state, the
-// loop maths of general_work on one lane, and the per-period body that the persistent kernel (trk_closed_loop.hip) and the mixed
-// kernel (trk_closed_loop_mixed.hip) both run.
+// loop maths of general_work on one lane, and what the persistent kernel (trk_closed_loop.hip), the mixed kernel
+// (trk_closed_loop_mixed.hip) and the GLONASS kernel (trk_closed_loop_glonass.hip) share: the channel shell, the period loop over a
+// loop kind, and the launch.
 #pragma once
+#include <type_traits>
 #include "gc_internal.h"
 #include "trk_device.hpp"
+#include "trk_loop_plan.h"
 
 #define LOOP_MAX_CN0 64
 #ifndef LOOP_NT
@@ -482,6 +485,39 @@ static __device__ __forceinline__ void loop_write_record(const LoopChan& s, gc_l
     rec->valid = valid;
 }
 
+// ---- the pieces every kernel of the engine is built from (State: LoopChan or GloChan) ----
+// the workgroup's word-wise copy of one channel's state, global memory -> LDS or back
+template <int THREADS, class State>
+static __device__ __forceinline__ void loop_copy_state(State* to, const State* from)
+{
+    static_assert(sizeof(State) % 4 == 0, "the channel state is copied in 4-byte words");
+    const int tid = threadIdx.x;
+    const unsigned* src = reinterpret_cast<const unsigned*>(from);
+    unsigned* dst = reinterpret_cast<unsigned*>(to);
+    for (unsigned i = tid; i < sizeof(State) / 4; i += THREADS) dst[i] = src[i];
+}
+
+// a channel that has not been started (or was stopped): the workgroup writes all-zero records, standby
+template <int THREADS>
+static __device__ __forceinline__ void loop_standby_records(gc_loop_record* crec, int n_epochs)
+{
+    const int tid = threadIdx.x;
+    for (int e = 0; e < n_epochs; e++)
+        {
+            unsigned* w = reinterpret_cast<unsigned*>(&crec[e]);
+            for (unsigned i = tid; i < sizeof(gc_loop_record) / 4; i += THREADS) w[i] = 0u;
+        }
+}
+
+// nothing to correlate: an invalid record marks the epoch, by one lane (records are written in place, field by field: no stack copies)
+static __device__ __forceinline__ void loop_invalid_record(gc_loop_record* rec, int state, unsigned long long sample_counter)
+{
+    unsigned* w = reinterpret_cast<unsigned*>(rec);
+    for (unsigned i = 0; i < sizeof(gc_loop_record) / 4; i++) w[i] = 0u;
+    rec->state = state;
+    rec->sample_counter = sample_counter;
+}
+
 // everything general_work does with one code period's correlator outputs (states 2, 3, 4; :1601-1896)
 template <int NTAPS, bool DATA>
 static __device__ __forceinline__ void loop_after_correlation(LoopChan& s, const float2* taps, gc_loop_record* rec)
@@ -670,22 +706,30 @@ static __device__ __forceinline__ int loop_prepare(LoopChan& s, unsigned long lo
             s_p.n_samples = (int)c.vector_length;
         }
     else
-        {
-            // nothing to correlate: an invalid record marks the epoch (records are written in place, field by field: no stack copies)
-            unsigned* w = reinterpret_cast<unsigned*>(rec);
-            for (unsigned i = 0; i < sizeof(gc_loop_record) / 4; i++) w[i] = 0u;
-            rec->state = s.state;
-            rec->sample_counter = s.sample_counter;
-        }
+        loop_invalid_record(rec, s.state, s.sample_counter);
     return go;
 }
 
+// A kind of loop, as loop_periods takes it: the state type, the correlator's shape and the one-lane maths around it.  The veml
+// kinds are these; the GLONASS one is GloLoopKind (trk_glonass_loop_device.hpp).
+template <int NTAPS_, bool DATA_, bool HD_>
+struct VemlLoopKind
+{
+    using State = LoopChan;
+    static constexpr int NTAPS = NTAPS_;
+    static constexpr bool DATA = DATA_, HD = HD_;
+    static __device__ __forceinline__ int prepare(LoopChan& s, unsigned long long limit, gc_epoch_params& s_p, gc_loop_record* rec) { return loop_prepare<HD>(s, limit, s_p, rec); }
+    static __device__ __forceinline__ void after_correlation(LoopChan& s, const float2* taps, gc_loop_record* rec) { loop_after_correlation<NTAPS, DATA>(s, taps, rec); }
+};
+
 // The n_epochs code periods of one channel whose state `s` the workgroup holds in LDS (crec: the channel's first record): the
-// body shared by the persistent kernel (one <NTAPS, DATA> per launch) and the mixed kernel (one per channel).
-template <int NTAPS, int THREADS, int FMT, bool DATA, bool HD>
-static __device__ __forceinline__ void loop_periods(LoopChan& s, gc_epoch_params& s_p, float2* s_corr, int& s_go, float* lds, gc_loop_record* crec,
+// body shared by the persistent kernel (one kind per launch), the mixed kernel (one per channel) and the GLONASS kernel.
+template <class KIND, int THREADS, int FMT>
+static __device__ __forceinline__ void loop_periods(typename KIND::State& s, gc_epoch_params& s_p, float2* s_corr, int& s_go, float* lds, gc_loop_record* crec,
     int n_epochs, int lds_table_floats, unsigned long long limit, int resident)
 {
+    constexpr int NTAPS = KIND::NTAPS;
+    constexpr bool DATA = KIND::DATA, HD = KIND::HD;
     const int tid = threadIdx.x;
     // The replica does not change during a launch and this workgroup has the CU's LDS to itself: the doubled image
     // R[i] = code[i mod L] is loaded ONCE and every period addresses its window inside it, instead of re-reading the window from
@@ -701,7 +745,7 @@ static __device__ __forceinline__ void loop_periods(LoopChan& s, gc_epoch_params
             gc_loop_record* rec = &crec[e];
             if (tid == 0)
                 {
-                    const int go = loop_prepare<HD>(s, limit, s_p, rec);
+                    const int go = KIND::prepare(s, limit, s_p, rec);
                     s_go = go;
                 }
             __syncthreads();
@@ -711,11 +755,81 @@ static __device__ __forceinline__ void loop_periods(LoopChan& s, gc_epoch_params
             if (tid < NTAPS + (DATA ? 1 : 0)) s_corr[tid] = r;
             __syncthreads();
 
-            if (tid == 0) loop_after_correlation<NTAPS, DATA>(s, s_corr, rec);
+            if (tid == 0) KIND::after_correlation(s, s_corr, rec);
             // the next iteration's barrier orders these writes before any other thread reads s / s_p again
         }
 }
 
-// the mixed kernel's launch (trk_closed_loop_mixed.hip) for an engine of n_channels slots: `threads` per workgroup (high_dyn: 256)
-hipError_t loop_launch_mixed(LoopChan* d_chans, int n_channels, int iq_format, int high_dyn, int threads, int n_epochs, gc_loop_record* dev_records,
-    hipStream_t st, int lds_table_floats, const unsigned long long* limits, int resident);
+// One channel of a launch, the shell of the persistent, the mixed and the GLONASS kernel: the workgroup loads slot blockIdx.x into
+// `s` (LDS); a stand-by slot gets its all-zero records and nothing else; otherwise body(crec, limit) runs the periods -- crec is the
+// channel's first record, limit the samples available to this launch: the channel's buffer length, or (ring input) the stream's
+// head -- and the state goes back.  standby() is evaluated once the state is loaded.
+template <int THREADS, class State, class Standby, class Body>
+static __device__ __forceinline__ void loop_channel(State& s, State* chans, gc_loop_record* recs, int n_epochs, const unsigned long long* limits, Standby standby, Body body)
+{
+    const int ch = blockIdx.x;
+    loop_copy_state<THREADS>(&s, &chans[ch]);
+    __syncthreads();
+    gc_loop_record* crec = &recs[(size_t)ch * n_epochs];
+    if (standby())
+        {
+            loop_standby_records<THREADS>(crec, n_epochs);
+            return;
+        }
+    const unsigned long long limit = limits ? limits[ch] : s.chan.n_iq;
+    body(crec, limit);
+    __syncthreads();
+    loop_copy_state<THREADS>(&chans[ch], &s);
+}
+
+// ---- launches (host) ----
+// One launch of n_channels workgroups over the engine's state buffer; plan.lds_bytes is the launch's dynamic LDS
+struct LoopLaunch
+{
+    void* d_state;  // LoopChan or GloChan slots: the kernel's first parameter says which
+    int n_channels, n_epochs;
+    gc_loop_record* dev_records;
+    hipStream_t st;
+    TrkLoopPlan plan;
+    const unsigned long long* limits;
+};
+
+// launches `kernel` with `threads` per workgroup; extra: the kernel's parameters behind `limits`
+template <class State, class... Extra>
+static hipError_t loop_launch_kernel(void (*kernel)(State*, gc_loop_record*, int, int, const unsigned long long*, Extra...), int threads, const LoopLaunch& a, Extra... extra)
+{
+    if (a.plan.lds_bytes > 48 * 1024)
+        {
+            hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.plan.lds_bytes);
+            if (ea != hipSuccess) return ea;
+        }
+    hipLaunchKernelGGL(kernel, dim3(a.n_channels), dim3(threads), a.plan.lds_bytes, a.st, static_cast<State*>(a.d_state), a.dev_records, a.n_epochs, a.plan.lds_table_floats,
+        a.limits, extra...);
+    return hipGetLastError();
+}
+
+// The runtime axes of a launch, each switched once: f is called with the value as a std::integral_constant.
+template <class F>
+static hipError_t loop_switch_format(int iq_format, F f)
+{
+    if (iq_format == GC_IQ_I16) return f(std::integral_constant<int, GC_IQ_I16>());
+    if (iq_format == GC_IQ_I8) return f(std::integral_constant<int, GC_IQ_I8>());
+    return f(std::integral_constant<int, GC_IQ_F32>());
+}
+// f(threads, high_dyn): high-dynamics kernels always take 256 threads
+template <class F>
+static hipError_t loop_switch_threads(int threads, bool high_dyn, F f)
+{
+    if (high_dyn) return f(std::integral_constant<int, 256>(), std::true_type());
+    if (threads == 1024) return f(std::integral_constant<int, 1024>(), std::false_type());
+    if (threads == 512) return f(std::integral_constant<int, 512>(), std::false_type());
+    return f(std::integral_constant<int, 256>(), std::false_type());
+}
+template <class F>
+static hipError_t loop_switch_bool(bool on, F f)
+{
+    return on ? f(std::true_type()) : f(std::false_type());
+}
+
+// the mixed kernel's launch (trk_closed_loop_mixed.hip)
+hipError_t loop_launch_mixed(const LoopLaunch& a, int iq_format, bool high_dyn);

@@ -380,6 +380,65 @@ def test_closed_loop_standby_slots_and_stop(gctx, oracle):
     loop.close()
 
 
+def test_refused_restart_leaves_a_running_ring_channel_alone(gctx, oracle):
+    """Two identical rings, two one-channel engines, the same 3-tap GPS channel on each.  After k periods engine A is asked to restart
+    its channel with five taps, another satellite's replica and a vector_length above the ring's max_window: the start is refused,
+    and a refused start changes nothing -- A's remaining periods equal B's byte for byte.  (Before the slot binding ran behind all
+    of its checks the refusal left A launching five-tap kernels over the three-tap state, standby records, with the replica
+    overwritten.)"""
+    import gnsscorr
+    fs, n_ep, k = 4e6, 40, 15
+    code, x = _signal(oracle, 5, fs, 4000 * (n_ep + 3), 101, 1680.0, 1234.0)
+    other = oracle.gps_l1_ca_code(9).astype(np.float32)
+    conf = dict(GPS, acq_delay_samples=1234.0, acq_doppler_hz=1690.0, acq_samplestamp_samples=0, sample_counter=0)
+    rings = [gnsscorr.IqStream(gctx, 1 << 18, 4000) for _ in range(2)]  # the whole stream stays resident
+    loops = [gnsscorr.TrackingLoop(gctx, 1, 1023) for _ in range(2)]
+    first = []
+    for ring, loop in zip(rings, loops):
+        loop.set_input_stream(0, ring)
+        ring.push(x)
+        loop.start(0, _conf(gnsscorr, **conf), code)
+        first.append(loop.run(k)[0])
+    with pytest.raises(gnsscorr.GnsscorrError, match="exceeds the stream's max_window") as e:
+        loops[0].start(0, _conf(gnsscorr, **dict(conf, veml=1, very_early_late_space_chips=1.0, vector_length=4001)), other)
+    assert e.value.status == gnsscorr.GC_ERR_INVALID
+    a, b = (np.concatenate([first[i], loops[i].run(n_ep - k)[0]]) for i in range(2))
+    for loop in loops:
+        loop.close()
+    assert np.all(b["valid"] == 1) and np.all(a["valid"] == 1), np.flatnonzero(a["valid"] != 1)[:5]
+    assert a.tobytes() == b.tobytes()
+
+
+def test_rebinding_a_running_channel_continues_the_run(gctx, oracle):
+    """gc_trk_loop_set_input_dev on a running channel keeps its state and restarts its position at 0: bound to the rest of the
+    same buffer (from the sample the channel would read next) it reads the same addresses, so the records continue byte for byte
+    those of an engine that ran the same two launches without the rebind."""
+    import gnsscorr
+    import torch
+    fs, n_ep, k = 4e6, 40, 15
+    code, x = _signal(oracle, 5, fs, 4000 * (n_ep + 3), 101, 1680.0, 1234.0)
+    conf = dict(GPS, acq_delay_samples=1234.0, acq_doppler_hz=1690.0, acq_samplestamp_samples=0, sample_counter=0)
+    d = torch.from_numpy(x.view(np.float32)).cuda()
+
+    def engine():
+        loop = gnsscorr.TrackingLoop(gctx, 1, 1023)
+        loop.set_input_dev(0, d.data_ptr(), x.size)
+        loop.start(0, _conf(gnsscorr, **conf), code)
+        return loop, loop.run(k)[0]
+
+    a, a_first = engine()
+    pos = int(a_first["sample_counter"][-1]) - conf["sample_counter"]
+    assert 0 < pos < x.size
+    a.set_input_dev(0, d.data_ptr() + pos * 8, x.size - pos)
+    got = np.concatenate([a_first, a.run(n_ep - k)[0]])
+    a.close()
+    b, b_first = engine()
+    want = np.concatenate([b_first, b.run(n_ep - k)[0]])
+    b.close()
+    assert np.all(want["valid"] == 1)
+    assert got.tobytes() == want.tobytes(), np.flatnonzero(got != want)[:5]
+
+
 @pytest.mark.parametrize("order,fll_pull_in,fll_steady", [(3, 0, 0), (2, 0, 0), (3, 0, 1), (2, 1, 0), (3, 1, 0)])
 def test_device_carrier_filter_against_the_pinned_filter(gctx, oracle, order, fll_pull_in, fll_steady):
     """The device loop's copy of Tracking_FLL_PLL_filter (trk_closed_loop.hip::pll_get_carrier_error) against

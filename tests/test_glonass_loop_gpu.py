@@ -200,6 +200,35 @@ def test_ring_input_in_uneven_pushes(gctx, bench, glonass_code):
         assert g[:n].tobytes() == alone[ch][:n].tobytes(), (ch, np.flatnonzero(g[:n] != alone[ch][:n])[:5])
 
 
+def test_rebinding_a_running_channel_continues_the_run(gctx, bench):
+    """gc_trk_loop_set_input_dev on a running GLONASS channel keeps its state and restarts its position at 0: bound to the rest of
+    the same buffer (from the sample the channel would read next) it reads the same addresses, so the records continue byte for byte
+    those of an engine that ran the same two launches without the rebind."""
+    import gnsscorr
+    name, k = "2048k_L1_km1", 25
+    x, conf = bench.stream(name), R.scenario_conf(R.SCENARIOS[name])
+    d = _device_samples(x, "f32")
+
+    def engine():
+        loop = gnsscorr.TrackingLoop(gctx, 1, 511)
+        loop.set_geometry(threads_per_workgroup=1024, slices_per_channel=1)
+        loop.set_input_dev(0, d.data_ptr(), x.size)
+        loop.start_glonass(0, _conf(gnsscorr, conf))
+        return loop, loop.run(k)[0]
+
+    a, a_first = engine()
+    pos = int(a_first["sample_counter"][-1]) - conf["sample_counter"]
+    assert 0 < pos < x.size
+    a.set_input_dev(0, d.data_ptr() + pos * 8, x.size - pos)
+    got = np.concatenate([a_first, a.run(R.N_PERIODS - k)[0]])
+    a.close()
+    b, b_first = engine()
+    want = np.concatenate([b_first, b.run(R.N_PERIODS - k)[0]])
+    b.close()
+    assert np.all(want["valid"] == 1) and np.all(want["state"] == 2)
+    assert got.tobytes() == want.tobytes(), np.flatnonzero(got != want)[:5]
+
+
 GPS = dict(fs_in=4e6, signal_carrier_freq_hz=1575.42e6, code_chip_rate_hz=1.023e6, code_period_s=0.001, carrier_lock_th=0.85, code_length_chips=1023,
     code_samples_per_chip=1, vector_length=4000, pull_in_time_s=0, veml=0, pll_filter_order=3, dll_filter_order=2, enable_fll_pull_in=0,
     enable_fll_steady_state=0, cn0_samples=20, cn0_min=25, max_lock_fail=50, pll_bw_hz=40.0, dll_bw_hz=2.0, fll_bw_hz=35.0, early_late_space_chips=0.5,
