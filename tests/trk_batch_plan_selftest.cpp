@@ -5,7 +5,13 @@
 // format is the kernel's TRK_MODE_* number (0 plain, 2 high-dynamics, 3 complex chips, 4 16-bit) -- and prints `n_slices lds_floats`;
 // or `l1:N,one_wg_max,partial_slices`, which prints the slice count of a level-1 call.  CPU only; tests/test_trk_batch_plan.py holds
 // the expected lines.
+// Built with -DTRK_SELFTEST_TRAITS (and the HIP headers on the include path, for trk_kernels.h) the argument `traits` prints what
+// decides which instantiations of trk_multicorrelator_kernel a caller can reach: `max_taps GC_MAX_TAPS`, then one line per TRK_MODE_*,
+// `mode iq_formats words_per_chip out_bytes` (iq_formats: bits 1 << gc_iq_format).  tests/open_loop_matrix_cases.py reads them.
 #include "trk_batch_plan.h"
+#ifdef TRK_SELFTEST_TRAITS
+#include "trk_kernels.h"
+#endif
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -34,6 +40,15 @@ int main(int argc, char** argv)
     for (int a = 1; a < argc; a++)
         {
             char* p = argv[a];
+#ifdef TRK_SELFTEST_TRAITS
+            if (std::strcmp(p, "traits") == 0)
+                {
+                    std::printf("max_taps %d\n", GC_MAX_TAPS);
+                    for (int m = TRK_MODE_PLAIN; m <= TRK_MODE_SC16; m++)
+                        std::printf("%d %u %d %d\n", m, TRK_FORMAT_TRAITS[m].iq_formats, TRK_FORMAT_TRAITS[m].words_per_chip, TRK_FORMAT_TRAITS[m].out_bytes);
+                    continue;
+                }
+#endif
             if (std::strncmp(p, "l1:", 3) == 0)
                 {
                     const std::vector<double> v = numbers(p + 3, &p);
