@@ -70,6 +70,9 @@ static __device__ __forceinline__ void sg_satellite(const SiggenJob& job, const 
             if (r > 0)
                 {
                     u = sg_code_advance(u, inc_k, inc_f);
+                    // the step that carries the sample number itself past 2^64: U of the wrapped t is 2^64 step less, so the
+                    // closed form's period count starts again, and with it the symbols (f and theta are residues: unchanged)
+                    if (t_run + (unsigned long long)r * STRIDE < (unsigned long long)STRIDE) u.k -= sat.code_step_q;
                     theta += carr_inc;
                 }
             if (r == 0 || u.k != k_cur)

@@ -49,14 +49,15 @@ static void check_run(uint64_t phase0, uint64_t step, uint64_t carr0, uint64_t c
             const SgCodePhase c = sg_code_phase(phase0, step, t);
             CHECK(c.k == (uint64_t)(exact >> 64) && c.f == (uint64_t)exact, "closed form at t = %llu", (unsigned long long)t);
             // the run's increments give the same integers; where t itself wraps 2^64 inside the run, f and theta still do (they are
-            // residues mod 2^64) and only the period count k, whose closed form starts again, is not compared
+            // residues mod 2^64) and the period count k, whose closed form starts again, is step less: the kernel's correction
             CHECK(u.f == c.f, "increment %d of f from t = %llu, stride %u", i, (unsigned long long)t_start, stride);
             CHECK(theta == sg_carrier_phase(carr0, cstep, t), "carrier increment %d from t = %llu", i, (unsigned long long)t_start);
-            if (t >= t_start) CHECK(u.k == c.k, "increment %d of k from t = %llu, stride %u", i, (unsigned long long)t_start, stride);
+            CHECK(u.k == c.k, "increment %d of k from t = %llu, stride %u", i, (unsigned long long)t_start, stride);
             const uint32_t e = sg_table_index(c.f, table_len);
             CHECK(e < table_len, "e = %u is not below table_len %u", e, table_len);
             CHECK(e == (uint32_t)(((u128)c.f * table_len) >> 64), "table index at t = %llu", (unsigned long long)t);
-            const SgCodePhase nxt = sg_code_advance(u, inc_k, inc_f);
+            SgCodePhase nxt = sg_code_advance(u, inc_k, inc_f);
+            if (t + stride < stride) nxt.k -= step;  // t wraps 2^64 with this step
             if (nxt.k != u.k) periods_crossed++;
             u = nxt;
             theta += cstep * stride;
@@ -86,7 +87,7 @@ int main()
         "half turns");
 
     // table index at the extremes
-    const uint32_t lens[] = {1u, 2u, 511u, 1023u, 10230u, 49104u};
+    const uint32_t lens[] = {1u, 2u, 7u, 511u, 1023u, 4092u, 10230u, 49104u};
     for (uint32_t len : lens)
         {
             CHECK(sg_table_index(0, len) == 0 && sg_table_index(~0ull, len) == len - 1, "table index extremes, table_len %u", len);
@@ -100,7 +101,7 @@ int main()
             for (unsigned stride : {1u, 256u})
                 {
                     const uint64_t phase0 = next_u64(), carr0 = next_u64(), cstep = next_u64();
-                    const uint32_t len = lens[next_u64() % 6];
+                    const uint32_t len = lens[next_u64() % 8];
                     check_run(phase0, step, carr0, cstep, t0, stride, 1400, len);
                 }
     // a period wrap is really crossed by the 1/4000 step within 1400 x 256 samples, and the count of periods is exact

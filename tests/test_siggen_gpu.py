@@ -5,7 +5,8 @@ closed tracking loop with no host link in between.
 
 The parity gate, max |dev - ref| <= 1e-5 A + 2e-5 sigma with A = sum_s amplitude_s sum_c |gain_c| max |table_c|, is derived:
   signal  an angle carried as float32 turns is off by at most 2 pi 2^-24 = 3.7e-7, sincos by a few 1e-7, each product and each of
-          up to 32 accumulations by at most 2^-24 relative: under 2e-6 A in all, gated with 5x margin
+          up to 32 accumulations by at most 2^-24 relative: under 2e-6 A in all, gated with 5x margin (32 satellites are
+          actually run, with every signal kind and both axes, in tests/test_siggen_matrix_gpu.py)
   noise   r <= 5.77 with relative error near 2e-7, 2 pi u2 rounded to float32 gives 3.7e-7 x 5.77: about 4e-6 sigma, 5x margin"""
 import numpy as np
 import pytest
@@ -42,7 +43,7 @@ def _generate(gctx, scene, calls, capacity, sigma, iq_format=None, scale=None, t
     ring = gnsscorr.IqStream(gctx, capacity_samples=capacity, max_window_samples=max_window, iq_format=fmt)
     if fmt != gnsscorr.GC_IQ_F32:
         ring.accept_quantised_output()
-    gen = gnsscorr.SignalGenerator(gctx, ring, FS, scene["sats"], noise_sigma=sigma, seed=scene["seed"], t0=t0, table_placement=placement)
+    gen = gnsscorr.SignalGenerator(gctx, ring, scene.get("fs", FS), scene["sats"], noise_sigma=sigma, seed=scene["seed"], t0=t0, table_placement=placement)
     if scale is not None:
         gen.set_output_scale(scale)
     head = 0
