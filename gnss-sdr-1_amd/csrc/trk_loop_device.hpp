@@ -356,8 +356,9 @@ static __device__ __forceinline__ void loop_run_dll_pll(LoopChan& s, bool veml)
     s.carrier_doppler_hz = s.carr_error_filt_hz;
     if (veml)
         {
-            const double pe = sqrt((double)(VE.x * VE.x + VE.y * VE.y) + (double)(E.x * E.x + E.y * E.y));
-            const double pl = sqrt((double)(VL.x * VL.x + VL.y * VL.y) + (double)(L.x * L.x + L.y * L.y));
+            // std::sqrt(std::norm(VE) + std::norm(E)) on gr_complex (tracking_discriminators.cc:121-122): a float sum and a float root
+            const double pe = (double)sqrtf((VE.x * VE.x + VE.y * VE.y) + (E.x * E.x + E.y * E.y));
+            const double pl = (double)sqrtf((VL.x * VL.x + VL.y * VL.y) + (L.x * L.x + L.y * L.y));
             s.code_error_chips = (pe + pl == 0.0) ? 0.0 : (pe - pl) / (pe + pl);
         }
     else

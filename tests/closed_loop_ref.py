@@ -4,12 +4,145 @@ the checker for the device closed-loop engine (test infrastructure).
 Follows dll_pll_veml_tracking.cc: pull-in :1568-1600, do_correlation_step :886-911, cn0_and_tracking_lock_status
 :839-878, run_dll_pll :914-973, update_tracking_vars :998-1070, acquire_secondary :800-836, save_correlation_results
 :1072-1125 and the states 2 / 3 / 4 of general_work :1601-1896, with the loop filters of
-tracking_loop_filter.cc:104-245 (no last integrator) and tracking_FLL_PLL_filter.cc:55-133, float32 where the
-reference uses float."""
+tracking_loop_filter.cc:104-245 (no last integrator) and tracking_FLL_PLL_filter.cc:55-133, the discriminators of
+tracking_discriminators.cc:49-128 and the lock detectors of lock_detectors.cc:68-111, float32 where the reference uses float.
+
+The filters, the discriminators and the lock detectors are module-level so that run() and the replay of the device's own records
+(tests/test_loop_maths_gpu.py) use the same code; tests/test_loop_filter_pin.py holds them to the reference's files compiled in
+oracle/_ref.  `move` arguments shift a libm result by that many ulp of its own type (np.nextafter): the replay's gate on the
+device's libm."""
 import numpy as np
 
 PI_2 = 6.283185307179586
 f32 = np.float32
+
+
+def moved(v, n):
+    """The float32 / float64 scalar v, n ulp up (n > 0) or down."""
+    to = type(v)(np.inf if n > 0 else -np.inf)
+    for _ in range(abs(int(n))):
+        v = np.nextafter(v, to)
+    return v
+
+
+# ---- discriminators (tracking_discriminators.cc): complex64 in, double out, radians / chips ----
+def fll_four_quadrant_atan(p1, p2, t1, t2, move=0):
+    """dot and cross are float expressions assigned to doubles; the atan2 is double (:49-55)."""
+    a, b, c, d = f32(p1.real), f32(p1.imag), f32(p2.real), f32(p2.imag)
+    with np.errstate(all="ignore"):
+        dot = np.float64(f32(f32(a * c) + f32(b * d)))
+        cross = np.float64(f32(f32(a * d) - f32(c * b)))
+        return float(moved(np.arctan2(cross, dot), move)) / (t2 - t1)
+
+
+def pll_four_quadrant_atan(p, move=0):
+    """float atan2 (:65-68): the double atan2 rounded to float.  (numpy's own float32 arctan2 is 2 ulp from glibc's, which is
+    correctly rounded, on about 1 input in 200.)"""
+    return float(moved(f32(np.arctan2(np.float64(f32(p.imag)), np.float64(f32(p.real)))), move))
+
+
+def pll_cloop_two_quadrant_atan(p, move=0):
+    """float division and float atan (:78-85): the double atan rounded to float, as above."""
+    if f32(p.real) != 0:
+        with np.errstate(all="ignore"):
+            return float(moved(f32(np.arctan(np.float64(f32(f32(p.imag) / f32(p.real))))), move))
+    return 0.0
+
+
+def dll_nc_e_minus_l_normalized(e, l, move=(0, 0)):
+    """std::abs(gr_complex) is a float hypot (:96-106): np.hypot on float32, which is libm's (np.abs of a complex64 is numpy's own
+    and 1 ulp away on half the inputs); move: ulp shifts of the two moduli."""
+    with np.errstate(all="ignore"):
+        pe = float(moved(np.hypot(f32(e.real), f32(e.imag)), move[0]))
+        pl = float(moved(np.hypot(f32(l.real), f32(l.imag)), move[1]))
+        if pe + pl == 0.0:
+            return 0.0
+        return float(np.float64(0.5 * (pe - pl)) / np.float64(pe + pl))
+
+
+def _norm(v):
+    re, im = f32(v.real), f32(v.imag)
+    return f32(f32(re * re) + f32(im * im))
+
+
+def dll_nc_vemlp_normalized(ve, e, l, vl):
+    """std::sqrt(std::norm(VE) + std::norm(E)) on gr_complex: a float sum and a float root, widened afterwards (:118-128)."""
+    with np.errstate(all="ignore"):
+        pe = float(np.sqrt(f32(_norm(ve) + _norm(e))))
+        pl = float(np.sqrt(f32(_norm(vl) + _norm(l))))
+        if pe + pl == 0.0:
+            return 0.0
+        return float(np.float64(pe - pl) / np.float64(pe + pl))
+
+
+# ---- lock detectors (lock_detectors.cc) ----
+def cn0_svn_estimator(prompts, coh_integration_time_s, move=(0, 0)):
+    """Sequential double sums (:68-85); move: ulp shifts of log10(SNR) and log10(T).  Returns a float32."""
+    psig = ptot = 0.0
+    for v in prompts:
+        re, im = float(v.real), float(v.imag)
+        psig += abs(re)
+        ptot += im * im + re * re
+    psig /= float(len(prompts))
+    psig = psig * psig
+    ptot /= float(len(prompts))
+    with np.errstate(all="ignore"):
+        snr = np.float64(psig) / np.float64(ptot - psig)
+        return f32(10.0 * moved(np.log10(snr), move[0]) - 10.0 * moved(np.log10(np.float64(coh_integration_time_s)), move[1]))
+
+
+def carrier_lock_detector(prompts):
+    """Sequential float sums (:97-111).  Returns a float32."""
+    si, sq = f32(0), f32(0)
+    for v in prompts:
+        si = f32(si + f32(v.real))
+        sq = f32(sq + f32(v.imag))
+    with np.errstate(all="ignore"):
+        return f32(f32(f32(si * si) - f32(sq * sq)) / f32(f32(si * si) + f32(sq * sq)))
+
+
+def lock_fail_update(fail, lock_test, cn0, pull_in, conf):
+    """The loss-of-lock counter of cn0_and_tracking_lock_status (:855-877): (new counter, still locked).  NaN compares false on both
+    sides of the `or`: an estimate that is not a number counts as a pass."""
+    if not pull_in:
+        if lock_test < conf["carrier_lock_th"] or cn0 < conf["cn0_min"]:
+            fail += 1
+        elif fail > 0:
+            fail -= 1
+    if fail > conf["max_lock_fail"]:
+        return 0, False
+    return fail, True
+
+
+def code_nco(doppler, cfilt, conf):
+    """d_code_freq_chips (:972)."""
+    return (1.0 + doppler / conf["signal_carrier_freq_hz"]) * conf["code_chip_rate_hz"] - cfilt
+
+
+def nco_update(code_freq, doppler, rem_code_samples, rem_carr, acc_phase, conf, carr_rate=None):
+    """update_tracking_vars (:998-1070) without the rate smoothers' histories: carr_rate(step, block length) gives the carrier
+    phase rate of the high-dynamics mode (None: 0).  Returns a dict of the new values."""
+    fs = conf["fs_in"]
+    T_prn = (1.0 / code_freq) * conf["code_length_chips"] * fs
+    K = T_prn + rem_code_samples
+    cur = int(np.floor(K))
+    step = PI_2 * doppler / fs
+    rate = carr_rate(step, float(cur)) if carr_rate else 0.0
+    adv = step * cur + 0.5 * rate * float(cur) * float(cur)
+    rem_carr = f32(f32(rem_carr) + f32(adv))
+    rem_carr = f32(np.fmod(rem_carr, f32(PI_2)))
+    rem = K - cur
+    return dict(cur=cur, step=step, carr_rate=rate, rem_carr=rem_carr, acc_phase=acc_phase - adv, code_step=code_freq / fs, rem_code_samples=rem,
+        rem_code_chips=code_freq * rem / fs)
+
+
+def pull_in(conf):
+    """The sample skip of state 1 (:1568-1600): (samples skipped, accumulated carrier phase after it)."""
+    fs = conf["fs_in"]
+    delta = float(conf["sample_counter"] - conf["acq_samplestamp_samples"]) - conf["acq_delay_samples"]
+    T_prn = (1.0 / conf["code_chip_rate_hz"]) * conf["code_length_chips"] * fs
+    offset = int(np.round(T_prn - np.fmod(delta, T_prn)))
+    return offset, 0.0 - (PI_2 * conf["acq_doppler_hz"] / fs) * offset
 
 
 class LoopFilter:
@@ -23,7 +156,7 @@ class LoopFilter:
     def design(self, T, bw):
         """update_coefficients: new coefficients, history untouched (set_noise_bandwidth / set_update_interval)."""
         order = self.order
-        T = f32(T)
+        T, bw = f32(T), float(f32(bw))  # both are floats in the reference; the arithmetic below widens where C widens
         zeta = f32(1.0 / np.sqrt(2.0))
         if order == 1:
             self.b, self.a = [f32(f32(bw * 4.0))], []
@@ -121,22 +254,16 @@ def run(oracle, x, code, conf, n_epochs, sync=None, data_code=None):
     rem_carr = f32(0.0)
     rem_code_samples = 0.0
     rem_code_chips = 0.0
-    acc_phase = 0.0
     sample_counter = conf["sample_counter"]
     acq_stamp = conf["acq_samplestamp_samples"]
     # pull-in
-    diff = sample_counter - acq_stamp
-    delta = float(diff) - conf["acq_delay_samples"]
     code_freq = conf["code_chip_rate_hz"]
     code_step = code_freq / fs
-    T_prn = (1.0 / code_freq) * conf["code_length_chips"] * fs
-    acq_code_phase = T_prn - np.fmod(delta, T_prn)
-    offset = int(np.round(acq_code_phase))
-    acc_phase -= step * offset
+    offset, acc_phase = pull_in(conf)
     sample_counter += offset
     pos = offset
     st = dict(state=2, cloop=True, corr_time=conf["code_period_s"], cur=N, prompt_buffer=[], cn0=0.0, lock_test=1.0, fail=0,
-        perr=0.0, cerr=0.0, hist=[], current_symbol=0, ext_count=0, pull_in=True, P_old=np.complex64(0))
+        perr=0.0, cerr=0.0, cfilt=0.0, hist=[], current_symbol=0, ext_count=0, pull_in=True, P_old=np.complex64(0))
     accu = np.zeros(5, np.complex64)  # VE E P L VL
     out = []
     # high dynamics (:1016-1033, :1047-1064)
@@ -159,37 +286,20 @@ def run(oracle, x, code, conf, n_epochs, sync=None, data_code=None):
             return True
         pb = np.array(st["prompt_buffer"], np.complex64)
         st["prompt_buffer"] = []
-        psig = np.mean(np.abs(pb.real.astype(np.float64))) ** 2
-        ptot = np.mean(pb.real.astype(np.float64) ** 2 + pb.imag.astype(np.float64) ** 2)
-        with np.errstate(all="ignore"):
-            st["cn0"] = float(f32(10 * np.log10(psig / (ptot - psig)) - 10 * np.log10(coh_time)))
-        si, sq = f32(0), f32(0)
-        for v in pb:
-            si = f32(si + v.real)
-            sq = f32(sq + v.imag)
-        st["lock_test"] = float(f32(f32(f32(si * si) - f32(sq * sq)) / f32(f32(si * si) + f32(sq * sq))))
-        if not st["pull_in"]:
-            if st["lock_test"] < conf["carrier_lock_th"] or st["cn0"] < conf["cn0_min"]:
-                st["fail"] += 1
-            elif st["fail"] > 0:
-                st["fail"] -= 1
-        if st["fail"] > conf["max_lock_fail"]:
-            st["fail"] = 0
-            return False
-        return True
+        st["cn0"] = float(cn0_svn_estimator(pb, coh_time))
+        st["lock_test"] = float(carrier_lock_detector(pb))
+        st["fail"], locked = lock_fail_update(st["fail"], st["lock_test"], st["cn0"], st["pull_in"], conf)
+        return locked
 
     def run_dll_pll():
         nonlocal doppler, code_freq
         P = accu[2]
         if st["cloop"]:
-            st["perr"] = (float(np.arctan(f32(P.imag / P.real))) if P.real != 0 else 0.0) / PI_2
+            st["perr"] = pll_cloop_two_quadrant_atan(P) / PI_2
         else:
-            st["perr"] = float(np.arctan2(f32(P.imag), f32(P.real))) / PI_2
+            st["perr"] = pll_four_quadrant_atan(P) / PI_2
         if (st["pull_in"] and conf["enable_fll_pull_in"]) or conf["enable_fll_steady_state"]:
-            po = st["P_old"]
-            dot = float(f32(f32(po.real * P.real) + f32(po.imag * P.imag)))
-            cross = float(f32(f32(po.real * P.imag) - f32(P.real * po.imag)))
-            ferr = np.arctan2(cross, dot) / st["corr_time"] / PI_2
+            ferr = fll_four_quadrant_atan(st["P_old"], P, 0.0, st["corr_time"]) / PI_2
             st["P_old"] = np.complex64(P)
             if st["pull_in"] and conf["enable_fll_pull_in"]:
                 doppler = float(pll.get_carrier_error(ferr, 0.0, st["corr_time"]))
@@ -198,33 +308,22 @@ def run(oracle, x, code, conf, n_epochs, sync=None, data_code=None):
         else:
             doppler = float(pll.get_carrier_error(0.0, st["perr"], st["corr_time"]))
         if veml:
-            pe = np.sqrt(float(f32(f32(accu[0].real * accu[0].real) + f32(accu[0].imag * accu[0].imag))) + float(f32(f32(accu[1].real * accu[1].real) + f32(accu[1].imag * accu[1].imag))))
-            pl = np.sqrt(float(f32(f32(accu[4].real * accu[4].real) + f32(accu[4].imag * accu[4].imag))) + float(f32(f32(accu[3].real * accu[3].real) + f32(accu[3].imag * accu[3].imag))))
-            st["cerr"] = 0.0 if pe + pl == 0 else (pe - pl) / (pe + pl)
+            st["cerr"] = dll_nc_vemlp_normalized(accu[0], accu[1], accu[3], accu[4])
         else:
-            pe, pl = float(f32(abs(accu[1]))), float(f32(abs(accu[3])))
-            st["cerr"] = 0.0 if pe + pl == 0 else 0.5 * (pe - pl) / (pe + pl)
-        cfilt = float(dll.apply(st["cerr"]))
-        code_freq = (1.0 + doppler / conf["signal_carrier_freq_hz"]) * conf["code_chip_rate_hz"] - cfilt
+            st["cerr"] = dll_nc_e_minus_l_normalized(accu[1], accu[3])
+        st["cfilt"] = float(dll.apply(st["cerr"]))
+        code_freq = code_nco(doppler, st["cfilt"], conf)
 
     def update_tracking_vars():
         nonlocal step, rem_carr, acc_phase, code_step, rem_code_samples, rem_code_chips
-        T_prn = (1.0 / code_freq) * conf["code_length_chips"] * fs
-        K = T_prn + rem_code_samples
-        cur = int(np.floor(K))
-        st["cur"] = cur
-        step = PI_2 * doppler / fs
+        u = nco_update(code_freq, doppler, rem_code_samples, rem_carr, acc_phase, conf,
+            carr_rate=(lambda s_, n_: smoothed(hd["carr"], s_, n_, hd["carr_rate"])) if sl else None)
+        cur = st["cur"] = u["cur"]
+        step, rem_carr, acc_phase, code_step = u["step"], u["rem_carr"], u["acc_phase"], u["code_step"]
         if sl:
-            hd["carr_rate"] = smoothed(hd["carr"], step, float(cur), hd["carr_rate"])
-        adv = step * cur + 0.5 * hd["carr_rate"] * float(cur) * float(cur)
-        rem_carr = f32(rem_carr + f32(adv))
-        rem_carr = f32(np.fmod(rem_carr, f32(PI_2)))
-        acc_phase -= adv
-        code_step = code_freq / fs
-        if sl:
+            hd["carr_rate"] = u["carr_rate"]
             hd["code_rate"] = smoothed(hd["code"], code_step, float(cur), hd["code_rate"])
-        rem_code_samples = K - cur
-        rem_code_chips = code_freq * rem_code_samples / fs
+        rem_code_samples, rem_code_chips = u["rem_code_samples"], u["rem_code_chips"]
 
     def save_correlation_results(taps):
         sign = 1.0
@@ -321,6 +420,6 @@ def run(oracle, x, code, conf, n_epochs, sync=None, data_code=None):
         sample_counter += cur
         pos += cur
         out.append(dict(corr=corr, doppler=doppler, code_freq=code_freq, cur=cur, sample_counter=sample_counter, cn0=st["cn0"], lock_test=st["lock_test"],
-            perr=st["perr"], cerr=st["cerr"], rem_code_samples=rem_code_samples, acc_phase=acc_phase, state=st["state"], state_in=state_in, valid=valid,
+            perr=st["perr"], cerr=st["cerr"], cfilt=st["cfilt"], pull_in=st["pull_in"], rem_code_samples=rem_code_samples, acc_phase=acc_phase, state=st["state"], state_in=state_in, valid=valid,
             integrating=integrating, accu=log_accu, ext_count=log_count, prompt_data=pdata, args=args, pos=pos_in, shifts=shifts_in))
     return out
