@@ -14,7 +14,9 @@ static constexpr int TRK_WINDOW_TARGET = 4096;      // floats of LDS per workgro
 static constexpr int TRK_CHUNK_SAMPLES = 512;       // samples a workgroup takes per step: slices are whole chunks
 
 // The arithmetic of a batch or of a level-1 code, indexed by the kernel's TRK_MODE_* (trk_kernels.h; gc_tracking.hip asserts the
-// order).  IQ formats as bits 1 << gc_iq_format (F32 1, I16 2, I8 4).
+// order).  IQ formats as bits 1 << gc_iq_format (F32 1, I16 2, I8 4): trk_launch (trk_kernels.hip) instantiates a kernel for exactly
+// these (mode, format) pairs and refuses the others.  No batch has TRK_MODE_HD_RESAMPLER; the level-1 object that selects it (the
+// 6-argument overload) correlates complex float input only.
 struct TrkFormatTraits
 {
     int words_per_chip;       // 4-byte words of the code table per chip
@@ -27,7 +29,7 @@ struct TrkFormatTraits
 };
 static constexpr TrkFormatTraits TRK_FORMAT_TRAITS[5] = {
     {1, 7u, 8, true, true, "real", "gc_trk_batch_set_code"},                         // TRK_MODE_PLAIN
-    {1, 7u, 8, true, false, "real", "gc_trk_batch_set_code"},                        // TRK_MODE_HD_RESAMPLER: the resampler's window is the
+    {1, 1u, 8, true, false, "real", "gc_trk_batch_set_code"},                        // TRK_MODE_HD_RESAMPLER: the resampler's window is the
     {1, 7u, 8, true, false, "real", "gc_trk_batch_set_code"},                        // TRK_MODE_HD_FULL:      whole epoch whatever the slice
     {2, 7u, 8, false, true, "complex float", "gc_trk_batch_set_code_complex"},       // TRK_MODE_COMPLEX_CODE
     {1, 2u, 4, false, false, "16-bit complex", "gc_trk_batch_set_code_16sc"},        // TRK_MODE_SC16
@@ -88,10 +90,11 @@ static inline TrkBatchPlan trk_batch_plan(int forced_slices, bool lds_sizing, in
             // (gc_trk_batch_run), else one code period per nominal window (device-resident records: a batch whose windows
             // span several code periods should state so with gc_trk_batch_set_slices(b, -1))
             const double chips_per_sample = max_step > 0.0f ? (double)max_step : (double)l_max / (double)len;
-            const int need = f.words_per_chip * ((int)std::ceil((double)cps * (double)TRK_CHUNK_SAMPLES * chips_per_sample * 1.002 + (double)spread) + TRK_LDS_MARGIN_FLOATS);
+            // (in double: a huge or garbage step must not overflow an int on its way to "the whole table")
+            const double need = (double)f.words_per_chip * (std::ceil((double)cps * (double)TRK_CHUNK_SAMPLES * chips_per_sample * 1.002 + (double)spread) + (double)TRK_LDS_MARGIN_FLOATS);
             // (a table that fits the 8-waves budget whole is left whole: nothing to gain, and windows of several code periods keep
-            // the LDS modulo path)
-            if (need < table_floats && table_floats > TRK_WINDOW_TARGET + 128) p.lds_floats = std::max((need + 63) & ~63, 1024);
+            // the LDS modulo path; so is one whose bound is not finite, not positive or not below the table)
+            if (std::isfinite(need) && need > 0.0 && need < (double)table_floats && table_floats > TRK_WINDOW_TARGET + 128) p.lds_floats = std::max(((int)need + 63) & ~63, 1024);
         }
     return p;
 }

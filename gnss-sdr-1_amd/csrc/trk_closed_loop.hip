@@ -133,7 +133,7 @@ __global__ __launch_bounds__(THREADS) void trk_closed_loop_slice_kernel(LoopChan
         }
     if (s_go)
         {
-            const float2 r = trk_epoch<NTAPS, HD, HD, FMT, false, false, THREADS, DATA, LOOP_PF, false, LOOP_NT != 0, LOOP_WHOLE != 0>(s.chan, s_p, slice, n_slices, lds_table_floats, lds, LOOP_ALIGN_PAIRS);
+            const float2 r = trk_epoch<LoopEpochPolicy<NTAPS, HD, FMT, THREADS, DATA>>(s.chan, s_p, slice, n_slices, lds_table_floats, lds, LOOP_ALIGN_PAIRS);
             if (tid < NOUT) s_corr[tid] = r;
         }
     __syncthreads();
@@ -706,8 +706,8 @@ static hipError_t loop_launch_slices(gc_trk_loop* l, const LoopLaunch& a, bool p
     const size_t lds_bytes = (size_t)(trk_hdr_floats(TH) + lds_table_floats) * sizeof(float);
     const unsigned grid = (unsigned)(((a.n_channels + 7) / 8) * n_slices * 8);
     LoopChan* d_chans = static_cast<LoopChan*>(a.d_state);
-    return loop_switch_format(l->iq_format, [&](auto fm) { return loop_switch_bool(l->kind.n_taps == 5, [&](auto veml) { return loop_switch_bool(pilot, [&](auto da) {
-        return loop_switch_bool(l->kind.high_dyn != 0, [&](auto hd) {
+    return trk_switch_format(l->iq_format, [&](auto fm) { return trk_switch_bool(l->kind.n_taps == 5, [&](auto veml) { return trk_switch_bool(pilot, [&](auto da) {
+        return trk_switch_bool(l->kind.high_dyn != 0, [&](auto hd) {
             const auto kernel = trk_closed_loop_slice_kernel<veml() ? 5 : 3, TH, fm(), da(), hd()>;
             if (lds_bytes > 48 * 1024)
                 {
@@ -741,8 +741,8 @@ static hipError_t loop_slices_reserve(gc_trk_loop* l, int n_slices, hipStream_t 
 // The persistent kernel of a plain engine: sample format, threads | high-dynamics, taps and data | pilot down to the instance's launch
 static hipError_t loop_launch_plain(const LoopLaunch& a, int n_taps, int iq_format, bool pilot, bool high_dyn)
 {
-    return loop_switch_format(iq_format, [&](auto fm) { return loop_switch_threads(a.plan.threads, high_dyn, [&](auto th, auto hd) {
-        return loop_switch_bool(n_taps == 5, [&](auto veml) { return loop_switch_bool(pilot, [&](auto da) {
+    return trk_switch_format(iq_format, [&](auto fm) { return trk_switch_threads(a.plan.threads, high_dyn, [&](auto th, auto hd) {
+        return trk_switch_bool(n_taps == 5, [&](auto veml) { return trk_switch_bool(pilot, [&](auto da) {
             return loop_launch_kernel(trk_closed_loop_kernel<veml() ? 5 : 3, th(), fm(), da(), hd()>, th(), a, a.plan.resident);
         }); });
     }); });

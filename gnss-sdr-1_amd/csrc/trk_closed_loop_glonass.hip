@@ -25,7 +25,7 @@ __global__ __launch_bounds__(THREADS) void trk_closed_loop_glonass_kernel(GloCha
 
 hipError_t glo_loop_launch(const LoopLaunch& a, int iq_format)
 {
-    return loop_switch_format(iq_format, [&](auto fm) {
-        return loop_switch_threads(a.plan.threads, false, [&](auto th, auto) { return loop_launch_kernel(trk_closed_loop_glonass_kernel<th(), fm()>, th(), a); });
+    return trk_switch_format(iq_format, [&](auto fm) {
+        return trk_switch_threads(a.plan.threads, false, [&](auto th, auto) { return loop_launch_kernel(trk_closed_loop_glonass_kernel<th(), fm()>, th(), a); });
     });
 }

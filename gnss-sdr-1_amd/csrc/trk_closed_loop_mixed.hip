@@ -33,8 +33,8 @@ __global__ __launch_bounds__(THREADS) void trk_closed_loop_mixed_kernel(LoopChan
 // the mixed kernel of a mixed engine (gc_trk_loop_set_mixed); high-dynamics engines take 256 threads like the persistent kernel
 hipError_t loop_launch_mixed(const LoopLaunch& a, int iq_format, bool high_dyn)
 {
-    return loop_switch_format(iq_format, [&](auto fm) {
-        return loop_switch_threads(a.plan.threads, high_dyn, [&](auto th, auto hd) {
+    return trk_switch_format(iq_format, [&](auto fm) {
+        return trk_switch_threads(a.plan.threads, high_dyn, [&](auto th, auto hd) {
             return loop_launch_kernel(trk_closed_loop_mixed_kernel<th(), fm(), hd()>, th(), a, a.plan.resident);
         });
     });

@@ -6,6 +6,7 @@
 #include "gnsscorr.h"
 #include "trk_kernels.h"
 #include "trk_loop_plan.h"  // trk_hdr_floats
+#include "trk_window_plan.h"
 #include <hip/hip_runtime.h>
 #include <type_traits>
 
@@ -15,44 +16,12 @@
 #define TRK_CHUNK (2 * TRK_THREADS)  // samples per workgroup iteration (2 per lane)
 #define TRK_HDR_FLOATS (TRK_THREADS / 64 * 16)
 #define TRK_RESYNC 64  // iterations between exact re-evaluations of the carrier phase
-#ifndef TRK_PF
-#define TRK_PF 2  // chunks prefetched ahead of the one being processed (16-byte loads in flight per lane)
-#endif
 #ifndef TRK_NT
 #define TRK_NT 1  // nontemporal IQ loads (0: plain): the stream is read once; with line-aligned chunks +5-7 % on the HBM-bound launch (alone: +1.5 %)
-#endif
-#ifndef TRK_PRELOAD
-#define TRK_PRELOAD 0  // the first two chunks of a window are requested before the workgroup's prologue (0: at the start of the loop)
 #endif
 #ifndef TRK_ALIGN_PAIRS
 #define TRK_ALIGN_PAIRS 8  // alignment, in sample pairs, of the address the chunks of a window are counted from (1 or 8)
 #endif
-
-static __device__ __forceinline__ int posmod(int i, int L)
-{
-    int r = i % L;
-    return r < 0 ? r + L : r;
-}
-
-// chip index before wrapping, generic resampler order: ((step*n) + shift) - rem
-static __device__ __forceinline__ int chip_index(float step, float nf, float shift, float rem)
-{
-    float a = step * nf;
-    float b = a + shift;
-    float c = b - rem;
-    return (int)floorf(c);
-}
-
-// high-dynamics first tap: (((step*n) + rate*(float)(n*n)) + shift0) - rem, n*n in uint32
-static __device__ __forceinline__ int chip_index_hd(float step, float rate, unsigned n, float shift0, float rem)
-{
-    float a = step * (float)n;
-    float r = rate * (float)(n * n);
-    float b = a + r;
-    float c = b + shift0;
-    float d = c - rem;
-    return (int)floorf(d);
-}
 
 // sum over the 64 lanes of a wave with DPP row shifts / broadcasts (no LDS traffic);
 // the total ends in lane 63
@@ -177,19 +146,22 @@ static __device__ __forceinline__ f32x4 trk_load_chunk(const GC_GLOBAL typename 
 //             component's replica, slaved to the pilot prompt tap (same shift pointer, same NCO scalars, hence
 //             the same chip index): table2 holds the data replica laid out like `table`; its sum goes to
 //             accr[NTAPS] / acci[NTAPS] (plain float mode only)
-//   PF      : full chunks kept in flight per lane ahead of the one being processed (2 everywhere: deeper queues were measured
-//             no faster in the batched kernel and slower in the closed-loop kernel)
-template <int NTAPS, bool HDR, bool HDC, bool WINDOWED, int FMT, bool CC = false, bool SC16 = false, int THREADS = TRK_THREADS, bool DATA = false, int PF = TRK_PF, bool NT = (TRK_NT != 0), bool WHOLE = true>
-static __device__ __forceinline__ void trk_loop(const GC_GLOBAL typename IqFmt<FMT>::elem* __restrict__ base, const float* __restrict__ table,
+// Two full chunks are kept in flight per lane ahead of the one being processed, everywhere: deeper queues were measured no faster in
+// the batched kernel and slower in the closed-loop kernel (4 in flight: 0.72 vs 0.68 ms for 256 channels x 64 periods -- a lone
+// workgroup per CU is bound by instruction issue at two waves per SIMD, not by loads in flight).
+// K: the kernel's policy struct (see trk_epoch)
+template <class K, bool WINDOWED>
+static __device__ __forceinline__ void trk_loop(const GC_GLOBAL typename IqFmt<K::FMT>::elem* __restrict__ base, const float* __restrict__ table,
     int a, int N, int V, int c0, int c1, int lo, int L, float step, float rem, float rate,
-    const float (&shifts)[NTAPS], const int (&tap_delay)[NTAPS], double theta0, double dtheta, double drate, float lnmod,
-    float (&accr)[NTAPS + (DATA ? 1 : 0)], float (&acci)[NTAPS + (DATA ? 1 : 0)], const float* __restrict__ table2,
-    int lc0, int lc1, f32x4 pre0, f32x4 pre1)
+    const float (&shifts)[K::NTAPS], const int (&tap_delay)[K::NTAPS], double theta0, double dtheta, double drate, float lnmod,
+    float (&accr)[K::NTAPS + (K::DATA ? 1 : 0)], float (&acci)[K::NTAPS + (K::DATA ? 1 : 0)], const float* __restrict__ table2,
+    int lc0, int lc1)
 {
     // lc0, lc1: chunks [lc0, lc1) lie inside the channel's buffer as WHOLE chunks (the ragged first / last chunk of a window usually
     // does: its neighbours in the stream are there), so they are fetched like the others -- 16-byte loads, prefetched -- and the
-    // samples outside the window zeroed in registers; pre0 / pre1: chunks c0 and c0 + 1 where they are such chunks, requested by
-    // the caller before its prologue (window fill, carrier angles), which then overlaps their latency
+    // samples outside the window zeroed in registers
+    constexpr int NTAPS = K::NTAPS, FMT = K::FMT, THREADS = K::THREADS;
+    constexpr bool HDR = K::HDR, HDC = K::HDC, CC = K::CC, SC16 = K::SC16, DATA = K::DATA, NT = K::NT, WHOLE = K::WHOLE;
     static_assert(!DATA || (!CC && !SC16), "the data-component correlator exists for real float replicas only");
     constexpr int CHUNK = 2 * THREADS;
     constexpr int PT = NTAPS / 2;  // prompt tap of E/P/L and VE/E/P/L/VL
@@ -402,10 +374,10 @@ static __device__ __forceinline__ void trk_loop(const GC_GLOBAL typename IqFmt<F
     };
 
     if (c0 >= c1) return;
-#if !TRK_PRELOAD
+    // the first two chunks of the slice, requested here where they may be fetched whole
+    f32x4 pre0 = {0.f, 0.f, 0.f, 0.f}, pre1 = {0.f, 0.f, 0.f, 0.f};
     if (loadable(c0)) pre0 = load_full(c0);
     if (c0 + 1 < c1 && loadable(c0 + 1)) pre1 = load_full(c0 + 1);
-#endif
     int c = c0;
     // ---- ragged head (at most one chunk) ----
     if (!chunk_is_full(c))
@@ -414,7 +386,7 @@ static __device__ __forceinline__ void trk_loop(const GC_GLOBAL typename IqFmt<F
             process(std::false_type{}, c, loadable(c) ? mask_window(c, pre0) : load_masked(c));
             ++c;
         }
-    // ---- interior: full chunks, TRK_PF loads in flight ahead of the chunk being processed ----
+    // ---- interior: full chunks, two loads in flight ahead of the chunk being processed ----
     const int cf1 = (c < c1 && !chunk_is_full(c1 - 1)) ? c1 - 1 : c1;
     if (c < cf1)
         {
@@ -424,66 +396,31 @@ static __device__ __forceinline__ void trk_loop(const GC_GLOBAL typename IqFmt<F
             // are then on their way when the tail asks for them; else the last full chunk; value unused): no branch
             // in the loop body, so the compiler can wait with vmcnt(1) and keep one load in flight
             const int clast = (cf1 < c1 && loadable(cf1)) ? cf1 : cf1 - 1;
-            if constexpr (PF == 2)
+            // chunks c0 and c0 + 1 were requested above where they may be fetched whole
+            f32x4 x0 = (c == c0) ? pre0 : (loadable(c0 + 1) ? pre1 : load_full(c));
+            f32x4 x1 = (c == c0 && c0 + 1 < c1 && loadable(c0 + 1)) ? pre1 : load_full(min(c + 1, clast));
+            while (c < cf1)
                 {
-                    // chunks c0 and c0 + 1 were requested by the caller where they may be fetched whole
-                    f32x4 x0 = (c == c0) ? pre0 : (loadable(c0 + 1) ? pre1 : load_full(c));
-                    f32x4 x1 = (c == c0 && c0 + 1 < c1 && loadable(c0 + 1)) ? pre1 : load_full(min(c + 1, clast));
-                    while (c < cf1)
+                    if ((c - c0) % TRK_RESYNC == 0) resync(c);
+                    const int gend = min(cf1, c0 + ((c - c0) / TRK_RESYNC + 1) * TRK_RESYNC);
+                    while (c + 2 <= gend)
                         {
-                            if ((c - c0) % TRK_RESYNC == 0) resync(c);
-                            const int gend = min(cf1, c0 + ((c - c0) / TRK_RESYNC + 1) * TRK_RESYNC);
-                            while (c + 2 <= gend)
-                                {
-                                    const f32x4 xa = x0;
-                                    x0 = load_full(min(c + 2, clast));
-                                    process(std::true_type{}, c, xa);
-                                    const f32x4 xb = x1;
-                                    x1 = load_full(min(c + 3, clast));
-                                    process(std::true_type{}, c + 1, xb);
-                                    c += 2;
-                                }
-                            if (c < gend)
-                                {
-                                    // odd chunk left in this group: the buffers swap roles
-                                    const f32x4 xa = x0;
-                                    x0 = x1;
-                                    x1 = load_full(min(c + 2, clast));
-                                    process(std::true_type{}, c, xa);
-                                    ++c;
-                                }
+                            const f32x4 xa = x0;
+                            x0 = load_full(min(c + 2, clast));
+                            process(std::true_type{}, c, xa);
+                            const f32x4 xb = x1;
+                            x1 = load_full(min(c + 3, clast));
+                            process(std::true_type{}, c + 1, xb);
+                            c += 2;
                         }
-                }
-            else
-                {
-                    // the same scheme with PF buffers: unrolled by PF, leftovers of a group one chunk at a time (the queue shifts)
-                    f32x4 x[PF];
-#pragma unroll
-                    for (int u = 0; u < PF; u++) x[u] = load_full(min(c + u, clast));
-                    while (c < cf1)
+                    if (c < gend)
                         {
-                            if ((c - c0) % TRK_RESYNC == 0) resync(c);
-                            const int gend = min(cf1, c0 + ((c - c0) / TRK_RESYNC + 1) * TRK_RESYNC);
-                            while (c + PF <= gend)
-                                {
-#pragma unroll
-                                    for (int u = 0; u < PF; u++)
-                                        {
-                                            const f32x4 xa = x[u];
-                                            x[u] = load_full(min(c + PF + u, clast));
-                                            process(std::true_type{}, c + u, xa);
-                                        }
-                                    c += PF;
-                                }
-                            while (c < gend)
-                                {
-                                    const f32x4 xa = x[0];
-#pragma unroll
-                                    for (int u = 0; u + 1 < PF; u++) x[u] = x[u + 1];
-                                    x[PF - 1] = load_full(min(c + PF, clast));
-                                    process(std::true_type{}, c, xa);
-                                    ++c;
-                                }
+                            // odd chunk left in this group: the buffers swap roles
+                            const f32x4 xa = x0;
+                            x0 = x1;
+                            x1 = load_full(min(c + 2, clast));
+                            process(std::true_type{}, c, xa);
+                            ++c;
                         }
                 }
         }
@@ -492,7 +429,7 @@ static __device__ __forceinline__ void trk_loop(const GC_GLOBAL typename IqFmt<F
         {
             if ((c - c0) % TRK_RESYNC == 0) resync(c);
             // (a window of two ragged chunks and nothing between them finds its tail in pre1)
-            process(std::false_type{}, c, loadable(c) ? mask_window(c, (c == c0 + 1 && PF == 2) ? pre1 : load_full(c)) : load_masked(c));
+            process(std::false_type{}, c, loadable(c) ? mask_window(c, (c == c0 + 1) ? pre1 : load_full(c)) : load_masked(c));
         }
 }
 
@@ -520,7 +457,6 @@ static __device__ void trk_loop_chips(B, A...);
 // it) in the LDS table across calls -- the closed-loop kernel, one workgroup per channel for many code periods: nothing is filled
 // here, a window [lo, hi] of up to L + TRK_RESIDENT_PAD chips is addressed inside the doubled image, longer ones through the first L
 // entries with the modulo form.  Same chips, same sums as the filled window.
-#define TRK_RESIDENT_PAD 64
 static __device__ __forceinline__ int trk_resident_floats(int L) { return 2 * L + TRK_RESIDENT_PAD; }
 template <int THREADS>
 static __device__ __forceinline__ void trk_fill_resident(float* lds, const float* code, const float* code2, int L)
@@ -542,11 +478,15 @@ static __device__ __forceinline__ void trk_fill_resident(float* lds, const float
 // GTAB: the launch may have been given LESS LDS than the whole code table needs (the batched kernel sizes its window by what a slice of
 // a nominal epoch touches: more workgroups per CU for long codes).  A record whose chips neither fit that window nor allow the whole
 // table in LDS then reads the table from global memory with the modulo form (slow, correct, rare: a code step far off the nominal one)
-template <int NTAPS, bool HDR, bool HDC, int FMT, bool CC = false, bool SC16 = false, int THREADS = TRK_THREADS, bool DATA = false, int PF = TRK_PF, bool CHIPS = false, bool NT = (TRK_NT != 0), bool WHOLE = true, bool GTAB = false>
+// K: the policy struct a kernel instantiates trk_epoch / trk_loop with, static constexpr members NTAPS, HDR, HDC, FMT, CC, SC16, THREADS,
+// DATA, CHIPS, NT, WHOLE, GTAB (above); one is defined next to each call site, with the reason for each setting
+template <class K>
 static __device__ __forceinline__ float2 trk_epoch(const TrkChan& cd, const gc_epoch_params& p, int slice, int n_slices,
     int lds_table_floats, float* lds, int align_pairs = TRK_ALIGN_PAIRS, bool resident = false)
 {
     // lds[0..HDRF): header (wave partials); then the code window
+    constexpr int NTAPS = K::NTAPS, FMT = K::FMT, THREADS = K::THREADS;
+    constexpr bool HDR = K::HDR, HDC = K::HDC, CC = K::CC, SC16 = K::SC16, DATA = K::DATA, CHIPS = K::CHIPS, GTAB = K::GTAB;
     static_assert(!CHIPS || (!HDR && !HDC && !CC && !SC16 && FMT == GC_IQ_F32), "the chip-domain loop exists for the plain float correlator");
     constexpr int CHUNK = CHIPS ? TRK_SEG : 2 * THREADS;  // unit of the slicing
     constexpr int HDRF = trk_hdr_floats(THREADS);
@@ -572,19 +512,13 @@ static __device__ __forceinline__ float2 trk_epoch(const TrkChan& cd, const gc_e
     const int c0 = slice * cps;
     const int c1 = min(n_chunks, c0 + cps);
     // Chunks [lc0, lc1) lie inside the channel's buffer as whole chunks: the ragged ends of a window are then fetched like its
-    // interior (trk_loop).  The first two chunks are requested HERE, before the prologue below, which hides their latency.
+    // interior (trk_loop).
     int lc0 = 0, lc1 = 0;
-    f32x4 pre0 = {0.f, 0.f, 0.f, 0.f}, pre1 = {0.f, 0.f, 0.f, 0.f};
     if (!CHIPS)
         {
             const unsigned long long end = cd.ring_len ? (unsigned long long)cd.ring_len : cd.n_iq;  // samples at cd.iq (a ring's mirror is not counted)
-            const unsigned long long room = end > off ? end - off : 0;
-            lc0 = off >= (unsigned long long)a ? 0 : 1;
-            lc1 = (int)min((unsigned long long)n_chunks, (room + (unsigned long long)a) / CHUNK);
-#if TRK_PRELOAD
-            if (c0 < c1 && c0 >= lc0 && c0 < lc1) pre0 = trk_load_chunk<FMT, THREADS, NT>(base, c0);
-            if (c0 + 1 < c1 && c0 + 1 >= lc0 && c0 + 1 < lc1) pre1 = trk_load_chunk<FMT, THREADS, NT>(base, c0 + 1);
-#endif
+            lc0 = trk_whole_first(off, a);
+            lc1 = trk_whole_end<CHUNK>(off, end, a, n_chunks);
         }
 
     const float step = p.code_phase_step_chips;
@@ -744,11 +678,11 @@ static __device__ __forceinline__ float2 trk_epoch(const TrkChan& cd, const gc_e
                 trk_loop_chips<NTAPS, false, THREADS, DATA>(base, table, table2, a, N, V, c0, c1, 0, L, step, rem, shifts, theta0, dtheta, scratch, accr, acci);
         }
     else if (windowed)
-        trk_loop<NTAPS, HDR, HDC, true, FMT, CC, SC16, THREADS, DATA, PF, NT, WHOLE>(base, table, a, N, V, c0, c1, lo, L, step, rem, rate, shifts, tap_delay, theta0, dtheta, drate, lnmod, accr, acci, table2, lc0, lc1, pre0, pre1);
+        trk_loop<K, true>(base, table, a, N, V, c0, c1, lo, L, step, rem, rate, shifts, tap_delay, theta0, dtheta, drate, lnmod, accr, acci, table2, lc0, lc1);
     else if (table_fits)
-        trk_loop<NTAPS, HDR, HDC, false, FMT, CC, SC16, THREADS, DATA, PF, NT, WHOLE>(base, table, a, N, V, c0, c1, 0, L, step, rem, rate, shifts, tap_delay, theta0, dtheta, drate, lnmod, accr, acci, table2, lc0, lc1, pre0, pre1);
+        trk_loop<K, false>(base, table, a, N, V, c0, c1, 0, L, step, rem, rate, shifts, tap_delay, theta0, dtheta, drate, lnmod, accr, acci, table2, lc0, lc1);
     else if constexpr (GTAB)
-        trk_loop<NTAPS, HDR, HDC, false, FMT, CC, SC16, THREADS, DATA, PF, NT, WHOLE>(base, reinterpret_cast<const float*>(cd.code), a, N, V, c0, c1, 0, L, step, rem, rate, shifts, tap_delay, theta0, dtheta, drate, lnmod, accr, acci, cd.code2, lc0, lc1, pre0, pre1);
+        trk_loop<K, false>(base, reinterpret_cast<const float*>(cd.code), a, N, V, c0, c1, 0, L, step, rem, rate, shifts, tap_delay, theta0, dtheta, drate, lnmod, accr, acci, cd.code2, lc0, lc1);
 
     // ---- reduction: lanes -> wave (shuffles) -> workgroup (LDS) ----
     __syncthreads();  // the code window has been consumed by every thread

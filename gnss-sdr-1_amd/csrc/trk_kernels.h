@@ -3,6 +3,7 @@
 #define TRK_KERNELS_H
 #include "gnsscorr.h"
 #include <hip/hip_runtime.h>
+#include <type_traits>
 
 #define GC_MAX_TAPS 8
 
@@ -35,9 +36,35 @@ enum
 // line_aligned: the chunks of a window are counted from the 128-byte boundary below its first sample (whole cache lines per wave
 // instruction: the streaming launches) instead of the 16-byte one (the level-1 calls, whose staging keeps a window's 16-byte phase so
 // that a call gives the same bits alone and in a batch).
+// TRK_FORMAT_TRAITS[mode].iq_formats (trk_batch_plan.h) lists the sample formats a mode has a kernel for: hipErrorInvalidValue for the others.
 bool trk_small_window_ok(int mode, int iq_format);
 hipError_t trk_launch(int n_taps, int mode, int iq_format, hipStream_t st, const TrkChan* chans,
     const gc_epoch_params* params, float2* out, float2* partial,
     int n_channels, int n_epochs, int n_slices, int lds_table_floats, bool line_aligned);
+
+// The runtime axes of a launch (this one's and the closed-loop engine's), each switched once: f is called with the value as a
+// std::integral_constant and instantiates the kernel from it.
+template <class F>
+static hipError_t trk_switch_format(int iq_format, F f)
+{
+    if (iq_format == GC_IQ_I16) return f(std::integral_constant<int, GC_IQ_I16>());
+    if (iq_format == GC_IQ_I8) return f(std::integral_constant<int, GC_IQ_I8>());
+    if (iq_format == GC_IQ_F32) return f(std::integral_constant<int, GC_IQ_F32>());
+    return hipErrorInvalidValue;  // (the setters refuse an unknown format long before a launch)
+}
+// f(threads, high_dyn): high-dynamics kernels always take 256 threads
+template <class F>
+static hipError_t trk_switch_threads(int threads, bool high_dyn, F f)
+{
+    if (high_dyn) return f(std::integral_constant<int, 256>(), std::true_type());
+    if (threads == 1024) return f(std::integral_constant<int, 1024>(), std::false_type());
+    if (threads == 512) return f(std::integral_constant<int, 512>(), std::false_type());
+    return f(std::integral_constant<int, 256>(), std::false_type());
+}
+template <class F>
+static hipError_t trk_switch_bool(bool on, F f)
+{
+    return on ? f(std::true_type()) : f(std::false_type());
+}
 
 #endif

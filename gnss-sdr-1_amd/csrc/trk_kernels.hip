@@ -20,6 +20,7 @@
 // reduced with wave shuffles, then across the 4 waves through LDS.  No MFMA:
 // 8 bytes of IQ per ~45 VALU operations is an HBM/VALU-bound complex MAC stream.
 #include "gc_internal.h"
+#include "trk_batch_plan.h"  // TRK_FORMAT_TRAITS: the sample formats of each mode
 #include "trk_device.hpp"
 
 #ifndef TRK_WAVES
@@ -30,6 +31,19 @@ static __device__ __forceinline__ short sat16(int v) { return (short)min(max(v, 
 #ifndef TRK_CHIPS_WAVES
 #define TRK_CHIPS_WAVES 4  // the chip-domain loop holds a lane's eight samples and the next segment's loads
 #endif
+// what the batched kernel instantiates trk_epoch with (trk_device.hpp)
+template <int NTAPS_, bool HDR_, bool HDC_, int FMT_, bool CC_, bool SC16_, bool CHIPS_>
+struct TrkBatchPolicy
+{
+    static constexpr int NTAPS = NTAPS_, FMT = FMT_;
+    static constexpr bool HDR = HDR_, HDC = HDC_, CC = CC_, SC16 = SC16_, CHIPS = CHIPS_;
+    static constexpr int THREADS = TRK_THREADS;
+    static constexpr bool DATA = false;        // the data component's correlator is the closed loop's
+    static constexpr bool NT = (TRK_NT != 0);  // every window streams once from HBM
+    static constexpr bool WHOLE = true;        // the ragged ends of a window take prefetched 16-byte loads like its interior
+    static constexpr bool GTAB = !CHIPS;       // launches sized below the table (trk_batch_plan.h); the chip-domain loop keeps the whole table in LDS
+};
+
 template <int NTAPS, bool HDR, bool HDC, int FMT, bool CC = false, bool SC16 = false, bool CHIPS = false>
 __global__ __launch_bounds__(TRK_THREADS, CHIPS ? TRK_CHIPS_WAVES : TRK_WAVES) void trk_multicorrelator_kernel(
     const TrkChan* __restrict__ chans, const gc_epoch_params* __restrict__ params,
@@ -65,7 +79,7 @@ __global__ __launch_bounds__(TRK_THREADS, CHIPS ? TRK_CHIPS_WAVES : TRK_WAVES) v
 
     const TrkChan cd = chans[ch];
     const gc_epoch_params p = params[job];
-    const float2 r = trk_epoch<NTAPS, HDR, HDC, FMT, CC, SC16, TRK_THREADS, false, TRK_PF, CHIPS, (TRK_NT != 0), true, !CHIPS>(cd, p, slice, n_slices, lds_table_floats, lds, align_pairs);
+    const float2 r = trk_epoch<TrkBatchPolicy<NTAPS, HDR, HDC, FMT, CC, SC16, CHIPS>>(cd, p, slice, n_slices, lds_table_floats, lds, align_pairs);
     if (threadIdx.x < NTAPS)
         {
             if (n_slices == 1)
@@ -140,64 +154,27 @@ bool trk_small_window_ok(int mode, int iq_format)
     return true;
 }
 
-template <int NTAPS, int FMT>
-static hipError_t launch_ntaps_fmt(int mode, dim3 grid, size_t lds_bytes, hipStream_t st,
-    const TrkChan* chans, const gc_epoch_params* params, float2* out, float2* partial,
-    int n_channels, int n_epochs, int n_slices, int lds_table_floats, int align_pairs)
+// the kernel's arithmetic switches per TRK_MODE_*; the sample formats of each come from TRK_FORMAT_TRAITS (trk_batch_plan.h)
+struct TrkModeSwitches
 {
-    switch (mode)
-        {
-        case TRK_MODE_PLAIN:
-#ifdef GNSSCORR_EXPERIMENTS
-            if (FMT == GC_IQ_F32 && trk_chip_domain() && trk_chips_lds_bytes(lds_table_floats) <= 64 * 1024)
-                {
-                    hipLaunchKernelGGL((trk_multicorrelator_kernel<NTAPS, false, false, GC_IQ_F32, false, false, true>), grid, dim3(TRK_THREADS),
-                        trk_chips_lds_bytes(lds_table_floats), st, chans, params, out, partial, n_channels, n_epochs, n_slices, lds_table_floats, align_pairs);
-                    break;
-                }
-#endif
-            hipLaunchKernelGGL((trk_multicorrelator_kernel<NTAPS, false, false, FMT>), grid, dim3(TRK_THREADS), lds_bytes, st,
-                chans, params, out, partial, n_channels, n_epochs, n_slices, lds_table_floats, align_pairs);
-            break;
-        case TRK_MODE_HD_RESAMPLER:
-            hipLaunchKernelGGL((trk_multicorrelator_kernel<NTAPS, true, false, FMT>), grid, dim3(TRK_THREADS), lds_bytes, st,
-                chans, params, out, partial, n_channels, n_epochs, n_slices, lds_table_floats, align_pairs);
-            break;
-        case TRK_MODE_HD_FULL:
-            hipLaunchKernelGGL((trk_multicorrelator_kernel<NTAPS, true, true, FMT>), grid, dim3(TRK_THREADS), lds_bytes, st,
-                chans, params, out, partial, n_channels, n_epochs, n_slices, lds_table_floats, align_pairs);
-            break;
-        case TRK_MODE_COMPLEX_CODE:
-            hipLaunchKernelGGL((trk_multicorrelator_kernel<NTAPS, false, false, FMT, true>), grid, dim3(TRK_THREADS), lds_bytes, st,
-                chans, params, out, partial, n_channels, n_epochs, n_slices, lds_table_floats, align_pairs);
-            break;
-        case TRK_MODE_SC16:
-            if (FMT != GC_IQ_I16) return hipErrorInvalidValue;  // lv_16sc_t in, lv_16sc_t out
-            hipLaunchKernelGGL((trk_multicorrelator_kernel<NTAPS, false, false, GC_IQ_I16, false, true>), grid, dim3(TRK_THREADS), lds_bytes, st,
-                chans, params, out, partial, n_channels, n_epochs, n_slices, lds_table_floats, align_pairs);
-            break;
-        default:
-            return hipErrorInvalidValue;
-        }
-    return hipGetLastError();
-}
+    bool hdr, hdc, cc, sc16;
+};
+static constexpr TrkModeSwitches TRK_MODE_SWITCHES[5] = {
+    {false, false, false, false},  // TRK_MODE_PLAIN
+    {true, false, false, false},   // TRK_MODE_HD_RESAMPLER
+    {true, true, false, false},    // TRK_MODE_HD_FULL
+    {false, false, true, false},   // TRK_MODE_COMPLEX_CODE
+    {false, false, false, true},   // TRK_MODE_SC16: lv_16sc_t in, lv_16sc_t out
+};
 
-template <int NTAPS>
-static hipError_t launch_ntaps(int mode, int fmt, dim3 grid, size_t lds_bytes, hipStream_t st,
-    const TrkChan* chans, const gc_epoch_params* params, float2* out, float2* partial,
-    int n_channels, int n_epochs, int n_slices, int lds_table_floats, int align_pairs)
+// f(std::integral_constant<int, v>) for v in [LO, HI]; hipErrorInvalidValue outside
+template <int LO, int HI, class F>
+static hipError_t trk_switch_int(int v, F f)
 {
-    switch (fmt)
-        {
-        case GC_IQ_F32:
-            return launch_ntaps_fmt<NTAPS, GC_IQ_F32>(mode, grid, lds_bytes, st, chans, params, out, partial, n_channels, n_epochs, n_slices, lds_table_floats, align_pairs);
-        case GC_IQ_I16:
-            return launch_ntaps_fmt<NTAPS, GC_IQ_I16>(mode, grid, lds_bytes, st, chans, params, out, partial, n_channels, n_epochs, n_slices, lds_table_floats, align_pairs);
-        case GC_IQ_I8:
-            return launch_ntaps_fmt<NTAPS, GC_IQ_I8>(mode, grid, lds_bytes, st, chans, params, out, partial, n_channels, n_epochs, n_slices, lds_table_floats, align_pairs);
-        default:
-            return hipErrorInvalidValue;
-        }
+    if constexpr (LO > HI)
+        return hipErrorInvalidValue;
+    else
+        return v == LO ? f(std::integral_constant<int, LO>()) : trk_switch_int<LO + 1, HI>(v, f);
 }
 
 hipError_t trk_launch(int n_taps, int mode, int iq_format, hipStream_t st, const TrkChan* chans,
@@ -208,31 +185,32 @@ hipError_t trk_launch(int n_taps, int mode, int iq_format, hipStream_t st, const
     const int epochs8 = n_epochs == 1 ? 1 : (n_epochs + 7) / 8 * 8;
     dim3 grid((unsigned)((size_t)epochs8 * n_channels * n_slices));
     size_t lds_bytes = (size_t)(TRK_HDR_FLOATS + lds_table_floats) * sizeof(float);
-    hipError_t e;
-#define CASE(NT)                                                                                       \
-    case NT:                                                                                           \
-        e = launch_ntaps<NT>(mode, iq_format, grid, lds_bytes, st, chans, params, out, partial, n_channels, n_epochs, \
-            n_slices, lds_table_floats, align_pairs);                                                  \
-        break;
-    switch (n_taps)
-        {
-#ifdef TRK_DEV_BUILD  // development builds: the bench's tap counts only (a full build takes minutes)
-            CASE(3)
-            CASE(5)
-#else
-            CASE(1)
-            CASE(2)
-            CASE(3)
-            CASE(4)
-            CASE(5)
-            CASE(6)
-            CASE(7)
-            CASE(8)
+    // one kernel per tap count and (mode, format) pair of TRK_FORMAT_TRAITS: the pairs no caller can reach are not compiled
+    hipError_t e = trk_switch_int<1, GC_MAX_TAPS>(n_taps, [&](auto nt) {
+        return trk_switch_int<TRK_MODE_PLAIN, TRK_MODE_SC16>(mode, [&](auto md) {
+            return trk_switch_format(iq_format, [&](auto fm) -> hipError_t {
+                constexpr int NTAPS = decltype(nt)::value, MODE = decltype(md)::value, FMT = decltype(fm)::value;
+                if constexpr ((TRK_FORMAT_TRAITS[MODE].iq_formats & (1u << FMT)) == 0)
+                    return hipErrorInvalidValue;
+                else
+                    {
+                        constexpr TrkModeSwitches m = TRK_MODE_SWITCHES[MODE];
+#ifdef GNSSCORR_EXPERIMENTS
+                        if constexpr (MODE == TRK_MODE_PLAIN && FMT == GC_IQ_F32)
+                            if (trk_chip_domain() && trk_chips_lds_bytes(lds_table_floats) <= 64 * 1024)
+                                {
+                                    hipLaunchKernelGGL((trk_multicorrelator_kernel<NTAPS, false, false, GC_IQ_F32, false, false, true>), grid, dim3(TRK_THREADS),
+                                        trk_chips_lds_bytes(lds_table_floats), st, chans, params, out, partial, n_channels, n_epochs, n_slices, lds_table_floats, align_pairs);
+                                    return hipGetLastError();
+                                }
 #endif
-        default:
-            return hipErrorInvalidValue;
-        }
-#undef CASE
+                        hipLaunchKernelGGL((trk_multicorrelator_kernel<NTAPS, m.hdr, m.hdc, FMT, m.cc, m.sc16>), grid, dim3(TRK_THREADS), lds_bytes, st,
+                            chans, params, out, partial, n_channels, n_epochs, n_slices, lds_table_floats, align_pairs);
+                        return hipGetLastError();
+                    }
+            });
+        });
+    });
     if (e != hipSuccess) return e;
     if (n_slices > 1)
         {

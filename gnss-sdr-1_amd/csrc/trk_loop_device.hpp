@@ -21,10 +21,6 @@
 #define LOOP_ALIGN_PAIRS 1  // chunk grid of a window: the 16-byte one (the batched kernel's 128-byte grid makes nearly every period start with
                             // a ragged chunk: 0.710 vs 0.689 ms)
 #endif
-#ifndef LOOP_PF
-#define LOOP_PF 2  // 16-byte loads in flight per lane; 4 was measured slower (0.72 vs 0.68 ms for 256 channels x 64 periods): a lone
-                   // workgroup per CU is bound by instruction issue at two waves per SIMD, not by loads in flight
-#endif
 #define LOOP_MAX_SMOOTHER 16
 #define LOOP_PI_2 6.283185307179586
 
@@ -723,6 +719,19 @@ struct VemlLoopKind
     static __device__ __forceinline__ void after_correlation(LoopChan& s, const float2* taps, gc_loop_record* rec) { loop_after_correlation<NTAPS, DATA>(s, taps, rec); }
 };
 
+// what the closed-loop kernels instantiate trk_epoch with (trk_device.hpp): real float replicas, one high-dynamics switch for the
+// resampler and the rotator, and the settings measured above (LOOP_NT, LOOP_WHOLE)
+template <int NTAPS_, bool HD_, int FMT_, int THREADS_, bool DATA_>
+struct LoopEpochPolicy
+{
+    static constexpr int NTAPS = NTAPS_, FMT = FMT_, THREADS = THREADS_;
+    static constexpr bool HDR = HD_, HDC = HD_, DATA = DATA_;
+    static constexpr bool CC = false, SC16 = false, CHIPS = false;
+    static constexpr bool NT = (LOOP_NT != 0);
+    static constexpr bool WHOLE = (LOOP_WHOLE != 0);
+    static constexpr bool GTAB = false;  // the launch's LDS holds the longest code's table (trk_loop_plan.h)
+};
+
 // The n_epochs code periods of one channel whose state `s` the workgroup holds in LDS (crec: the channel's first record): the
 // body shared by the persistent kernel (one kind per launch), the mixed kernel (one per channel) and the GLONASS kernel.
 template <class KIND, int THREADS, int FMT>
@@ -752,7 +761,7 @@ static __device__ __forceinline__ void loop_periods(typename KIND::State& s, gc_
             __syncthreads();
             if (!s_go) continue;  // uniform: every later epoch of this launch is skipped the same way
 
-            const float2 r = trk_epoch<NTAPS, HD, HD, FMT, false, false, THREADS, DATA, LOOP_PF, false, LOOP_NT != 0, LOOP_WHOLE != 0>(s.chan, s_p, 0, 1, lds_table_floats, lds, LOOP_ALIGN_PAIRS, resident != 0);
+            const float2 r = trk_epoch<LoopEpochPolicy<NTAPS, HD, FMT, THREADS, DATA>>(s.chan, s_p, 0, 1, lds_table_floats, lds, LOOP_ALIGN_PAIRS, resident != 0);
             if (tid < NTAPS + (DATA ? 1 : 0)) s_corr[tid] = r;
             __syncthreads();
 
@@ -809,28 +818,7 @@ static hipError_t loop_launch_kernel(void (*kernel)(State*, gc_loop_record*, int
     return hipGetLastError();
 }
 
-// The runtime axes of a launch, each switched once: f is called with the value as a std::integral_constant.
-template <class F>
-static hipError_t loop_switch_format(int iq_format, F f)
-{
-    if (iq_format == GC_IQ_I16) return f(std::integral_constant<int, GC_IQ_I16>());
-    if (iq_format == GC_IQ_I8) return f(std::integral_constant<int, GC_IQ_I8>());
-    return f(std::integral_constant<int, GC_IQ_F32>());
-}
-// f(threads, high_dyn): high-dynamics kernels always take 256 threads
-template <class F>
-static hipError_t loop_switch_threads(int threads, bool high_dyn, F f)
-{
-    if (high_dyn) return f(std::integral_constant<int, 256>(), std::true_type());
-    if (threads == 1024) return f(std::integral_constant<int, 1024>(), std::false_type());
-    if (threads == 512) return f(std::integral_constant<int, 512>(), std::false_type());
-    return f(std::integral_constant<int, 256>(), std::false_type());
-}
-template <class F>
-static hipError_t loop_switch_bool(bool on, F f)
-{
-    return on ? f(std::true_type()) : f(std::false_type());
-}
+// The runtime axes of a launch are each switched once, with trk_switch_format / trk_switch_threads / trk_switch_bool (trk_kernels.h).
 
 // the mixed kernel's launch (trk_closed_loop_mixed.hip)
 hipError_t loop_launch_mixed(const LoopLaunch& a, int iq_format, bool high_dyn);

@@ -17,7 +17,8 @@ test_open_loop_matrix_inputs.py asserts each is taken.  Every launch runs with 1
 High-dynamics modes: the taps are tap 0 delayed by whole samples and wrapped at N, and the reference needs the delays below N (it
 memcpy()s N - delay floats), so their windows of 1 and 2 samples are 64 samples longer, as in test_fuzz_gpu.py.  The high-dynamics
 resampler with the plain rotator (TRK_MODE_HD_RESAMPLER) is reached through the level-1 object's 6-argument overload alone, whose
-input is float: LEVEL1_ONLY below is the one place that says so.
+input is float: TRK_FORMAT_TRAITS (trk_batch_plan.h) gives that mode the F32 format only, trk_launch compiles no other kernel for it, and
+LEVEL1_ONLY below says how the matrix reaches it.
 
 Smaller tables: RESYNC (a window of 66 chunks and 77 samples, carrier step 1.3 rad per sample: the exact re-evaluation of the rotators
 every 64 chunks), TABLE PATHS (L = 8184, or 7936 complex chips, N = 4608, 2 slices, records on the device: the launch's LDS is below the table, one record
@@ -140,8 +141,8 @@ def build_selftest(directory):
 
 
 def reachable(exe):
-    """{(n_taps, mode, fmt)} a caller can reach: GC_MAX_TAPS tap counts x the sample formats TRK_FORMAT_TRAITS gives each mode, less
-    LEVEL1_ONLY's restriction."""
+    """{(n_taps, mode, fmt)} a caller can reach: GC_MAX_TAPS tap counts x the sample formats TRK_FORMAT_TRAITS gives each mode (the
+    ones trk_launch compiles a kernel for), of which a mode of LEVEL1_ONLY can take its listed ones."""
     out = subprocess.run([exe, "traits"], capture_output=True, text=True, timeout=60, check=True).stdout.splitlines()
     assert out[0].split()[0] == "max_taps" and len(out) == 1 + len(MODES), out
     keys = set()

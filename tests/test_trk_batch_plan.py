@@ -10,7 +10,8 @@ rules (integer divisions round down):
               slices > 1: cps = ceil((len + 16 + 511) / 512 / slices) chunks per slice, chips per sample = max_step when the records
                 are on the host, else l_max / len;
                 need = words per chip * (ceil(cps * 512 * chips per sample * 1.002 + widest tap spread) + 64)
-                need < table and table > 4096 + 128: window = max(need rounded up to 64, 1024)
+                need < table and table > 4096 + 128: window = max(need rounded up to 64, 1024); need is compared as a double, so a
+                huge or non-finite step leaves the table whole
   level 1   N <= one_wg_max: 1; else max((N + 1 + 511) / 512 / 2, 1); at most what the partial buffer holds
 
 An argument is `forced,sizing,epochs,CUs,format,small_window_ok,len,max_step,table / COUNTxL,shifts...` per channel group; format 0
@@ -69,6 +70,8 @@ TABLE = [
     ("0,1,1,256,0,1,100000,1.0,8248" + E1, "49 2176"),
     # ... a step that needs more than the table: whole (2048 * 5.0 * 1.002 + 1.0 = 10261.48 -> 10262 + 64 = 10326 >= 8248)
     ("0,1,1,256,0,1,100000,5.0,8248" + E1, "49 8248"),
+    # ... a huge step: 2048 * 1e9 * 1.002 = 2.05e12 is past what an int holds; the bound is compared as a double, the table stays whole
+    ("0,1,1,256,0,1,100000,1e9,8248" + E1, "49 8248"),
     # the widest tap spread of any channel (100.25, the second one's) and the longest code of any (the first one's); 2 jobs: still 49 slices:
     # 2052.096 + 100.25 = 2152.35 -> 2153 + 64 = 2217 -> 2240
     ("0,1,1,256,0,1,100000,1.0,8248/1x8184,-0.5,0,0.5/1x1023,-50,0,50.25", "49 2240"),
